@@ -13,7 +13,14 @@ the ranks (strong scaling: 18 candidates in total, whatever N is).
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 ...
 
 Prints ONE JSON line (rank 0).  Synthetic data: seeded random-init weights of
-the exact architectures and a synthetic 256x256 target (no network here).
+the exact architectures and a synthetic 256x256 target (no network here), so
+the same arguments give the same inputs on every run.
+
+A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...).  --full adds the side measurements: per-launch
+roofline legs, re-score rate, telemetry, the exact-fp32 leg, the other
+BASELINE configurations and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step returned (out, loss, z, c) as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -628,6 +635,14 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure, run every side measurement: the per-launch roofline legs, the '
+                         'forward-only re-score rate, telemetry, the exact-fp32 leg, the other configurations and the '
+                         'CPU baseline (the --no-* options below leave single ones out).  Default: set-up, warm-up, '
+                         'the timed steps and the result line only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what their last step returned as DIR/<name>.npy (float32): '
+                         'out (the rendered images), loss (per candidate) and the latents the Adam step left, z and c')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--prof-period', type=int, default=20,
                     help='time every N-th conv launch with hipEvents inside the timed steps '
@@ -660,7 +675,8 @@ def main():
                          'after the other); 18 = one pass of the whole population on one stream')
     args = ap.parse_args()
     if args.pmc_run:
-        args.eager = args.no_alone = args.no_fp32_leg = args.no_extra = args.no_cpu_baseline = True
+        # (the per-launch record is built from the event pairs inside the timed steps)
+        args.full = args.eager = args.no_alone = args.no_fp32_leg = args.no_extra = args.no_cpu_baseline = True
 
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -725,45 +741,24 @@ def main():
     # step); time every PERIOD-th launch, rotating the phase with the step, so that each
     # launch of the step is timed once per PERIOD steps
     period = max(1, min(args.prof_period, args.steps))
-    if not graph_timed:
+    events_timed = args.full and not graph_timed
+    if events_timed:
         N.check(lib.p2l_prof_begin(n_prof), 'p2l_prof_begin')
-    with _GpuTelemetry(local_rank, enabled=not args.no_telemetry) as telemetry:
+    with _GpuTelemetry(local_rank, enabled=args.full and not args.no_telemetry) as telemetry:
         t0 = time.perf_counter()
         for i in range(args.steps):
-            if not graph_timed:
+            if events_timed:
                 lib.p2l_prof_step(i, period)
             opt.step(variables, optimize=True)
         sync()
         elapsed = time.perf_counter() - t0
     graph_replayed = graph_timed and replaying()
-    if graph_timed:
-        # the launches of the same two-lane step, eagerly, with event pairs: the leg `roofline.concurrent` (or,
-        # without lanes, the top-level record) is built from
-        saved_graph, opt.use_graph = opt.use_graph, False
-        ev_steps = max(period, min(args.steps, 20))
-        opt.step(variables, optimize=True)
-        sync()
-        N.check(lib.p2l_prof_begin(n_prof), 'p2l_prof_begin')
-        t0e = time.perf_counter()
-        for i in range(ev_steps):
-            lib.p2l_prof_step(i, period)
-            opt.step(variables, optimize=True)
-        sync()
-        ev_elapsed = time.perf_counter() - t0e
-        opt.use_graph = saved_graph
-    else:
-        ev_steps, ev_elapsed = args.steps, elapsed
-    T = N.prof_totals()
-    last_loss = [float(x) for x in opt.loss]     # (sharded: the one all-gather, on every rank)
-    # SURVEY 8(d) also asks for the fwd-only rate (the CMA re-score); outside the timed K steps
-    sync()
-    t1 = time.perf_counter()
-    n_rescore = 0 if args.pmc_run else 3
-    for _ in range(n_rescore):
-        opt.step(variables, optimize=False)
-    sync()
-    rescore_rate = POP * n_rescore / (time.perf_counter() - t1) if n_rescore else 0.0
-
+    # (before any leg below runs more steps on the same variables)
+    if args.dump_outputs:
+        dump_outputs(opt, variables, args.dump_outputs, world, rank)
+    if args.full:
+        full_record = side_measurements(args, opt, variables, lib, world, rank, sync, elapsed, graph_timed, period,
+                                        n_prof, lanes_used)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -774,65 +769,6 @@ def main():
         # generator fwd+dgrad 58.80 GMAC + LPIPS net fwd+dgrad (VGG16 40.08 | AlexNet 1.74 GMAC)
         gflop_eval = GFLOP_PER_EVAL if args.lpips_net == 'vgg' else 2 * (58.80 + 1.737)
         bf3 = N.default_wfmt() != N.WFMT_F32
-        # what the timed steps measured.  With two lanes a launch's hipEvent pair also spans the time it
-        # shares the GPU with the OTHER lane's launches: the step is faster, every launch looks slower, and
-        # the durations sum to more than the step -- reported, but not as the kernel's figure
-        timed = family_record(T, ev_steps, ev_elapsed, period, bf3, args.exec_batch, lanes_used)
-        if world > 1:
-            # a rank's launches hold its block of the population (2 ... 9 candidates), not an execution batch the
-            # single-GPU PMC passes were taken at: no traffic figure rather than one that belongs to other launches
-            timed['traffic'] = timed['traffic_read_write'] = None
-            timed['traffic_source'] = {'refused': 'PMC passes exist for single-GPU execution batches only; this '
-                                                  'rank launches its block of %d ranks' % world}
-            timed['exec_batch_size'] = 'rank-local block (population %d over %d ranks)' % (POP, world)
-        kernel_text = (
-            'every 3x3 conv launch of the step: wino16s_conv_kernel<.., H2> (Winograd F(2x2,3x3), '
-            '16x16-pixel blocks, hand-scheduled; fp16 x 2 arithmetic: power-of-two scaled operands '
-            'in two fp16 pieces, 3 x v_mfma_f32_32x32x16_f16 per product; per-image maxima handed '
-            'over by the launch that wrote the input, wino_amax_kernel where none did), '
-            'conv_h2_kernel<TAPS=9|4> (direct | sub-pixel, the same fp16 x 2 arithmetic) and '
-            'conv_thinin/thinout_kernel (3-channel image convs) in the bf16 x 3 arithmetic (6 x '
-            'v_mfma_f32_32x32x16_bf16 per product on 3-way split fp32 operands); `dominant_kernel` names the one '
-            'that takes the most time' if bf3 else
-            'conv_mfma_kernel<TAPS=9> (3x3 implicit GEMM, v_mfma_f32_32x32x2_f32)')
-        # achieved / peak / frac are what the matrix pipe EXECUTES -- 16-bit MFMA
-        # FLOP/s issued by these launches (3 products per fp32 product for the fp16 x 2 launches, 6 for bf16
-        # x 3; Winograd launches 16 instead of 36 products per output quad, sub-pixel launches 4
-        # phase-taps, image convs their padded channels) over the dense 16-bit MFMA peak.
-        roof = {'kernel': kernel_text, 'bound': 'mfma'}
-        if lanes_used > 1 and world == 1 and not args.no_alone:
-            # the TOP-LEVEL figures are the kernels' own -- the same build, the same
-            # launches with nothing beside them: one pass of the 18 candidates on one stream, 8 more steps
-            # right after the timed region, every launch timed twice.  What the launches get while the two
-            # lanes overlap is under `concurrent`.
-            Ta, el_a, st_a, per_a = alone_leg(opt, variables, lib)
-            roof.update(family_record(Ta, st_a, el_a, per_a, bf3, POP, 1))
-            roof['measured'] = ('one pass of %d candidates on one stream (exec_batch_size = population), %d steps '
-                                'right after the timed region, hipEvent pairs on the launch stream around every '
-                                '%d-th conv launch, phase rotating with the step: NON-overlapped launch durations. '
-                                'The timed steps themselves run the reference chunks on %d lanes: see `concurrent`'
-                                % (POP, st_a, per_a, lanes_used))
-            conc = {k: timed[k] for k in ('exec_batch_size', 'lanes', 'achieved', 'frac', 'avg_launch_ms',
-                                          'sampled_launches', 'launches_per_step', 'time_share_of_step',
-                                          'algo_bytes_per_launch', 'traffic', 'traffic_source', 'traffic_read_write')}
-            conc['dominant_kernel'] = timed['dominant_kernel']
-            conc['conv1x1'] = timed['conv1x1']
-            conc['what'] = ('the launches of the timed configuration (reference chunks of %d on %d HIP streams), %s: a '
-                            'hipEvent pair spans the time a launch shares the GPU with the other lane, so these '
-                            'durations overlap -- time_share_of_step sums overlapping intervals and may exceed 1 -- '
-                            'and `achieved` is what a launch gets while overlapped, not what the kernel does'
-                            % (args.exec_batch, lanes_used,
-                               ('%d eager steps right behind the timed region (%.3f ms per step; the timed steps '
-                                'replay a HIP graph, which cannot hold event pairs)'
-                                % (ev_steps, 1e3 * ev_elapsed / ev_steps)) if graph_timed else 'inside the timed steps'))
-            roof['concurrent'] = conc
-        else:
-            roof.update(timed)
-            roof['measured'] = (('%d eager steps right behind the timed region' % ev_steps if graph_timed else
-                                 'the timed steps') + ': hipEvent pairs on the launch stream around every %d-th conv '
-                                'launch, phase rotating with the step' % period) + (
-                '; %d lanes: durations overlap (see DESIGN section 6)' % lanes_used if lanes_used > 1 else '')
-        roof['launch_sampling'] = 'every %d-th conv launch of the event legs timed (hipEvent pairs)' % period
         rec = {
             'metric': 'candidate-latent evals/sec (fwd+loss+bwd), BigGAN-256 pop=18',
             'value': round(evals / elapsed, 3),
@@ -871,35 +807,150 @@ def main():
                 'hip_graph_replay': bool(graph_replayed),
                 'timed_steps_run_as': ('one HIP graph per step, replayed (two branches = the two lanes): the default of '
                                        'optimize() for this configuration' if graph_replayed else
-                                       'eager launches' + (' with hipEvent pairs inside' if not graph_timed else '')),
+                                       'eager launches' + (' with hipEvent pairs inside' if events_timed else '')),
                 'gflop_per_eval_basis': gflop_eval,
                 'end_to_end_tflops': round(gflop_eval * evals / elapsed / 1e3, 2),
-                'fwd_only_rescore_evals_per_s': round(rescore_rate, 1),
-                'last_losses_min_max': [round(min(last_loss), 5), round(max(last_loss), 5)],
-                'last_losses': [round(x, 6) for x in last_loss],
             },
-            'roofline': roof,
-            'telemetry': telemetry.summary(),
         }
-        if world == 1 and bf3 and not args.no_fp32_leg:
-            # the same steps with every conv on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32),
-            # reported beside `value` so the arithmetic choice is visible in one line
-            rec['config']['exact_fp32_mfma_evals_per_s'] = round(exact_fp32_leg(dev, args), 1)
-        if world == 1 and not args.no_extra:
-            try:
-                rec['config']['extra'] = extra_configs(dev)
-            except Exception as e:          # the headline must not be lost to a side measurement
-                rec['config']['extra'] = {'error': repr(e)[:300]}
-            try:
-                rec['config']['extra'].update(full_schedule_and_default_loss(dev, 1e3 * elapsed / args.steps))
-            except Exception as e:
-                rec['config']['extra']['full_schedule_error'] = repr(e)[:300]
-        if world == 1 and not args.no_cpu_baseline:
-            rec['cpu_baseline'] = cpu_baseline(problem)
+        if args.full:
+            rec['config'].update(full_record['config'])
+            rec['roofline'] = full_record['roofline']
+            rec['telemetry'] = telemetry.summary()
+            if world == 1 and bf3 and not args.no_fp32_leg:
+                # the same steps with every conv on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32),
+                # reported beside `value` so the arithmetic choice is visible in one line
+                rec['config']['exact_fp32_mfma_evals_per_s'] = round(exact_fp32_leg(dev, args), 1)
+            if world == 1 and not args.no_extra:
+                try:
+                    rec['config']['extra'] = extra_configs(dev)
+                except Exception as e:          # the headline must not be lost to a side measurement
+                    rec['config']['extra'] = {'error': repr(e)[:300]}
+                try:
+                    rec['config']['extra'].update(full_schedule_and_default_loss(dev, 1e3 * elapsed / args.steps))
+                except Exception as e:
+                    rec['config']['extra']['full_schedule_error'] = repr(e)[:300]
+            if world == 1 and not args.no_cpu_baseline:
+                rec['cpu_baseline'] = cpu_baseline(problem)
         print(json.dumps(rec), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(opt, variables, out_dir, world, rank):
+    """what the caller of the timed step receives after its last step: the images and per-candidate losses it
+    returns, and the latents its Adam update left in `variables` -- float32, 18 x 3 x 256 x 256 images = 14 MB"""
+    if world > 1:
+        opt.gather_population(variables)          # (a collective: every rank takes part)
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'out': opt.out.detach().float().cpu().numpy(),
+              'loss': np.asarray([float(x) for x in opt.loss], dtype=np.float32)}
+    for name, v in variables.input.items():
+        arrays[name] = torch.stack(list(v.data)).detach().float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def side_measurements(args, opt, variables, lib, world, rank, sync, elapsed, graph_timed, period, n_prof, lanes_used):
+    """--full: the measurements behind the timed steps that need the bench problem as the timed steps left it -- the
+    per-launch roofline legs, the losses of the last step and the forward-only re-score rate"""
+    from pix2latent_amd import _native as N
+    if graph_timed:
+        # the launches of the same two-lane step, eagerly, with event pairs: the leg `roofline.concurrent` (or,
+        # without lanes, the top-level record) is built from
+        saved_graph, opt.use_graph = opt.use_graph, False
+        ev_steps = max(period, min(args.steps, 20))
+        opt.step(variables, optimize=True)
+        sync()
+        N.check(lib.p2l_prof_begin(n_prof), 'p2l_prof_begin')
+        t0e = time.perf_counter()
+        for i in range(ev_steps):
+            lib.p2l_prof_step(i, period)
+            opt.step(variables, optimize=True)
+        sync()
+        ev_elapsed = time.perf_counter() - t0e
+        opt.use_graph = saved_graph
+    else:
+        ev_steps, ev_elapsed = args.steps, elapsed
+    T = N.prof_totals()
+    last_loss = [float(x) for x in opt.loss]     # (sharded: the one all-gather, on every rank)
+    # SURVEY 8(d) also asks for the fwd-only rate (the CMA re-score); outside the timed K steps
+    sync()
+    t1 = time.perf_counter()
+    n_rescore = 0 if args.pmc_run else 3
+    for _ in range(n_rescore):
+        opt.step(variables, optimize=False)
+    sync()
+    rescore_rate = POP * n_rescore / (time.perf_counter() - t1) if n_rescore else 0.0
+    if rank != 0:
+        return None
+
+    bf3 = N.default_wfmt() != N.WFMT_F32
+    # what the timed steps measured.  With two lanes a launch's hipEvent pair also spans the time it
+    # shares the GPU with the OTHER lane's launches: the step is faster, every launch looks slower, and
+    # the durations sum to more than the step -- reported, but not as the kernel's figure
+    timed = family_record(T, ev_steps, ev_elapsed, period, bf3, args.exec_batch, lanes_used)
+    if world > 1:
+        # a rank's launches hold its block of the population (2 ... 9 candidates), not an execution batch the
+        # single-GPU PMC passes were taken at: no traffic figure rather than one that belongs to other launches
+        timed['traffic'] = timed['traffic_read_write'] = None
+        timed['traffic_source'] = {'refused': 'PMC passes exist for single-GPU execution batches only; this '
+                                              'rank launches its block of %d ranks' % world}
+        timed['exec_batch_size'] = 'rank-local block (population %d over %d ranks)' % (POP, world)
+    kernel_text = (
+        'every 3x3 conv launch of the step: wino16s_conv_kernel<.., H2> (Winograd F(2x2,3x3), '
+        '16x16-pixel blocks, hand-scheduled; fp16 x 2 arithmetic: power-of-two scaled operands '
+        'in two fp16 pieces, 3 x v_mfma_f32_32x32x16_f16 per product; per-image maxima handed '
+        'over by the launch that wrote the input, wino_amax_kernel where none did), '
+        'conv_h2_kernel<TAPS=9|4> (direct | sub-pixel, the same fp16 x 2 arithmetic) and '
+        'conv_thinin/thinout_kernel (3-channel image convs) in the bf16 x 3 arithmetic (6 x '
+        'v_mfma_f32_32x32x16_bf16 per product on 3-way split fp32 operands); `dominant_kernel` names the one '
+        'that takes the most time' if bf3 else
+        'conv_mfma_kernel<TAPS=9> (3x3 implicit GEMM, v_mfma_f32_32x32x2_f32)')
+    # VERDICT round 3 #11: achieved / peak / frac are what the matrix pipe EXECUTES -- 16-bit MFMA
+    # FLOP/s issued by these launches (3 products per fp32 product for the fp16 x 2 launches, 6 for bf16
+    # x 3; Winograd launches 16 instead of 36 products per output quad, sub-pixel launches 4
+    # phase-taps, image convs their padded channels) over the dense 16-bit MFMA peak.
+    roof = {'kernel': kernel_text, 'bound': 'mfma'}
+    if lanes_used > 1 and world == 1 and not args.no_alone:
+        # VERDICT round 5 #3: the TOP-LEVEL figures are the kernels' own -- the same build, the same
+        # launches with nothing beside them: one pass of the 18 candidates on one stream, 8 more steps
+        # right after the timed region, every launch timed twice.  What the launches get while the two
+        # lanes overlap is under `concurrent`.
+        Ta, el_a, st_a, per_a = alone_leg(opt, variables, lib)
+        roof.update(family_record(Ta, st_a, el_a, per_a, bf3, POP, 1))
+        roof['measured'] = ('one pass of %d candidates on one stream (exec_batch_size = population), %d steps '
+                            'right after the timed region, hipEvent pairs on the launch stream around every '
+                            '%d-th conv launch, phase rotating with the step: NON-overlapped launch durations. '
+                            'The timed steps themselves run the reference chunks on %d lanes: see `concurrent`'
+                            % (POP, st_a, per_a, lanes_used))
+        conc = {k: timed[k] for k in ('exec_batch_size', 'lanes', 'achieved', 'frac', 'avg_launch_ms',
+                                      'sampled_launches', 'launches_per_step', 'time_share_of_step',
+                                      'algo_bytes_per_launch', 'traffic', 'traffic_source', 'traffic_read_write')}
+        conc['dominant_kernel'] = timed['dominant_kernel']
+        conc['conv1x1'] = timed['conv1x1']
+        conc['what'] = ('the launches of the timed configuration (reference chunks of %d on %d HIP streams), %s: a '
+                        'hipEvent pair spans the time a launch shares the GPU with the other lane, so these '
+                        'durations overlap -- time_share_of_step sums overlapping intervals and may exceed 1 -- '
+                        'and `achieved` is what a launch gets while overlapped, not what the kernel does'
+                        % (args.exec_batch, lanes_used,
+                           ('%d eager steps right behind the timed region (%.3f ms per step; the timed steps '
+                            'replay a HIP graph, which cannot hold event pairs)'
+                            % (ev_steps, 1e3 * ev_elapsed / ev_steps)) if graph_timed else 'inside the timed steps'))
+        roof['concurrent'] = conc
+    else:
+        roof.update(timed)
+        roof['measured'] = (('%d eager steps right behind the timed region' % ev_steps if graph_timed else
+                             'the timed steps') + ': hipEvent pairs on the launch stream around every %d-th conv '
+                            'launch, phase rotating with the step' % period) + (
+            '; %d lanes: durations overlap (see DESIGN section 6)' % lanes_used if lanes_used > 1 else '')
+    roof['launch_sampling'] = 'every %d-th conv launch of the event legs timed (hipEvent pairs)' % period
+    return {'roofline': roof,
+            'config': {'fwd_only_rescore_evals_per_s': round(rescore_rate, 1),
+                       'last_losses_min_max': [round(min(last_loss), 5), round(max(last_loss), 5)],
+                       'last_losses': [round(x, 6) for x in last_loss]}}
 
 
 if __name__ == '__main__':

@@ -8,12 +8,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-fp32-leg', '--no-extra']
+QUICK = ['--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-fp32-leg', '--no-extra']
 
 
 def _bench_line(stdout):
@@ -57,6 +58,30 @@ def test_bench_single_gpu_line():
 
 
 @pytest.mark.timeout(600)
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run: the headline line and nothing behind the timed steps; --dump-outputs writes what the last timed
+    step returned"""
+    if not torch.cuda.is_available():
+        pytest.skip('needs a GPU')
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(out)], cwd=ROOT, capture_output=True, text=True, timeout=550)
+    assert r.returncode == 0, r.stderr[-4000:]
+    rec = _bench_line(r.stdout)
+    assert rec['steps'] == 3 and rec['value'] > 0 and rec['unit'] == 'evals/s' and rec['higher_is_better'] is True
+    assert rec['dtype'].startswith('f32') and abs(rec['value'] - 18 * 1e3 / rec['ms_per_step']) < 1e-2 * rec['value']
+    assert rec['config']['hip_graph_replay'] is True
+    for moved in ('roofline', 'telemetry', 'cpu_baseline'):
+        assert moved not in rec
+    assert 'extra' not in rec['config'] and 'last_losses' not in rec['config']
+    shapes = {'out': (18, 3, 256, 256), 'loss': (18,), 'z': (18, 128), 'c': (18, 128)}
+    assert sorted(os.listdir(out)) == sorted(n + '.npy' for n in shapes)
+    for name, shape in shapes.items():
+        a = np.load(out / (name + '.npy'))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+
+
+@pytest.mark.timeout(600)
 def test_bench_eager_form_for_profilers():
     """`--pmc-run` (implies --eager: events inside the timed steps, no legs behind them) is what tools/gpu_round6.sh
     wraps in rocprofv3: warm-up + timed steps only, every dispatch at the named execution batch; the record is then
@@ -64,8 +89,9 @@ def test_bench_eager_form_for_profilers():
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     for eb, lanes in ((9, 2), (18, 1)):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--pmc-run', '--steps', '2', '--warmup', '1',
-                            '--exec-batch', str(eb)], cwd=ROOT, capture_output=True, text=True, timeout=550)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--pmc-run', '--steps', '2',
+                            '--warmup', '1', '--exec-batch', str(eb)], cwd=ROOT, capture_output=True, text=True,
+                           timeout=550)
         assert r.returncode == 0, r.stderr[-4000:]
         rec = _bench_line(r.stdout)
         assert rec['config']['hip_graph_replay'] is False and rec['config']['exec_batch_size'] == eb

@@ -20,7 +20,7 @@ def test_bench_two_ranks_over_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', '29611', os.path.join(ROOT, 'bench.py'),
-           '--gpus', '2', '--steps', '2', '--warmup', '1', '--backend', 'nccl']
+           '--gpus', '2', '--full', '--steps', '2', '--warmup', '1', '--backend', 'nccl']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -41,7 +41,7 @@ def test_sharded_step_matches_single_gpu_losses():
     for n in (1, 2):
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
                '--master-addr', '127.0.0.1', '--master-port', str(29620 + n),
-               os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1',
+               os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--full', '--steps', '2', '--warmup', '1',
                '--no-cpu-baseline', '--no-fp32-leg', '--no-extra']
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
         assert r.returncode == 0, r.stderr[-4000:]

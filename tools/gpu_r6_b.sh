@@ -6,7 +6,7 @@ cd $R
 timeout 1500 python -m pytest tests/test_sg2_fullsize_oracle_gpu.py -q -s -m gpu > $O/sg2_fullsize.txt 2>&1
 echo "sg2 fullsize rc=$?" >> $O/sg2_fullsize.txt
 timeout 600 python -m pytest tests/test_lanes_gpu.py tests/test_bench_gpu.py -x -q > $O/small_tests.txt 2>&1
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 grep -v "^$" $O/sg2_fullsize.txt | grep "cars-512\|ffhq-1024\|passed\|failed\|Error" ; tail -3 $O/small_tests.txt
 python - <<PY
 import json; r=json.load(open('$O/bench.json')); ro=r['roofline']

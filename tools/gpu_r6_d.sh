@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6d
 cd $R
 timeout 2400 python -m pytest tests/ -x -q -m gpu > $O/gpu_tests.txt 2>&1
 tail -5 $O/gpu_tests.txt
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python tools/prof_layers.py > $O/layers.txt 2>/dev/null
 python tools/step_vs_batch.py 2>/dev/null | grep "local candidates" > $O/step_vs_batch.txt
 python - <<PY

@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6f
 cd $R
 timeout 900 python -m pytest tests/test_bench_gpu.py -x -q > $O/bench_tests.txt 2>&1
 tail -3 $O/bench_tests.txt
-python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg > $O/bench_graph.json 2> $O/bench_graph.err
-python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg --eager > $O/bench_eager.json 2> $O/bench_eager.err
-python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg > $O/bench_graph2.json 2>> $O/bench_graph.err
+python bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg > $O/bench_graph.json 2> $O/bench_graph.err
+python bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg --eager > $O/bench_eager.json 2> $O/bench_eager.err
+python bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-fp32-leg > $O/bench_graph2.json 2>> $O/bench_graph.err
 python - <<PY
 import json
 for n in ('bench_graph', 'bench_eager', 'bench_graph2'):

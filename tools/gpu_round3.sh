@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r3
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python tools/prof_layers.py > $O/layers.txt 2>/dev/null
 python tools/roofline_1x1.py $O/layers.txt > $O/conv1x1_roofline.txt
 python tools/step_vs_batch.py 2>/dev/null | grep "local candidates" > $O/step_vs_batch.txt
@@ -17,13 +17,13 @@ tools/micro/conv_lab_abl 18 2>&1 | grep -v "pass 0" > $O/wino16s_ablation.txt
 tools/micro/issue_rate > $O/issue_rate.txt 2>&1
 tools/micro/mem_rate > $O/mem_rate.txt 2>&1
 cd /tmp
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/prof_bench.json 2> $O/prof.err
-timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/pmc_fetch.json 2> $O/pmc_fetch.err
-timeout 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/pmc_write.json 2> $O/pmc_write.err
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/prof_bench.json 2> $O/prof.err
+timeout 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/pmc_fetch.json 2> $O/pmc_fetch.err
+timeout 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra > $O/pmc_write.json 2> $O/pmc_write.err
 cd $R
 python tools/pmc_summary.py $(ls $O/pmc_fetch/*counter_collection.csv | head -1) $O/pmc_fetch_summary.csv > /dev/null
 python tools/pmc_summary.py $(ls $O/pmc_write/*counter_collection.csv | head -1) $O/pmc_write_summary.csv > /dev/null
-python tools/traffic_json.py $O/pmc_fetch_summary.csv $O/pmc_write_summary.csv $O/traffic.json "${1:-unknown}" "$(hostname)" "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra" > /dev/null
+python tools/traffic_json.py $O/pmc_fetch_summary.csv $O/pmc_write_summary.csv $O/traffic.json "${1:-unknown}" "$(hostname)" "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-extra" > /dev/null
 rm -f $O/pmc_fetch/*counter_collection.csv $O/pmc_write/*counter_collection.csv $O/prof/*kernel_trace.csv
 python -c "
 import json; r=json.load(open('$O/bench.json')); print(r['value'], r['ms_per_step'], r['roofline']['achieved'], r['roofline']['frac'], r['roofline']['frac_executed'], r['roofline']['conv1x1']['achieved'], r['telemetry'], r['cpu_baseline']['value'])

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r6
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python tools/prof_layers.py > $O/layers.txt 2>/dev/null
 python tools/roofline_1x1.py $O/layers.txt > $O/conv1x1_roofline.txt
 python tools/step_vs_batch.py 2>/dev/null | grep "local candidates" > $O/step_vs_batch.txt
