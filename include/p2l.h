@@ -815,6 +815,42 @@ int p2l_affine_grid_sample_bwd(const float* src, const float* theta, const float
                                float* dsrc, float* dtheta, int Bn, int C, int H, int W,
                                void* workspace, size_t ws_bytes, void* stream);
 
+/* Colour transformations of pix2latent/transform/color_transform.py (ColorTransform.apply, one
+ * torchvision PIL op per call there): a chain of ops on NCHW fp32 RGB images (C = 3, any B, H, W)
+ * in [-1, 1], bit-exact to the reference's byte path, every image with its own parameter.
+ *   op          param[b] (fp32, already clamped)  reference op (torchvision, Pillow)
+ *   BRIGHTNESS  factor                             adjust_brightness: ImageEnhance.Brightness
+ *   SATURATION  factor                             adjust_saturation: ImageEnhance.Color
+ *   CONTRAST    factor                             adjust_contrast: ImageEnhance.Contrast
+ *   GAMMA       gamma (its LUT carries it)         adjust_gamma: lut[b][256], built by the CALLER on
+ *                                                  the host in double (int((256 - 1e-3) * pow(k/255, g)));
+ *                                                  a caller holding g on the device pays one small D2H
+ *   HUE         hue factor in [-0.5, 0.5]          adjust_hue: HSV round trip, h += (uint8)(f * 255)
+ * dst may equal src.  Cost: one launch; each CONTRAST op adds one pre-pass (the mean of the L image at
+ * its point in the chain) and the chain one memset of its workspace
+ * (p2l_color_adjust_ws_bytes; 0 without contrast ops, then workspace may be NULL). */
+#define P2L_COLOR_BRIGHTNESS 0
+#define P2L_COLOR_SATURATION 1
+#define P2L_COLOR_CONTRAST 2
+#define P2L_COLOR_GAMMA 3
+#define P2L_COLOR_HUE 4
+#define P2L_COLOR_MAX_OPS 8
+typedef struct P2LColorOp {
+  int32_t op;                     /* P2L_COLOR_*                                          */
+  int32_t reserved;
+  const float* param;             /* [Bn] device                                          */
+  const uint8_t* lut;             /* GAMMA: [Bn][256] device; otherwise unused            */
+} P2LColorOp;
+typedef struct P2LColorChain {
+  size_t size;                    /* sizeof(P2LColorChain): later members are appended    */
+  int32_t n_ops;                  /* 1 .. P2L_COLOR_MAX_OPS, applied in order             */
+  int32_t reserved;
+  P2LColorOp ops[P2L_COLOR_MAX_OPS];
+} P2LColorChain;
+size_t p2l_color_adjust_ws_bytes(const P2LColorChain* chain, int Bn);
+int p2l_color_adjust(const P2LColorChain* chain, const float* src, float* dst, int Bn, int C, int H, int W,
+                     void* workspace, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* StyleGAN2 (rosinality) pieces; replace fused_bias_act / upfirdn2d and the   */
 /* torch ops inside Generator.forward (reference model/stylegan2.py:116-125).  */

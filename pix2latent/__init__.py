@@ -21,7 +21,8 @@ for _name in ('distribution', 'variable_manager', 'loss_functions', 'optimizer',
               'optimizer.ng_optimizer', 'optimizer.hybrid_ng_optimizer',
               'optimizer.base_ng_optimizer', 'model.biggan', 'model.stylegan2', 'transform',
               'transform.spatial_transform', 'transform.transform_optimizer',
-              'transform.transform_utils', 'transform.base_transform'):
+              'transform.transform_utils', 'transform.base_transform',
+              'transform.color_transform', 'transform.transform_functions'):
     try:
         sys.modules['pix2latent.' + _name] = importlib.import_module('pix2latent_amd.' + _name)
     except Exception:  # pragma: no cover  (e.g. native library missing: raised on use)

@@ -308,6 +308,7 @@ EXPORTS = [
     'p2l_sqzloss_bwd', 'p2l_sqzloss_ws_lookup',
     'p2l_sg2_blur_fwd_amax', 'p2l_sg2_styled_act_bwd_amax', 'p2l_sg2_blur_bwd_amax', 'p2l_sg2_noise_relayout',
     'p2l_sg2_rows_defer_begin', 'p2l_sg2_rows_defer_flush', 'p2l_sg2_rows_defer_cancel',
+    'p2l_color_adjust_ws_bytes', 'p2l_color_adjust',
 ]
 
 _lib = None
@@ -340,7 +341,7 @@ def lib():
                      'p2l_projloss_ws_bytes', 'p2l_loss_cache_floats', 'p2l_sg2_ws_bytes',
                      'p2l_alexloss_ws_bytes', 'p2l_alex_cache_floats', 'p2l_sqzloss_ws_bytes', 'p2l_sqz_cache_floats', 'p2l_gemm_ws_bytes',
                      'p2l_packed_weight_floats', 'p2l_packed_subpix_weight_floats', 'p2l_attn_fwd_ws_bytes', 'p2l_affine_grid_sample_bwd_ws_bytes',
-                     'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes'):
+                     'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
     return _lib
 

@@ -108,13 +108,27 @@ class ComposeTransform(object):
         return out
 
     def __call__(self, ims, t, invert=False, only_spatial=False):
+        """Consecutive colour transformations run as ONE chain (one native call on the device,
+        color_transform.apply_chain); the result equals applying them one after the other."""
+        from .color_transform import ColorTransform, apply_chain
         if t.size(0) == 1:
             t = t.repeat(ims.size(0), 1)
+        ops, params = [], []
         for fn, w, default, lo, hi in self.slices():
             if only_spatial and not getattr(fn, 'is_spatial', False):
                 continue
             centre = torch.from_numpy(default).type_as(t)
-            ims = fn(ims, self.reweight(t[:, lo:hi], w, centre), invert=invert)
+            t_fn = self.reweight(t[:, lo:hi], w, centre)
+            if isinstance(fn, ColorTransform):
+                assert ims.size(0) == t_fn.size(0)
+                ops.append(fn.fn)
+                params.append(fn.clamped(t_fn, invert))
+                continue
+            if ops:
+                ims, ops, params = apply_chain(ims, ops, params), [], []
+            ims = fn(ims, t_fn, invert=invert)
+        if ops:
+            ims = apply_chain(ims, ops, params)
         return ims
 
     def __str__(self):
@@ -122,8 +136,9 @@ class ComposeTransform(object):
             '\n\t'.join(str(fn) for fn, _ in self.transform_list))
 
 
-#: colour transformations of the reference (transform/color_transform.py) are CPU PIL /
-#: torchvision operations outside the hot path ("OUT")
+#: colour transformations by name: setup_transform_fn refuses them (the reference's own cannot build
+#: a chain: its TF module has neither SpatialTransform nor ComposeTransform); build the classes of
+#: color_transform.py and a ComposeTransform directly
 _COLOR_NAMES = ('hue', 'gamma', 'saturation', 'brightness', 'contrast')
 
 
