@@ -851,6 +851,16 @@ size_t p2l_color_adjust_ws_bytes(const P2LColorChain* chain, int Bn);
 int p2l_color_adjust(const P2LColorChain* chain, const float* src, float* dst, int Bn, int C, int H, int W,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* fp64 Gram of a tall fp32 panel (GANSpace components, pix2latent/edit/ganspace.py): gram = X^T X
+ * ([cols][cols] row-major, symmetric) and colsum = the column sums of X, both fp64 device buffers.
+ * rows >= 1, 1 <= cols <= 128; element (r, j) of X is X[r * ld + j] (trans = 0, ld >= cols) or
+ * X[j * ld + r] (trans = 1, ld >= rows).  Products are exact, the sums fp64 in a fixed order: the
+ * result depends on (rows, cols, trans) only, bit for bit.  Needs p2l_gram_f64_ws_bytes of workspace
+ * (0 for invalid sizes); two launches, no memset. */
+size_t p2l_gram_f64_ws_bytes(int64_t rows, int cols, int trans);
+int p2l_gram_f64(const float* X, int64_t rows, int cols, int64_t ld, int trans, double* gram, double* colsum,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* StyleGAN2 (rosinality) pieces; replace fused_bias_act / upfirdn2d and the   */
 /* torch ops inside Generator.forward (reference model/stylegan2.py:116-125).  */

@@ -10,6 +10,7 @@ import sys
 import pix2latent_amd as _impl
 from pix2latent_amd import *  # noqa: F401,F403
 from pix2latent_amd import distribution, VariableManager, save_variables  # noqa: F401
+from pix2latent_amd import edit  # noqa: F401  (the README's `pix2latent.edit.BigGANLatentEditor`)
 
 __version__ = _impl.__version__
 
@@ -22,7 +23,8 @@ for _name in ('distribution', 'variable_manager', 'loss_functions', 'optimizer',
               'optimizer.base_ng_optimizer', 'model.biggan', 'model.stylegan2', 'transform',
               'transform.spatial_transform', 'transform.transform_optimizer',
               'transform.transform_utils', 'transform.base_transform',
-              'transform.color_transform', 'transform.transform_functions'):
+              'transform.color_transform', 'transform.transform_functions',
+              'edit', 'edit.editor', 'edit.ganspace'):
     try:
         sys.modules['pix2latent.' + _name] = importlib.import_module('pix2latent_amd.' + _name)
     except Exception:  # pragma: no cover  (e.g. native library missing: raised on use)

@@ -309,6 +309,7 @@ EXPORTS = [
     'p2l_sg2_blur_fwd_amax', 'p2l_sg2_styled_act_bwd_amax', 'p2l_sg2_blur_bwd_amax', 'p2l_sg2_noise_relayout',
     'p2l_sg2_rows_defer_begin', 'p2l_sg2_rows_defer_flush', 'p2l_sg2_rows_defer_cancel',
     'p2l_color_adjust_ws_bytes', 'p2l_color_adjust',
+    'p2l_gram_f64_ws_bytes', 'p2l_gram_f64',
 ]
 
 _lib = None
@@ -341,8 +342,13 @@ def lib():
                      'p2l_projloss_ws_bytes', 'p2l_loss_cache_floats', 'p2l_sg2_ws_bytes',
                      'p2l_alexloss_ws_bytes', 'p2l_alex_cache_floats', 'p2l_sqzloss_ws_bytes', 'p2l_sqz_cache_floats', 'p2l_gemm_ws_bytes',
                      'p2l_packed_weight_floats', 'p2l_packed_subpix_weight_floats', 'p2l_attn_fwd_ws_bytes', 'p2l_affine_grid_sample_bwd_ws_bytes',
-                     'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes'):
+                     'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes',
+                     'p2l_gram_f64_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
+        # (64-bit sizes: without argtypes ctypes would pass them as C int)
+        _lib.p2l_gram_f64_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+        _lib.p2l_gram_f64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     return _lib
 
 

@@ -181,7 +181,8 @@ class BigGAN(nn.Module):
         d.ch = self.ch
         d.z_dim = self.z_dim
         d.c_dim = self.z_dim
-        d.genz_w = self._dev_t(W['generator.gen_z.weight'].t()).data_ptr()
+        self._genz_wt = self._dev_t(W['generator.gen_z.weight'].t())     # [z_dim + c_dim][16 * 16 * ch]
+        d.genz_w = self._genz_wt.data_ptr()
         d.genz_b = self._dev_t(W['generator.gen_z.bias']).data_ptr()
         scale_cols, offset_cols = [], []
         self._bn_prefixes = []
