@@ -37,6 +37,18 @@ extern "C" {
 #define P2L_ELAUNCH (-2)  /* hipLaunchKernel reported an error               */
 #define P2L_EWS (-3)      /* workspace too small                             */
 #define P2L_EUNSUP (-4)   /* combination not implemented                     */
+/* Host-side argument checks.  The entry points listed here refuse, with
+ * P2L_EINVAL and BEFORE anything is launched, a NULL where a pointer is required, Bn < 1, any other size < 1
+ * (p2l_reduce_rows: n < 0), a row pitch below the row length, and Bn > 65535 where the batch is a y/z grid
+ * dimension (p2l_scale_bwd, p2l_sg2_styled_act_bwd(_amax), p2l_weight_map, p2l_l1_loss_fwd/_bwd):
+ *   p2l_linear_fwd(_ld), p2l_linear_bwd(_ld), p2l_cbn_fold_fwd/_bwd, p2l_scale_bwd, p2l_relu_mask,
+ *   p2l_nchw3_to_nhwc16, p2l_nhwc16_to_nchw3, p2l_tanh_bwd16, p2l_weight_sum, p2l_weight_map, p2l_l1_loss_fwd/_bwd,
+ *   p2l_reduce_rows, p2l_adam_step, p2l_adam_step_dev, p2l_clamp, p2l_vec_scale_div, p2l_concat2, p2l_split2,
+ *   p2l_sg2_pixelnorm_fwd/_bwd, p2l_sg2_bias_lrelu_fwd, p2l_sg2_lrelu_bwd, p2l_sg2_demod_fwd/_bwd,
+ *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
+ *   p2l_add_inplace, p2l_sg2_noise_relayout.
+ * Every OTHER entry point checks only what its own comment states (a shape or alignment constraint, an unsupported
+ * size): it does not test its pointers or its batch size, and a caller must not rely on it to. */
 
 int p2l_version(void);
 const char* p2l_strerror(int rc);
@@ -520,6 +532,10 @@ int p2l_relu_mask(const float* y, int y_ld, const float* g, int g_ld, float* dy,
 
 /* ------------------------------------------------------------------------- */
 /* Image <-> NHWC16 helpers (3 channels padded to 16 floats per pixel).      */
+/* p2l_nchw3_to_nhwc16 WRITES channels 3..15 of every pixel as +0.0 (all 16    */
+/* floats of dst are defined afterwards); p2l_nhwc16_to_nchw3 reads channels   */
+/* 0..2 only.  p2l_tanh_bwd16 sets channel 3 of dimg to 0 and leaves channels  */
+/* 4..15 as they are.                                                          */
 /* ------------------------------------------------------------------------- */
 int p2l_nchw3_to_nhwc16(const float* src, float* dst, int Bn, int H, int W,
                         void* stream);
@@ -585,6 +601,7 @@ int p2l_bilinear_adjoint(const float* wsrc, float* wt, int Bn, int H, int W,
                          int h, int w, void* stream);
 /* deterministic finishing reduction:                                         */
 /*   out[b] (+)= scale * sum_i partial[b][i] / (div ? div[b] : 1)             */
+/* partial is [Bn][n], n >= 0 (n == 0: the empty sum).                          */
 int p2l_reduce_rows(const float* partial, float* out, int Bn, int n, float scale,
                     const float* div, int accumulate, void* stream);
 
@@ -880,7 +897,9 @@ int p2l_sg2_blur_fwd(const float* u, const float* d, const float* noise, float n
                      const float* bias, float* y, int Bn, int H, int W, int C, void* stream);
 /* activation backward of a styled conv: gd = dy*lrelu'(y)*d ; dd[b,c] = sum_p dy*lrelu'(y)*c
  * with c = (pre - nw*noise - bias)/d recomputed from y ; dnoise[b,p] = nw*sum_c dy*lrelu'(y)
- * (optional).  partial: B*nblk*C floats, strips: (C/64)*B*P floats (if dnoise). */
+ * (optional).  partial: B*nblk*C floats (nblk = p2l_sg2_act_bwd_nblk(P)); strips (if dnoise):
+ * (C / (C % 64 ? 32 : 64)) * B * P floats -- the kernel works on strips of 64 channels, of 32 where C is not a
+ * multiple of 64.  C % 32 == 0, 1 <= Bn <= 65535; y == 0 takes the negative slope, as the forward does. */
 int p2l_sg2_act_bwd_nblk(int P);
 int p2l_sg2_styled_act_bwd(const float* dy, const float* y, const float* d, const float* noise,
                            float nw, const float* bias, float* gd, float* dd, float* dnoise,
@@ -907,10 +926,15 @@ int p2l_sg2_blur_bwd_amax(const float* g, float* du, int Bn, int H, int W, int C
 void p2l_sg2_rows_defer_begin(void);
 int p2l_sg2_rows_defer_flush(void* stream);
 void p2l_sg2_rows_defer_cancel(void);
-/* RGB skip upsample (upfirdn2d up=2, [1,3,3,1]) on NHWC16 images and its transpose */
+/* RGB skip upsample (upfirdn2d up=2, [1,3,3,1]) on NHWC16 images and its transpose.  Channels 0..3 are filtered,
+ * channels 4..15 of out (and of dskip when accumulate == 0) are written as 0; accumulate == 1 adds to channels
+ * 0..3 of dskip and leaves the rest. */
 int p2l_sg2_rgb_up_fwd(const float* skip, float* out, int Bn, int h, int w, void* stream);
 int p2l_sg2_rgb_up_bwd(const float* dout, float* dskip, int Bn, int h, int w, int accumulate,
                        void* stream);
+/* y = clamp(x, -1, 1) on channels 0..2 of P NHWC16 pixels, channels 3..15 of y / dx written as 0.  Backward as
+ * torch.clamp's autograd: dx = dy where -1 <= x <= 1 -- a value exactly at -1 or +1 PASSES its gradient --
+ * and 0 elsewhere. */
 int p2l_sg2_clamp16_fwd(const float* x, float* y, int64_t P, void* stream);
 int p2l_sg2_clamp16_bwd(const float* x, const float* dy, float* dx, int64_t P, void* stream);
 int p2l_broadcast_rows(const float* src, float* dst, int64_t n, int Bn, void* stream);

@@ -338,6 +338,8 @@ def lib():
         _lib.p2l_strerror.restype = C.c_char_p
         _lib.p2l_arb_defer_begin.restype = None
         _lib.p2l_arb_defer_cancel.restype = None
+        _lib.p2l_sg2_rows_defer_begin.restype = None
+        _lib.p2l_sg2_rows_defer_cancel.restype = None
         for name in ('p2l_conv_workspace_bytes', 'p2l_biggan_ws_bytes',
                      'p2l_projloss_ws_bytes', 'p2l_loss_cache_floats', 'p2l_sg2_ws_bytes',
                      'p2l_alexloss_ws_bytes', 'p2l_alex_cache_floats', 'p2l_sqzloss_ws_bytes', 'p2l_sqz_cache_floats', 'p2l_gemm_ws_bytes',
@@ -346,6 +348,22 @@ def lib():
                      'p2l_gram_f64_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
         # (64-bit sizes: without argtypes ctypes would pass them as C int)
+        # the small entry points that take an int64_t count or a float: a bare Python number would travel as C int
+        vp, i32, i64_, f32_ = C.c_void_p, C.c_int, C.c_int64, C.c_float
+        _lib.p2l_relu_mask.argtypes = [vp, i32, vp, i32, vp, i32, i64_, i32, vp]
+        _lib.p2l_tanh_bwd16.argtypes = [vp, vp, i64_, vp]
+        _lib.p2l_clamp.argtypes = [vp, i64_, f32_, f32_, vp]
+        _lib.p2l_adam_step.argtypes = [vp, vp, vp, vp, i64_, f32_, f32_, f32_, f32_, i32, vp]
+        _lib.p2l_adam_step_dev.argtypes = [vp, vp, vp, vp, i64_, f32_, f32_, f32_, f32_, vp, i32, vp]
+        _lib.p2l_reduce_rows.argtypes = [vp, vp, i32, i32, f32_, vp, i32, vp]
+        _lib.p2l_vec_scale_div.argtypes = [vp, vp, vp, i32, f32_, vp]
+        _lib.p2l_sg2_bias_lrelu_fwd.argtypes = [vp, vp, f32_, i32, i32, vp]
+        _lib.p2l_sg2_clamp16_fwd.argtypes = [vp, vp, i64_, vp]
+        _lib.p2l_sg2_clamp16_bwd.argtypes = [vp, vp, vp, i64_, vp]
+        _lib.p2l_broadcast_rows.argtypes = [vp, vp, i64_, i32, vp]
+        _lib.p2l_add_inplace.argtypes = [vp, vp, i64_, vp]
+        _lib.p2l_sg2_styled_act_bwd.argtypes = [vp, vp, vp, vp, f32_, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+        _lib.p2l_sg2_styled_act_bwd_amax.argtypes = [vp, vp, vp, vp, f32_, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
         _lib.p2l_gram_f64_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
         _lib.p2l_gram_f64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

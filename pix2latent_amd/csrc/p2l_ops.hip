@@ -991,7 +991,7 @@ extern "C" int p2l_linear_fwd(const float* x, const float* W, const float* bias,
 }
 extern "C" int p2l_linear_fwd_ld(const float* x, int x_ld, const float* W, const float* bias,
                                  float* y, int Bn, int K, int N, void* stream) {
-  if (!x || !W || !y || K % 4 || K > 1024 || Bn < 1) return P2L_EINVAL;
+  if (!x || !W || !y || K < 4 || K % 4 || K > 1024 || Bn < 1 || N < 1 || x_ld < K) return P2L_EINVAL;
   // every launch streams W once: rows in groups of 16, or of 24 when that saves a launch (the
   // population of 18: one pass over the 33 MB gen_z matrix instead of two); a row's sum does not
   // depend on its group
@@ -1019,7 +1019,7 @@ extern "C" int p2l_linear_bwd(const float* dy, const float* W, float* dx, int Bn
 }
 extern "C" int p2l_linear_bwd_ld(const float* dy, const float* W, float* dx, int dx_ld, int Bn,
                                  int K, int N, int accumulate, void* stream) {
-  if (!dy || !W || !dx || Bn < 1 || (N % 4)) return P2L_EINVAL;
+  if (!dy || !W || !dx || Bn < 1 || K < 1 || N < 4 || (N % 4) || dx_ld < K) return P2L_EINVAL;
   constexpr int BG = 16, BGW = 24;      // (as p2l_linear_fwd_ld: 24 rows per pass over W when that saves one)
   if (cdiv(Bn, BGW) < cdiv(Bn, BG)) {
     for (int b0 = 0; b0 < Bn; b0 += BGW)
@@ -1036,6 +1036,8 @@ extern "C" int p2l_linear_bwd_ld(const float* dy, const float* W, float* dx, int
 extern "C" int p2l_cbn_fold_fwd(const float* g_raw, const float* b_raw,
                                 const float* mean, const float* rstd, float* s,
                                 float* t, int Bn, int C, int raw_ld, void* stream) {
+  if (!g_raw || !b_raw || !mean || !rstd || !s || !t) return P2L_EINVAL;
+  if (Bn < 1 || C < 1 || raw_ld < C || (int64_t)Bn * C > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(cbn_fold_fwd_kernel, dim3(cdiv(Bn * C, 256)), dim3(256), 0,
                      ST(stream), g_raw, b_raw, mean, rstd, s, t, Bn, C, raw_ld);
   return p2l_check_launch();
@@ -1043,6 +1045,8 @@ extern "C" int p2l_cbn_fold_fwd(const float* g_raw, const float* b_raw,
 extern "C" int p2l_cbn_fold_bwd(const float* ds, const float* dt, const float* mean,
                                 const float* rstd, float* dg_raw, float* db_raw,
                                 int Bn, int C, int raw_ld, void* stream) {
+  if (!ds || !dt || !mean || !rstd || !dg_raw || !db_raw) return P2L_EINVAL;
+  if (Bn < 1 || C < 1 || raw_ld < C || (int64_t)Bn * C > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(cbn_fold_bwd_kernel, dim3(cdiv(Bn * C, 256)), dim3(256), 0,
                      ST(stream), ds, dt, mean, rstd, dg_raw, db_raw, Bn, C, raw_ld);
   return p2l_check_launch();
@@ -1121,6 +1125,8 @@ extern "C" int p2l_scale_bwd(const float* da, int da_ld, const float* x, int x_l
                              float* partial, int Bn, int H, int W, int C, void* stream) {
   if (!da || !x || !s || !dx || !ds || !dt_scratch || !partial) return P2L_EINVAL;
   if (C % 32 || da_ld % 4 || x_ld % 4 || dx_ld % 4 || st_bstride % 4) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || H < 1 || W < 1 || C < 32) return P2L_EINVAL;      // (Bn is the grid's z)
+  if (skip && (skip_ld % 4 || skip_C % 4 || skip_C < 0 || skip_C > C)) return P2L_EINVAL;
   ArbK k{};
   k.da = da; k.x = x; k.s = s; k.t = s; k.skip = skip; k.dx = dx; k.partial = partial;
   k.da_ld = da_ld; k.x_ld = x_ld; k.dx_ld = dx_ld; k.skip_ld = skip_ld;
@@ -1179,7 +1185,8 @@ extern "C" int p2l_maxpool2_bwd(const float* y, int y_ld, const float* dyp,
 }
 extern "C" int p2l_relu_mask(const float* y, int y_ld, const float* g, int g_ld,
                              float* dy, int dy_ld, int64_t P, int C, void* stream) {
-  if (C % 4) return P2L_EINVAL;
+  if (!y || !g || !dy || P < 1 || C < 4 || y_ld < C || g_ld < C || dy_ld < C) return P2L_EINVAL;
+  if (C % 4 || y_ld % 4 || g_ld % 4 || dy_ld % 4) return P2L_EINVAL;      // (float4 accesses)
   hipLaunchKernelGGL(relu_mask_kernel, dim3(cdiv((size_t)P * (C / 4), 256)), dim3(256),
                      0, ST(stream), y, y_ld, g, g_ld, dy, dy_ld, (long long)P, C);
   return p2l_check_launch();
@@ -1187,17 +1194,20 @@ extern "C" int p2l_relu_mask(const float* y, int y_ld, const float* g, int g_ld,
 
 extern "C" int p2l_nchw3_to_nhwc16(const float* src, float* dst, int Bn, int H, int W,
                                    void* stream) {
+  if (!src || !dst || Bn < 1 || H < 1 || W < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(nchw3_to_nhwc16_kernel, dim3(cdiv((size_t)Bn * H * W, 256)),
                      dim3(256), 0, ST(stream), src, dst, Bn, H * W);
   return p2l_check_launch();
 }
 extern "C" int p2l_nhwc16_to_nchw3(const float* src, float* dst, int Bn, int H, int W,
                                    void* stream) {
+  if (!src || !dst || Bn < 1 || H < 1 || W < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(nhwc16_to_nchw3_kernel, dim3(cdiv((size_t)Bn * H * W, 256)),
                      dim3(256), 0, ST(stream), src, dst, Bn, H * W);
   return p2l_check_launch();
 }
 extern "C" int p2l_tanh_bwd16(const float* img, float* dimg, int64_t P, void* stream) {
+  if (!img || !dimg || P < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(tanh_bwd16_kernel, dim3(cdiv(P, 256)), dim3(256), 0, ST(stream),
                      img, dimg, (long long)P);
   return p2l_check_launch();
@@ -1205,12 +1215,14 @@ extern "C" int p2l_tanh_bwd16(const float* img, float* dimg, int64_t P, void* st
 
 extern "C" int p2l_weight_sum(const float* weight, const float* loss_mask, float* wsum,
                               int Bn, int HW3, void* stream) {
+  if (!weight || !wsum || Bn < 1 || HW3 < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(weight_sum_kernel, dim3(Bn), dim3(1024), 0, ST(stream), weight,
                      loss_mask, wsum, HW3);
   return p2l_check_launch();
 }
 extern "C" int p2l_weight_map(const float* weight, const float* loss_mask, float* wsrc,
                               int Bn, int H, int W, void* stream) {
+  if (!weight || !wsrc || Bn < 1 || Bn > 65535 || H < 1 || W < 1) return P2L_EINVAL;      // (Bn is the grid's y)
   hipLaunchKernelGGL(weight_map_kernel, dim3(cdiv(H * W, 256), Bn), dim3(256), 0,
                      ST(stream), weight, loss_mask, wsrc, H * W);
   return p2l_check_launch();
@@ -1220,6 +1232,8 @@ extern "C" int p2l_l1_loss_fwd(const float* img16, const float* target,
                                const float* weight, const float* loss_mask,
                                const float* wsum, float* loss, float* partial, int Bn,
                                int H, int W, void* stream) {
+  if (!img16 || !target || !weight || !wsum || !loss || !partial) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || H < 1 || W < 1) return P2L_EINVAL;      // (Bn is the grid's y)
   const int nblk = cdiv(H * W, 256);
   hipLaunchKernelGGL(l1_fwd_kernel, dim3(nblk, Bn), dim3(256), 0, ST(stream), img16,
                      target, weight, loss_mask, partial, H * W);
@@ -1231,6 +1245,8 @@ extern "C" int p2l_l1_loss_bwd(const float* img16, const float* target,
                                const float* weight, const float* loss_mask,
                                const float* wsum, const float* gscale, float* dimg16,
                                int Bn, int H, int W, int accumulate, void* stream) {
+  if (!img16 || !target || !weight || !wsum || !gscale || !dimg16) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || H < 1 || W < 1) return P2L_EINVAL;      // (Bn is the grid's y)
   hipLaunchKernelGGL(l1_bwd_kernel, dim3(cdiv(H * W, 256), Bn), dim3(256), 0,
                      ST(stream), img16, target, weight, loss_mask, wsum, gscale,
                      dimg16, H * W, accumulate);
@@ -1329,6 +1345,7 @@ extern "C" int p2l_bilinear_adjoint(const float* wsrc, float* wt, int Bn, int H,
 extern "C" int p2l_reduce_rows(const float* partial, float* out, int Bn, int n,
                                float scale, const float* div, int accumulate,
                                void* stream) {
+  if (!partial || !out || Bn < 1 || n < 0) return P2L_EINVAL;      // (n == 0: the empty sum)
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(Bn), dim3(256), 0, ST(stream), partial,
                      out, n, scale, div, accumulate);
   return p2l_check_launch();
@@ -1367,7 +1384,7 @@ extern "C" int p2l_affine_grid_sample_bwd(const float* src, const float* theta, 
 extern "C" int p2l_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
                              float lr, float beta1, float beta2, float eps,
                              int step_count, void* stream) {
-  if (!p || !g || !m || !v || step_count < 1) return P2L_EINVAL;
+  if (!p || !g || !m || !v || step_count < 1 || n < 1) return P2L_EINVAL;
   // same host-side double arithmetic as torch.optim.adam._single_tensor_adam
   const double bc1 = 1.0 - pow((double)beta1, (double)step_count);
   const double bc2 = 1.0 - pow((double)beta2, (double)step_count);
@@ -1380,7 +1397,7 @@ extern "C" int p2l_adam_step(float* p, const float* g, float* m, float* v, int64
 extern "C" int p2l_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
                                  float lr, float beta1, float beta2, float eps,
                                  int32_t* step_counters, int n_counters, void* stream) {
-  if (!p || !g || !m || !v || !step_counters || n_counters < 1) return P2L_EINVAL;
+  if (!p || !g || !m || !v || !step_counters || n_counters < 1 || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), p, g, m,
                      v, (long long)n, lr, beta1, beta2, eps, (const int*)step_counters);
   hipLaunchKernelGGL(counters_advance_kernel, dim3(cdiv(n_counters, 256)), dim3(256), 0,
@@ -1388,6 +1405,7 @@ extern "C" int p2l_adam_step_dev(float* p, const float* g, float* m, float* v, i
   return p2l_check_launch();
 }
 extern "C" int p2l_clamp(float* p, int64_t n, float lo, float hi, void* stream) {
+  if (!p || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(clamp_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), p,
                      (long long)n, lo, hi);
   return p2l_check_launch();

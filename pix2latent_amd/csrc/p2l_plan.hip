@@ -491,18 +491,21 @@ int bg_layout(const P2LBigGAN* m, int B, BGLayout& L) {
 
 extern "C" int p2l_vec_scale_div(const float* a, const float* div, float* out, int n,
                                  float scale, void* stream) {
+  if (!a || !out || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(vec_scale_div_kernel, dim3(cdiv(n, 256)), dim3(256), 0,
                      (hipStream_t)stream, a, div, out, n, scale);
   return p2l_check_launch();
 }
 extern "C" int p2l_concat2(const float* z, const float* c, float* cond, int Bn, int nz,
                            int nc, void* stream) {
+  if (!z || !c || !cond || Bn < 1 || nz < 1 || nc < 1 || (int64_t)Bn * (nz + nc) > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(concat2_kernel, dim3(cdiv(Bn * (nz + nc), 256)), dim3(256), 0,
                      (hipStream_t)stream, z, c, cond, Bn, nz, nc);
   return p2l_check_launch();
 }
 extern "C" int p2l_split2(const float* dcond, float* dz, float* dc, int Bn, int nz,
                           int nc, void* stream) {
+  if (!dcond || !dz || !dc || Bn < 1 || nz < 1 || nc < 1 || (int64_t)Bn * (nz + nc) > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(split2_kernel, dim3(cdiv(Bn * (nz + nc), 256)), dim3(256), 0,
                      (hipStream_t)stream, dcond, dz, dc, Bn, nz, nc);
   return p2l_check_launch();

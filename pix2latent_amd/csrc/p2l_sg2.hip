@@ -501,26 +501,31 @@ __global__ void add_inplace_kernel(float* a, const float* b, size_t n) {
 }  // namespace
 
 extern "C" int p2l_sg2_pixelnorm_fwd(const float* z, float* y, int Bn, int D, void* stream) {
+  if (!z || !y || Bn < 1 || D < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(pixelnorm_fwd_kernel, dim3(cdiv(Bn, 4)), dim3(256), 0, ST(stream), z, y, Bn, D);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_pixelnorm_bwd(const float* z, const float* dy, float* dz, int Bn, int D,
                                      void* stream) {
+  if (!z || !dy || !dz || Bn < 1 || D < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(pixelnorm_bwd_kernel, dim3(cdiv(Bn, 4)), dim3(256), 0, ST(stream), z, dy, dz, Bn, D);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_bias_lrelu_fwd(float* x, const float* bias, float bias_mul, int Bn, int D,
                                       void* stream) {
+  if (!x || !bias || Bn < 1 || D < 1 || (int64_t)Bn * D > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(bias_lrelu_fwd_kernel, dim3(cdiv(Bn * D, 256)), dim3(256), 0, ST(stream), x, bias,
                      bias_mul, Bn * D, D);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_lrelu_bwd(const float* y, float* g, int n, void* stream) {
+  if (!y || !g || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), y, g, n);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_demod_fwd(const float* s, const float* Wsq, float* d, int Bn, int Cin,
                                  int Cout, void* stream) {
+  if (!s || !Wsq || !d || Bn < 1 || Cin < 1 || Cout < 1 || (int64_t)Bn * Cout > INT32_MAX) return P2L_EINVAL;
   hipLaunchKernelGGL(demod_fwd_kernel, dim3(cdiv(Bn * Cout, 256)), dim3(256), 0, ST(stream), s, Wsq, d,
                      Bn, Cin, Cout);
   return p2l_check_launch();
@@ -528,6 +533,8 @@ extern "C" int p2l_sg2_demod_fwd(const float* s, const float* Wsq, float* d, int
 extern "C" int p2l_sg2_demod_bwd(const float* s, const float* Wsq, const float* d, const float* dd,
                                  float* ds, int Bn, int Cin, int Cout, int accumulate,
                                  void* stream) {
+  if (!s || !Wsq || !d || !dd || !ds || Bn < 1 || Cin < 1 || Cout < 1 || (int64_t)Bn * Cin > INT32_MAX)
+    return P2L_EINVAL;
   hipLaunchKernelGGL(demod_bwd_kernel, dim3(cdiv(Bn * Cin, 256)), dim3(256), 0, ST(stream), s, Wsq, d,
                      dd, ds, Bn, Cin, Cout, accumulate);
   return p2l_check_launch();
@@ -560,6 +567,8 @@ extern "C" int p2l_sg2_styled_act_bwd_amax(const float* dy, const float* y, cons
                                            const float* noise, float nw, const float* bias, float* gd,
                                            float* dd, float* dnoise, float* partial, float* strips,
                                            int Bn, int P, int C, float* amax_out, void* stream) {
+  if (!dy || !y || !d || !bias || !gd || !dd || !partial || (dnoise && !strips)) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || P < 1 || C < 32) return P2L_EINVAL;      // (Bn is the grid's z)
   if (C % 32) return P2L_EINVAL;
   const int sw = (C % 64) ? 32 : 64;
   ActBwdK k{};
@@ -606,22 +615,26 @@ extern "C" int p2l_sg2_blur_bwd(const float* g, float* du, int Bn, int H, int W,
   return p2l_sg2_blur_bwd_amax(g, du, Bn, H, W, C, nullptr, stream);
 }
 extern "C" int p2l_sg2_rgb_up_fwd(const float* skip, float* out, int Bn, int h, int w, void* stream) {
+  if (!skip || !out || Bn < 1 || h < 1 || w < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(rgb_up_fwd_kernel, dim3(cdiv((size_t)Bn * 4 * h * w, 256)), dim3(256), 0,
                      ST(stream), skip, out, Bn, h, w);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_rgb_up_bwd(const float* dout, float* dskip, int Bn, int h, int w,
                                   int accumulate, void* stream) {
+  if (!dout || !dskip || Bn < 1 || h < 1 || w < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(rgb_up_bwd_kernel, dim3(cdiv((size_t)Bn * h * w, 256)), dim3(256), 0, ST(stream),
                      dout, dskip, Bn, h, w, accumulate);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_clamp16_fwd(const float* x, float* y, int64_t P, void* stream) {
+  if (!x || !y || P < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(clamp16_fwd_kernel, dim3(cdiv(P, 256)), dim3(256), 0, ST(stream), x, y, (size_t)P);
   return p2l_check_launch();
 }
 extern "C" int p2l_sg2_clamp16_bwd(const float* x, const float* dy, float* dx, int64_t P,
                                    void* stream) {
+  if (!x || !dy || !dx || P < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(clamp16_bwd_kernel, dim3(cdiv(P, 256)), dim3(256), 0, ST(stream), x, dy, dx,
                      (size_t)P);
   return p2l_check_launch();
@@ -643,11 +656,13 @@ extern "C" int p2l_sg2_noise_relayout(const P2LStyleGAN2* m, const float* src, f
   return p2l_check_launch();
 }
 extern "C" int p2l_broadcast_rows(const float* src, float* dst, int64_t n, int Bn, void* stream) {
+  if (!src || !dst || n < 1 || Bn < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(broadcast_rows_kernel, dim3(cdiv(n * Bn, 256)), dim3(256), 0, ST(stream), src, dst,
                      (size_t)n, Bn);
   return p2l_check_launch();
 }
 extern "C" int p2l_add_inplace(float* a, const float* b, int64_t n, void* stream) {
+  if (!a || !b || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(add_inplace_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), a, b, (size_t)n);
   return p2l_check_launch();
 }

@@ -1,0 +1,228 @@
+"""Plain float64 references of the small entry points of include/p2l.h (the HBM-bound glue of both generators, the
+losses and the optimiser), written from the formulas in the header comments and the reference arithmetic they cite
+-- not from the kernels.  Forwards are direct restatements; every backward is autograd through its forward in
+float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks these functions against
+independent formulations, tests/test_small_kernels_gpu.py holds the kernels to them.
+
+Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
+Every function takes tensors of any float dtype and computes in the dtype of its first argument, so that the same
+text is the fp64 reference and -- called with float32 tensors -- the "straightforward fp32 restatement" the GPU
+tests use as a yardstick for the error bars."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+SQRT2 = math.sqrt(2.0)
+SLOPE = 0.2
+U = 2.0 ** -24          # unit round-off of fp32
+
+
+def vjp(fn, inputs, grad_out, wrt=None):
+    """gradients of sum(fn(*inputs) * grad_out) w.r.t. inputs[i], i in wrt (default: all), by autograd."""
+    wrt = list(range(len(inputs))) if wrt is None else list(wrt)
+    xs = [t.detach().clone().requires_grad_(i in wrt) for i, t in enumerate(inputs)]
+    out = fn(*xs)
+    outs = out if isinstance(out, (tuple, list)) else (out,)
+    gos = grad_out if isinstance(grad_out, (tuple, list)) else (grad_out,)
+    total = sum((o * g.to(o.dtype)).sum() for o, g in zip(outs, gos))
+    grads = torch.autograd.grad(total, [xs[i] for i in wrt], allow_unused=True)
+    grads = [torch.zeros_like(xs[i]) if g is None else g for i, g in zip(wrt, grads)]
+    return grads if len(grads) > 1 else grads[0]
+
+
+def lrelu(v):
+    """leaky_relu(0.2): the branch torch.where(v > 0, ...) takes (0 and -0 go down the negative slope)."""
+    return torch.where(v > 0, v, SLOPE * v)
+
+
+# ---- StyleGAN2 mapping network ---------------------------------------------------------------------------------
+def pixelnorm(z):                                   # PixelNorm: x * rsqrt(mean(x^2, dim=1) + 1e-8)
+    return z * torch.rsqrt((z * z).mean(dim=1, keepdim=True) + 1e-8)
+
+
+def bias_lrelu(x, bias, bias_mul):                  # fused_leaky_relu(x, bias * lr_mul)
+    return lrelu(x + bias.to(x.dtype) * bias_mul) * SQRT2
+
+
+def lrelu_bwd(y, g):
+    """g * d(lrelu(v) * sqrt2)/dv at a pre-activation of the sign of the saved output y."""
+    return vjp(lambda v: lrelu(v) * SQRT2, [y], g)
+
+
+# ---- StyleGAN2 modulation ----------------------------------------------------------------------------------------
+def demod(s, Wsq):                                  # d[b,o] = rsqrt(sum_i s[b,i]^2 Wsq[i][o] + 1e-8)
+    return torch.rsqrt((s * s) @ Wsq.to(s.dtype) + 1e-8)
+
+
+def demod_bwd(s, Wsq, dd):
+    return vjp(lambda s_: demod(s_, Wsq), [s], dd)
+
+
+def scale_fwd(x, s):                                # a[b,p,c] = x[b,p,c] * s[b,c]
+    return x * s.to(x.dtype)[:, None, :]
+
+
+def scale_bwd(da, x, s, skip=None, skip_C=0):
+    """dx = da * s (+ skip on channels < skip_C), ds[b,c] = sum_p da * x; x, da: [B, P, C]"""
+    dx, ds = vjp(scale_fwd, [x, s.to(x.dtype)], da)
+    if skip is not None:
+        dx = dx.clone()
+        dx[:, :, :skip_C] += skip.to(dx.dtype)[:, :, :skip_C]
+    return dx, ds
+
+
+# ---- StyleGAN2 styled-conv activation -----------------------------------------------------------------------------
+def styled_act(c, d, noise, nw, bias):
+    """y = lrelu(c * d[b,ch] + nw * noise[b,p] + bias[ch]) * sqrt2 ; c: [B, P, C], noise: [B, P] or None"""
+    pre = c * d[:, None, :] + bias[None, None, :]
+    if noise is not None:
+        pre = pre + nw * noise[:, :, None]
+    return lrelu(pre) * SQRT2
+
+
+def styled_act_bwd(dy, c, d, noise, nw, bias):
+    """-> gd (gradient of the un-scaled conv result c), dd [B, C], dnoise [B, P] (or None) from the TRUE c"""
+    if noise is None:
+        gd, dd = vjp(lambda c_, d_: styled_act(c_, d_, None, nw, bias), [c, d], dy)
+        return gd, dd, None
+    gd, dd, dn = vjp(lambda c_, d_, n_: styled_act(c_, d_, n_, nw, bias), [c, d, noise], dy)
+    return gd, dd, dn
+
+
+# ---- StyleGAN2 image tail -----------------------------------------------------------------------------------------
+def upfirdn2d_up2(x):
+    """upfirdn2d(x, [1,3,3,1] x [1,3,3,1] / 16 * 4, up=2, pad=(2,1)) on [B, C, h, w]: zero-insert, zero-pad, FIR
+    with the flipped kernel."""
+    b, c, h, w = x.shape
+    k1 = torch.tensor([1.0, 3.0, 3.0, 1.0], dtype=x.dtype)
+    k = torch.outer(k1, k1)
+    k = k / k.sum() * 4
+    o = x.new_zeros(b, c, h, 2, w, 2)
+    o[:, :, :, 0, :, 0] = x
+    o = F.pad(o.reshape(b, c, 2 * h, 2 * w), [2, 1, 2, 1])
+    wk = torch.flip(k, [0, 1]).view(1, 1, 4, 4)
+    return F.conv2d(o.reshape(b * c, 1, 2 * h + 3, 2 * w + 3), wk).view(b, c, 2 * h, 2 * w)
+
+
+def rgb_up(skip16):
+    """[B, h, w, 16] -> [B, 2h, 2w, 16]: channels 0..3 filtered, 4..15 zero (p2l.h)."""
+    x = skip16[..., :4].permute(0, 3, 1, 2)
+    up = upfirdn2d_up2(x).permute(0, 2, 3, 1)
+    return torch.cat([up, up.new_zeros(up.shape[:3] + (12,))], dim=3)
+
+
+def rgb_up_bwd(dout16, h, w):
+    B = dout16.shape[0]
+    return vjp(rgb_up, [dout16.new_zeros(B, h, w, 16)], dout16)
+
+
+def clamp16(x16):
+    """channels 0..2 clamped to [-1, 1], 3..15 zero."""
+    y = torch.zeros_like(x16)
+    idx = torch.zeros(16, dtype=torch.bool)
+    idx[:3] = True
+    return torch.where(idx, torch.clamp(x16, -1.0, 1.0), y)
+
+
+def clamp16_bwd(x16, dy16):
+    return vjp(clamp16, [x16], dy16)
+
+
+# ---- BigGAN conditioning ------------------------------------------------------------------------------------------
+def cbn_fold(g_raw, b_raw, mean, rstd):             # s = (1 + g) * rstd ; t = b - mean * s
+    s = (1.0 + g_raw) * rstd.to(g_raw.dtype)
+    return s, b_raw - mean.to(g_raw.dtype) * s
+
+
+def cbn_fold_bwd(ds, dt, mean, rstd):
+    z = torch.zeros_like(ds)
+    return vjp(lambda g_, b_: cbn_fold(g_, b_, mean.to(ds.dtype), rstd.to(ds.dtype)), [z, z.clone()], (ds, dt))
+
+
+def linear(x, W, bias=None):                        # y[b][n] = sum_k x[b][k] W[k][n] + bias[n]
+    y = x @ W.to(x.dtype)
+    return y if bias is None else y + bias.to(x.dtype)
+
+
+def linear_bwd(dy, W):
+    K = W.shape[0]
+    return vjp(lambda x_: linear(x_, W.to(dy.dtype)), [dy.new_zeros(dy.shape[0], K)], dy)
+
+
+# ---- image layout -------------------------------------------------------------------------------------------------
+def nchw3_to_nhwc16(src):
+    B, _, H, W = src.shape
+    out = src.new_zeros(B, H, W, 16)
+    out[..., :3] = src.permute(0, 2, 3, 1)
+    return out
+
+
+def nhwc16_to_nchw3(src16):
+    return src16[..., :3].permute(0, 3, 1, 2).contiguous()
+
+
+def tanh_bwd16(img16, dimg16):
+    """d(pre-tanh) on channels 0..2 = autograd through tanh at pre = atanh(img); channel 3 -> 0, 4..15 unchanged"""
+    img = img16[..., :3]
+    pre = torch.atanh(img.clamp(-1 + 1e-12, 1 - 1e-12))
+    out = dimg16.clone()
+    out[..., :3] = vjp(torch.tanh, [pre], dimg16[..., :3])
+    out[..., 3] = 0
+    return out
+
+
+def relu_mask(y, g):
+    return vjp(torch.relu, [y], g)                  # torch.relu's gradient at 0 (and -0) is 0
+
+
+# ---- losses -------------------------------------------------------------------------------------------------------
+def _w(weight, loss_mask):
+    return weight if loss_mask is None else loss_mask.to(weight.dtype) * weight
+
+
+def weight_sum(weight, loss_mask=None):             # [B,3,H,W] -> [B]
+    return _w(weight, loss_mask).sum(dim=(1, 2, 3))
+
+
+def weight_map(weight, loss_mask=None):             # [B,3,H,W] -> [B,H,W]
+    return _w(weight, loss_mask).sum(dim=1)
+
+
+def l1_loss(img16, target, weight, loss_mask=None):
+    """sum |target - out| * w / sum w over (c, p): ReconstructionLoss with weights (loss_functions.py:117-124)."""
+    out = nhwc16_to_nchw3(img16)
+    w = _w(weight.to(img16.dtype), loss_mask)
+    return (torch.abs(target.to(img16.dtype) - out) * w).sum(dim=(1, 2, 3)) / w.sum(dim=(1, 2, 3))
+
+
+def l1_loss_bwd(img16, target, weight, loss_mask, gscale):
+    return vjp(lambda i_: l1_loss(i_, target, weight, loss_mask), [img16], gscale)
+
+
+def reduce_rows(partial, scale, div=None):
+    s = partial.sum(dim=1) * scale
+    return s if div is None else s / div.to(s.dtype)
+
+
+def vec_scale_div(a, scale, div=None):
+    return a * scale if div is None else a * scale / div.to(a.dtype)
+
+
+# ---- optimiser ----------------------------------------------------------------------------------------------------
+def adam_reference(p0, grads, lr, first_step=1, m0=None, v0=None):
+    """torch.optim.Adam (defaults) stepped on the CPU in fp32 from step number `first_step`; returns the parameter
+    after every step."""
+    p = p0.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([p], lr=lr)
+    if first_step > 1 or m0 is not None:
+        st = opt.state[p]
+        st['step'] = torch.tensor(float(first_step - 1))
+        st['exp_avg'] = (torch.zeros_like(p0) if m0 is None else m0.clone())
+        st['exp_avg_sq'] = (torch.zeros_like(p0) if v0 is None else v0.clone())
+    out = []
+    for g in grads:
+        p.grad = g.clone()
+        opt.step()
+        out.append(p.detach().clone())
+    return out
