@@ -878,6 +878,26 @@ size_t p2l_gram_f64_ws_bytes(int64_t rows, int cols, int trans);
 int p2l_gram_f64(const float* X, int64_t rows, int cols, int64_t ld, int trans, double* gram, double* colsum,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* Poisson compositing (pix2latent/utils/image.py poisson_blend): paste `generated` into `target` over the masked
+ * region so that the seam vanishes.  NCHW fp32 images in [-1, 1]; mask uint8 [H][W] per image (non-zero = inside),
+ * one mask for all channels.  Per (image, channel), with Omega = the masked pixels that are not on the outermost
+ * one-pixel frame of the image:
+ *   out = target outside Omega (bit for bit), out = clamp(generated + u, -1, 1) inside, where
+ *   4 u(p) - sum_{q in N4(p), in Omega} u(q) = sum_{q in N4(p), not in Omega} (target(q) - generated(q)).
+ * This is the contract (cv2.seamlessClone NORMAL_CLONE solves a neighbouring problem with another solver and is
+ * NOT reproduced byte for byte).  Solver: conjugate gradients in fp64, one block per system, until
+ * |r| <= tol |b| or max_iter iterations; iters [Bn * C] int32 and relres [Bn * C] fp64 receive the iteration
+ * count and the final relative residual of every system (0 and 0 for an empty Omega or b = 0).  All sums run in
+ * a fixed order: a system's result does not depend on Bn or on its place in the batch.  target_bstride /
+ * mask_bstride: elements between the images of a batch, 0 = one target / mask shared by all.  out must not
+ * alias an input.  Refuses (P2L_EINVAL, before the launch) NULL pointers, sizes < 1, a stride between 0 and one
+ * image, tol < 0 or NaN, max_iter < 0; P2L_EWS when ws_bytes < p2l_poisson_blend_ws_bytes (host-only; 0 for
+ * sizes it refuses).  One launch, no memset. */
+size_t p2l_poisson_blend_ws_bytes(int Bn, int C, int H, int W);
+int p2l_poisson_blend(const float* target, int64_t target_bstride, const uint8_t* mask, int64_t mask_bstride,
+                      const float* generated, float* out, int Bn, int C, int H, int W, double tol, int max_iter,
+                      int32_t* iters, double* relres, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* StyleGAN2 (rosinality) pieces; replace fused_bias_act / upfirdn2d and the   */
 /* torch ops inside Generator.forward (reference model/stylegan2.py:116-125).  */
