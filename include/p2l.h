@@ -878,6 +878,18 @@ size_t p2l_gram_f64_ws_bytes(int64_t rows, int cols, int trans);
 int p2l_gram_f64(const float* X, int64_t rows, int cols, int64_t ld, int trans, double* gram, double* colsum,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* The same for a panel of up to 512 columns (StyleGAN2's W space, pix2latent/edit/ganspace.py w_covariance):
+ * gram = X^T X ([cols][cols] row-major, exactly symmetric) and colsum = the column sums of X, both fp64 device
+ * buffers.  rows >= 1, 1 <= cols <= 512; element (r, j) of X is X[r * ld + j], ld >= cols; columns >= cols and
+ * rows >= rows of the buffer are never read.  Products are exact, the sums fp64 in a fixed order (no atomics;
+ * each block owns a fixed row range of one pair of 128-column panels, a finish kernel adds the partials in
+ * range order): the result depends on (rows, cols) only, bit for bit.  Needs p2l_gram_f64_wide_ws_bytes of
+ * workspace (0 for invalid sizes; at most 68 MB); two launches, no memset.  P2L_EINVAL for a NULL X, gram or
+ * colsum and for sizes outside the above, P2L_EWS for a missing or short workspace, both before any launch. */
+size_t p2l_gram_f64_wide_ws_bytes(int64_t rows, int cols);
+int p2l_gram_f64_wide(const float* X, int64_t rows, int cols, int64_t ld, double* gram, double* colsum,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* Poisson compositing (pix2latent/utils/image.py poisson_blend): paste `generated` into `target` over the masked
  * region so that the seam vanishes.  NCHW fp32 images in [-1, 1]; mask uint8 [H][W] per image (non-zero = inside),
  * one mask for all channels.  Per (image, channel), with Omega = the masked pixels that are not on the outermost

@@ -309,7 +309,7 @@ EXPORTS = [
     'p2l_sg2_blur_fwd_amax', 'p2l_sg2_styled_act_bwd_amax', 'p2l_sg2_blur_bwd_amax', 'p2l_sg2_noise_relayout',
     'p2l_sg2_rows_defer_begin', 'p2l_sg2_rows_defer_flush', 'p2l_sg2_rows_defer_cancel',
     'p2l_color_adjust_ws_bytes', 'p2l_color_adjust',
-    'p2l_gram_f64_ws_bytes', 'p2l_gram_f64',
+    'p2l_gram_f64_ws_bytes', 'p2l_gram_f64', 'p2l_gram_f64_wide_ws_bytes', 'p2l_gram_f64_wide',
     'p2l_poisson_blend_ws_bytes', 'p2l_poisson_blend',
 ]
 
@@ -346,7 +346,7 @@ def lib():
                      'p2l_alexloss_ws_bytes', 'p2l_alex_cache_floats', 'p2l_sqzloss_ws_bytes', 'p2l_sqz_cache_floats', 'p2l_gemm_ws_bytes',
                      'p2l_packed_weight_floats', 'p2l_packed_subpix_weight_floats', 'p2l_attn_fwd_ws_bytes', 'p2l_affine_grid_sample_bwd_ws_bytes',
                      'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes',
-                     'p2l_gram_f64_ws_bytes', 'p2l_poisson_blend_ws_bytes'):
+                     'p2l_gram_f64_ws_bytes', 'p2l_gram_f64_wide_ws_bytes', 'p2l_poisson_blend_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
         # (64-bit sizes: without argtypes ctypes would pass them as C int)
         # the small entry points that take an int64_t count or a float: a bare Python number would travel as C int
@@ -368,6 +368,9 @@ def lib():
         _lib.p2l_gram_f64_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
         _lib.p2l_gram_f64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.p2l_gram_f64_wide_ws_bytes.argtypes = [C.c_int64, C.c_int]
+        _lib.p2l_gram_f64_wide.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]
         _lib.p2l_poisson_blend_ws_bytes.argtypes = [i32, i32, i32, i32]
         _lib.p2l_poisson_blend.argtypes = [vp, i64_, vp, i64_, vp, vp, i32, i32, i32, i32, C.c_double, i32,
                                            vp, vp, vp, C.c_size_t, vp]

@@ -1,13 +1,16 @@
 """BigGANLatentEditor (reference pix2latent/edit/editor.py): loads the `vars.npy` an inversion saved and
-re-renders its best candidate with the class swapped or z moved along a GANSpace direction."""
+re-renders its best candidate with the class swapped or z moved along a GANSpace direction.
+StyleGAN2LatentEditor does the same for the StyleGAN2 results (z or w+ search): the latent moves along a
+principal direction of W, in all layers or in some."""
 import numpy as np
 import torch
 
 from ..model import BigGAN
 from ..utils.checkpoint import load_result
-from .ganspace import biggan_components
+from .ganspace import biggan_components, stylegan2_components
 
-SWEEP_CHUNK = 18            # render_z_sweep: images per forward
+SWEEP_CHUNK = 18            # render_z_sweep / render_w_sweep: images per forward
+NOISE_SEED = 0              # StyleGAN2LatentEditor, z search: the seed of its fixed per-layer noise
 
 
 class BigGANLatentEditor():
@@ -70,3 +73,80 @@ class BigGANLatentEditor():
         with torch.no_grad():
             out = self.model(self._z, self._c)[0]
         return out
+
+
+class StyleGAN2LatentEditor():
+    def __init__(self, model):
+        self.model = model
+
+    def _device(self):
+        return self.model._dev
+
+    def load_result(self, var_path):
+        """ load optimized result: the best candidate's latent as w+ [1, n_latent, 512] and its per-layer
+        noises (list of [1, 1, h, w]).  z search: w = mapping(z) in every layer, and a noise list drawn once
+        from a seeded CPU generator (the model draws fresh noise on every forward, which would change the
+        image between two renders of one edit).  w+ search: the stored latent and its stored noises. """
+        model, dev = self.model, self._device()
+        self._var = load_result(var_path)
+        self._idx = np.argmin(self._var.loss[-1][1]['loss'])
+        z = self._var.input.z.data[self._idx].detach().float().to(dev)
+        n_latent = model._desc.n_latent
+        with torch.no_grad():
+            if model.search == 'z':
+                w = model.mapping(z.reshape(1, 512))
+                self._latent = w.unsqueeze(1).expand(-1, n_latent, -1).contiguous()
+                g = torch.Generator().manual_seed(NOISE_SEED)
+                self._noises = [torch.randn(1, 1, s[-2], s[-1], generator=g).to(dev) for s in model.noise_shape]
+            else:
+                self._latent = z.reshape(1, n_latent, 512).contiguous()
+                flat = self._var.input.noises.data[self._idx].detach().float().to(dev)
+                self._noises = [n.contiguous() for n in model.reshape_noise(flat.reshape(1, -1))]
+        return
+
+    def _components(self):
+        if not hasattr(self, 'components'):
+            self.components, self.stdev, self.mean = stylegan2_components(self.model)
+        return self.components
+
+    def _layers(self, layers):
+        n_latent = self.model._desc.n_latent
+        idx = list(range(n_latent)) if layers is None else [int(l) for l in layers]
+        bad = [l for l in idx if not 0 <= l < n_latent]
+        if bad:
+            raise ValueError('layers must be in [0, %d), got %s' % (n_latent, bad))
+        return idx
+
+    def _edited(self, component, sigma, idx):
+        """the latent with sigma * stdev[k] * components[k] added to the rows `idx`"""
+        U = self._components()
+        latent = self._latent.clone()
+        latent[:, idx] = latent[:, idx] + sigma * self.stdev[component] * U[component]
+        return latent
+
+    def _render(self, latent):
+        B = latent.shape[0]
+        noises = [n.expand(B, -1, -1, -1) for n in self._noises]
+        with torch.no_grad():
+            return self.model.synthesis(latent, noises)
+
+    def edit_w(self, component, sigma, layers=None):
+        """ edit the latent along a principal direction of W in `layers` (indices in [0, n_latent); None:
+        all of them) """
+        return self._render(self._edited(component, sigma, self._layers(layers)))[0]
+
+    def render_w_sweep(self, components, sigmas, layers=None):
+        """edit_w for every (component, sigma) pair, component-major: image i * len(sigmas) + j is
+        edit_w(components[i], sigmas[j], layers), bit for bit (the generator is batch-invariant).  Rendered
+        in batches of at most 18.  Returns [len(components) * len(sigmas), 3, S, S]."""
+        idx = self._layers(layers)
+        S = self.model.im_res
+        ws = [self._edited(k, s, idx) for k in components for s in sigmas]
+        if not ws:
+            return torch.empty(0, 3, S, S, device=self._device())
+        w = torch.cat(ws)
+        return torch.cat([self._render(w[i:i + SWEEP_CHUNK]) for i in range(0, w.shape[0], SWEEP_CHUNK)])
+
+    def default(self):
+        """ optimized result """
+        return self._render(self._latent)[0]

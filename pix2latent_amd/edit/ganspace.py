@@ -1,4 +1,4 @@
-"""GANSpace components of BigGAN in z-space (reference pix2latent/edit/ganspace.py).
+"""GANSpace components of BigGAN in z-space (reference pix2latent/edit/ganspace.py) and of StyleGAN2 in W.
 
 The reference draws z, materialises feat = gen_z([z, c]) (N x 32768), runs `torch.pca_lowrank` on it and
 fits z ~ x u^T with 100 Adam steps.  gen_z is affine and c is the same in every row, so the centred
@@ -7,6 +7,11 @@ bias and the class cancel, and everything the procedure needs follows from two 1
 S = Zc^T Zc and G = W_z^T W_z.  Both come from one HIP kernel (`p2l_gram_f64`, the
 only O(N) work); the rest is 128 x 128 algebra and the reference's Adam loop on the host in float64.
 The PCA is the exact one that `pca_lowrank`'s randomized sketch approximates.
+
+StyleGAN2 (the GANSpace paper's own case; the reference has no editor for it): the principal directions of
+w = mapping(z) are the eigenvectors of the 512 x 512 covariance of w.  Its Gram and column sums come from
+`p2l_gram_f64_wide`, one call per chunk of samples (`w_covariance`); the eigh is host float64
+(`components_from_covariance`).
 """
 import ctypes as C
 
@@ -149,3 +154,98 @@ def biggan_components(model, class_lbl, num_components=32, num_samples=12800,
     S = zz - torch.outer(zsum, zsum) / num_samples            # Zc^T Zc = Z^T Z - N mean mean^T
     u = components_from_grams(S, G, num_samples, u0, num_components, method)
     return u.float().to(dev)
+
+
+# ---------------------------------------------------------------------------------------- StyleGAN2, W space
+W_DIM = 512
+
+
+def gram_f64_wide(x, rows, cols, ld):
+    """(X^T X [cols, cols], column sums [cols]) of the fp32 panel X of up to 512 columns inside the device
+    tensor `x`, float64 device tensors (p2l_gram_f64_wide): element (r, j) at x.flatten()[r * ld + j]."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError('gram_f64_wide expects a contiguous fp32 device tensor')
+    if rows < 1 or not 1 <= cols <= W_DIM or ld < cols or (rows - 1) * ld + cols - 1 >= x.numel():
+        raise ValueError('gram_f64_wide: rows %d, cols %d, ld %d do not describe a panel of a tensor of '
+                         '%d floats' % (rows, cols, ld, x.numel()))
+    L = N.lib()
+    nbytes = L.p2l_gram_f64_wide_ws_bytes(rows, cols)
+    with torch.cuda.device(x.device):
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        gram = torch.empty(cols, cols, dtype=torch.float64, device=x.device)
+        colsum = torch.empty(cols, dtype=torch.float64, device=x.device)
+        N.check(L.p2l_gram_f64_wide(x.data_ptr(), rows, cols, ld, gram.data_ptr(), colsum.data_ptr(),
+                                    ws.data_ptr(), nbytes, N.stream()), 'p2l_gram_f64_wide')
+    return gram, colsum
+
+
+def w_covariance(model, num_samples, chunk_rows=65536):
+    """(C [512, 512], mean [512]) of w = model.mapping(z), z ~ N(0, I), float64 on the CPU.
+
+    z is drawn with torch.randn on the CPU generator in chunks of `chunk_rows` rows, so under one
+    torch.manual_seed the draws depend on (num_samples, chunk_rows) only.  Each chunk is mapped on the device
+    and goes through p2l_gram_f64_wide once; the Grams and column sums are added in float64 on the device in
+    chunk order, C = (G - s s^T / N) / (N - 1).  Only one chunk of w exists at a time."""
+    if num_samples < 2:
+        raise ValueError('num_samples must be at least 2')
+    if chunk_rows < 1:
+        raise ValueError('chunk_rows must be at least 1')
+    dev = model._dev
+    G = torch.zeros(W_DIM, W_DIM, dtype=torch.float64, device=dev)
+    s = torch.zeros(W_DIM, dtype=torch.float64, device=dev)
+    with torch.no_grad():
+        for start in range(0, num_samples, chunk_rows):
+            n = min(chunk_rows, num_samples - start)
+            w = model.mapping(torch.randn(n, W_DIM)).contiguous()
+            g, cs = gram_f64_wide(w, n, W_DIM, W_DIM)
+            G += g
+            s += cs
+            del w
+    G, s = G.cpu(), s.cpu()
+    C = (G - torch.outer(s, s) / num_samples) / (num_samples - 1)
+    return C, s / num_samples
+
+
+def components_from_covariance(C, num_components):
+    """(V [K, d] unit rows, stdev [K]) float64 on the CPU: the top K eigenpairs of the covariance C [d, d] in
+    descending order, stdev = sqrt(max(lambda, 0)).  Each direction is oriented by `orient`: its entry of
+    largest magnitude is positive, the lowest index on ties."""
+    C = torch.as_tensor(C, dtype=torch.float64).cpu()
+    d = C.shape[0]
+    if C.dim() != 2 or C.shape[1] != d:
+        raise ValueError('C must be square, got %s' % (tuple(C.shape),))
+    if not 1 <= num_components <= d:
+        raise ValueError('num_components must be in [1, %d], got %d' % (d, num_components))
+    lam, Y = torch.linalg.eigh(C)
+    lam = lam.flip(0)[:num_components]
+    Y = Y.flip(1)[:, :num_components]
+    V = (Y * orient(Y)).t().contiguous()
+    return V, lam.clamp(min=0.0).sqrt()
+
+
+def stylegan2_components(model, num_components=32, num_samples=100000):
+    """
+    Args:
+        model: StyleGAN2 model instance
+        num_components: number of PCA components (at most 512)
+        num_samples: number of z samples to estimate the covariance of w = mapping(z)
+
+    Returns (components [K, 512], stdev [K], mean [512]) float32 on the model's device: the principal
+    directions of W (unit rows), the standard deviation of w along each, and the mean w.  Cached on the model
+    per (num_components, num_samples).  z is drawn on the CPU generator (w_covariance).
+
+    GANSpace: Erik Härkönen et al., https://arxiv.org/abs/2004.02546
+    """
+    if not 1 <= num_components <= W_DIM:
+        raise ValueError('num_components must be in [1, %d], got %d' % (W_DIM, num_components))
+    if num_samples < 2:
+        raise ValueError('num_samples must be at least 2')
+    cache = getattr(model, '_ganspace_w', None)
+    if cache is None:
+        cache = model._ganspace_w = {}
+    key = (num_components, num_samples)
+    if key not in cache:
+        C, mean = w_covariance(model, num_samples)
+        V, stdev = components_from_covariance(C, num_components)
+        cache[key] = tuple(t.float().to(model._dev) for t in (V, stdev, mean))
+    return cache[key]
