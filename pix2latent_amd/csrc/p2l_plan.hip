@@ -8,24 +8,9 @@
 // weight gradients); target features are cached (F8).
 // No allocation, no synchronisation: one workspace arena owned by the caller,
 // every launch on the caller's stream, so a whole step can be graph-captured.
-#include "p2l_common.h"
+#include "p2l_loss_shell.h"
 
 namespace {
-
-struct Arena {
-  size_t off = 0;  // in floats
-  size_t take(size_t n) {
-    const size_t o = off;
-    off += (n + 63) & ~(size_t)63;
-    return o;
-  }
-};
-
-#define RET_IF(x)          \
-  do {                     \
-    int _rc = (x);         \
-    if (_rc) return _rc;   \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // small kernels local to the plans
@@ -905,19 +890,21 @@ inline int vgg_tap_of(int i) {
   return -1;
 }
 
-struct PLLayout {
+struct PLLayout : LossLayout {
   size_t y[13];        // post-ReLU conv outputs
   size_t yp[4];        // pooled outputs after convs 1,3,6,9
-  size_t tgt16;        // prepare: target in NHWC16
-  size_t wsrc;         // prepare: per-pixel weight map
-  size_t part;         // loss partial sums
-  size_t lp, l1;       // per-sample partial losses
-  size_t gs;           // per-sample gradient scale
-  size_t ga, gb, gtap; // backward scratch
   size_t skws, skws_floats;
   size_t amax_ring, amax_set_floats, amax_set_stride;   // AmaxReg
-  size_t total;
 };
+
+// grids and channels of the five taps (p2l_loss_cache_floats asks for them at ANY size, as it always has)
+void vgg_taps(int H, int W, LossTaps& T) {
+  T.n = 5;
+  for (int k = 0; k < 5; ++k) {
+    const int ci = kVggTapConv[k];
+    T.h[k] = H / kVggDiv[ci]; T.w[k] = W / kVggDiv[ci]; T.C[k] = kVggCout[ci];
+  }
+}
 
 int pl_layout(int B, int H, int W, PLLayout& L) {
   if (B < 1 || H < 32 || W < 32 || !is_pow2(H) || !is_pow2(W)) return P2L_EINVAL;
@@ -946,21 +933,9 @@ int pl_layout(int B, int H, int W, PLLayout& L) {
       if (n4 > max_slots) max_slots = n4;
     }
   }
-  L.tgt16 = a.take((size_t)B * H * W * 16);
-  L.wsrc = a.take((size_t)B * H * W);
-  size_t maxpart = (size_t)p2l_l1_loss_nblk(H, W);
-  for (int k = 0; k < 5; ++k) {
-    const int d = kVggDiv[kVggTapConv[k]];
-    const size_t nb = (size_t)p2l_lpips_tap_nblk((H / d) * (W / d), kVggCout[kVggTapConv[k]]);
-    if (nb > maxpart) maxpart = nb;
-  }
-  L.part = a.take((size_t)B * maxpart);
-  L.lp = a.take(B);
-  L.l1 = a.take(B);
-  L.gs = a.take(B);
-  L.ga = a.take(max_act);
-  L.gb = a.take(max_act);
-  L.gtap = a.take(max_act);
+  vgg_taps(H, W, L.taps);
+  for (int k = 0; k < 5; ++k) L.taps.y[k] = L.y[kVggTapConv[k]];
+  L.tail.take(a, B, H, W, L.taps, max_act);
   L.skws_floats = max_sk;
   L.skws = a.take(max_sk ? max_sk : 64);
   L.amax_set_floats = (size_t)B * max_slots;
@@ -1001,15 +976,9 @@ int vgg_forward(const P2LVggLpips* v, const float* img16, int B, int H, int W, f
 
 extern "C" size_t p2l_loss_cache_floats(int B, int H, int W, size_t nft_off[5],
                                         size_t wt_off[5], size_t* wsum_off) {
-  Arena a;
-  for (int k = 0; k < 5; ++k) {
-    const int d = kVggDiv[kVggTapConv[k]];
-    const size_t P = (size_t)(H / d) * (W / d);
-    nft_off[k] = a.take((size_t)B * P * kVggCout[kVggTapConv[k]]);
-    wt_off[k] = a.take((size_t)B * P);
-  }
-  *wsum_off = a.take(B);
-  return a.off;
+  LossTaps T;
+  vgg_taps(H, W, T);
+  return loss_cache_floats(T, B, nft_off, wt_off, wsum_off);
 }
 
 // debug/test hook: float offset + shape of the post-ReLU output of VGG conv `idx` (0..12) in ws
@@ -1045,26 +1014,9 @@ extern "C" int p2l_projloss_prepare(const P2LVggLpips* v, const float* target,
   g_plan_wfmt = v ? v->wfmt : P2L_WFMT_F32;
   PLLayout L;
   RET_IF(pl_layout(B, H, W, L));
-  if (!ws || ws_bytes < L.total * sizeof(float) || !cache || !target) return P2L_EWS;
-  float* Wk = (float*)ws;
-  if (weight) {
-    RET_IF(p2l_weight_sum(weight, loss_mask, cache->wsum, B, 3 * H * W, st));
-    RET_IF(p2l_weight_map(weight, loss_mask, Wk + L.wsrc, B, H, W, st));
-    for (int k = 0; k < 5; ++k) {
-      const int d = kVggDiv[kVggTapConv[k]];
-      RET_IF(p2l_bilinear_adjoint(Wk + L.wsrc, cache->wt[k], B, H, W, H / d, W / d, st));
-    }
-  }
-  if (v) {
-    RET_IF(p2l_nchw3_to_nhwc16(target, Wk + L.tgt16, B, H, W, st));
-    RET_IF(vgg_forward(v, Wk + L.tgt16, B, H, W, Wk, L, st));
-    for (int k = 0; k < 5; ++k) {
-      const int ci = kVggTapConv[k], d = kVggDiv[ci];
-      RET_IF(p2l_lpips_normalize(Wk + L.y[ci], cache->nft[k],
-                                 (int64_t)B * (H / d) * (W / d), kVggCout[ci], st));
-    }
-  }
-  return P2L_OK;
+  L.taps.bind(v, cache);
+  return loss_prepare(L, target, weight, loss_mask, B, H, W, ws, ws_bytes, st,
+                      [&](const float* x) { return vgg_forward(v, x, B, H, W, (float*)ws, L, st); });
 }
 
 extern "C" int p2l_projloss_fwd(const P2LVggLpips* v, const float* img16,
@@ -1076,27 +1028,9 @@ extern "C" int p2l_projloss_fwd(const P2LVggLpips* v, const float* img16,
   g_plan_wfmt = v ? v->wfmt : P2L_WFMT_F32;
   PLLayout L;
   RET_IF(pl_layout(B, H, W, L));
-  if (!ws || ws_bytes < L.total * sizeof(float) || !cache || !img16 || !loss) return P2L_EWS;
-  float* Wk = (float*)ws;
-  float* l1 = loss_l1 ? loss_l1 : Wk + L.l1;
-  float* lp = loss_lpips ? loss_lpips : Wk + L.lp;
-  RET_IF(p2l_l1_loss_fwd(img16, target, weight, loss_mask, cache->wsum, l1, Wk + L.part, B,
-                         H, W, st));
-  RET_IF(p2l_vec_scale_div(l1, nullptr, loss, B, 1.f, st));
-  if (use_lpips) {
-    if (!v) return P2L_EINVAL;
-    RET_IF(vgg_forward(v, img16, B, H, W, Wk, L, st));
-    for (int k = 0; k < 5; ++k) {
-      const int ci = kVggTapConv[k], d = kVggDiv[ci];
-      const int P = (H / d) * (W / d), C = kVggCout[ci];
-      const int nblk = p2l_lpips_tap_nblk(P, C);
-      RET_IF(p2l_lpips_tap_fwd(Wk + L.y[ci], cache->nft[k], (int64_t)P * C, v->lin[k],
-                               cache->wt[k], P, Wk + L.part, B, P, C, st));
-      RET_IF(p2l_reduce_rows(Wk + L.part, lp, B, nblk, 1.f, cache->wsum, k > 0, st));
-    }
-    RET_IF(p2l_reduce_rows(lp, loss, B, 1, beta, nullptr, 1, st));
-  }
-  return P2L_OK;
+  L.taps.bind(v, cache);
+  return loss_fwd(L, img16, target, weight, loss_mask, beta, use_lpips, B, H, W, ws, ws_bytes, loss, loss_l1,
+                  loss_lpips, st, [&](const float* x) { return vgg_forward(v, x, B, H, W, (float*)ws, L, st); });
 }
 
 extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
@@ -1110,27 +1044,18 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
 #endif
   PLLayout L;
   RET_IF(pl_layout(B, H, W, L));
-  if (!ws || ws_bytes < L.total * sizeof(float) || !cache || !img16 || !gloss || !dimg16)
-    return P2L_EWS;
+  L.taps.bind(v, cache);
+  LossBwd bw;
+  RET_IF(loss_bwd_begin(L, img16, target, weight, loss_mask, beta, use_lpips, gloss, B, H, W, ws, ws_bytes, dimg16,
+                        st, bw));
+  if (bw.done) return P2L_OK;
   float* Wk = (float*)ws;
-  if (!use_lpips) {
-    return p2l_l1_loss_bwd(img16, target, weight, loss_mask, cache->wsum, gloss, dimg16, B,
-                           H, W, 0, st);
-  }
-  if (!v) return P2L_EINVAL;
-  // gs[b] = gloss[b] * beta / wsum[b]
-  RET_IF(p2l_vec_scale_div(gloss, cache->wsum, Wk + L.gs, B, beta, st));
+  const LossTaps& T = L.taps;
   AmaxScope amax_scope(Wk + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
-  float* ga = Wk + L.ga;   // gradient w.r.t. the PRE-ReLU output of conv i (masked)
-  float* gb = Wk + L.gb;
-  float* gtap = Wk + L.gtap;
+  float *ga = bw.ga, *gb = bw.gb;
   // top: relu5_3 is only consumed by the LPIPS tap
-  {
-    const int ci = 12, d = kVggDiv[ci], P = (H / d) * (W / d), C = kVggCout[ci];
-    RET_IF(p2l_lpips_tap_bwd(Wk + L.y[ci], cache->nft[4], (int64_t)P * C, v->lin[4],
-                             cache->wt[4], P, Wk + L.gs, gtap, B, P, C, st));
-    RET_IF(p2l_relu_mask(Wk + L.y[ci], C, gtap, C, ga, C, (int64_t)B * P, C, st));
-  }
+  RET_IF(bw.tap(4));
+  RET_IF(p2l_relu_mask(Wk + L.y[12], T.C[4], bw.gtap, T.C[4], ga, T.C[4], (int64_t)B * T.P(4), T.C[4], st));
   int pi = 3;
   for (int i = 12; i >= 1; --i) {
     const int h = H / kVggDiv[i], w = W / kVggDiv[i];
@@ -1147,24 +1072,22 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
       // input is maxpool(relu(conv_{i-1})); conv_{i-1} is also an LPIPS tap
       RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
       const int k = vgg_tap_of(prev);
-      const int hp = H / kVggDiv[prev], wp = W / kVggDiv[prev];
-      const int P = hp * wp, C = kVggCout[prev];
+      const int hp = T.h[k], wp = T.w[k], P = T.P(k), C = T.C[k];
       // (written by a non-conv kernel, which leaves its own maxima for the dgrad that reads ga next)
       amax_drop(ga);
       float* so = nullptr;
       int set_o = -1;
 #ifdef P2L_AB_TAP_POOL_2PASS      // A/B builds: the two-pass form of rounds 1-4
-      RET_IF(p2l_lpips_tap_bwd(Wk + L.y[prev], cache->nft[k], (int64_t)P * C, v->lin[k],
-                               cache->wt[k], P, Wk + L.gs, gtap, B, P, C, st));
+      RET_IF(bw.tap(k));
       const int ns = p2l_maxpool2_bwd_amax_slots(hp, wp, C);
       if (g_amax && prev >= 1 && ns > 0 && (size_t)ns * B <= g_amax->set_floats) so = g_amax->take(&set_o);
-      RET_IF(p2l_maxpool2_bwd_amax(Wk + L.y[prev], C, gb, C, gtap, C, ga, C, B, hp, wp, C, 1, so, st));
+      RET_IF(p2l_maxpool2_bwd_amax(Wk + L.y[prev], C, gb, C, bw.gtap, C, ga, C, B, hp, wp, C, 1, so, st));
 #else
       // tap gradient + pool backward of gb + ReLU mask in one pass over conv_{i-1}'s output
       const int ns = p2l_lpips_tap_nblk(P, C);
       if (g_amax && prev >= 1 && ns > 0 && (size_t)ns * B <= g_amax->set_floats) so = g_amax->take(&set_o);
-      RET_IF(p2l_lpips_tap_pool_bwd(Wk + L.y[prev], cache->nft[k], (int64_t)P * C, v->lin[k], cache->wt[k], P,
-                                    Wk + L.gs, gb, ga, so, B, hp, wp, C, st));
+      RET_IF(p2l_lpips_tap_pool_bwd(Wk + T.y[k], T.nft[k], (int64_t)P * C, T.lin[k], T.wt[k], P, Wk + L.tail.gs, gb,
+                                    ga, so, B, hp, wp, C, st));
 #endif
       if (so) g_amax->put(ga, B, hp, wp, C, so, ns, set_o);
       --pi;
@@ -1181,8 +1104,5 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
     if (g_plan_wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
     RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
   }
-  if (use_lpips == 2) return P2L_OK;   // PerceptualLoss on its own: no L1 term
-  RET_IF(p2l_l1_loss_bwd(img16, target, weight, loss_mask, cache->wsum, gloss, dimg16, B, H,
-                         W, 1, st));
-  return P2L_OK;
+  return loss_bwd_end(bw);
 }

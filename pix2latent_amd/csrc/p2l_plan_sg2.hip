@@ -15,16 +15,10 @@
 //     transpose, input-gradient convs (sub-pixel ups=3 for the up convs) with the
 //     modulation backward (dx = dx'*s, ds = sum dx'*x) fused into their epilogue.
 // Noise layout at this boundary: layer-major, noise + Bn*noise_off[l] is [Bn][h*w].
-#include "p2l_common.h"
+#include "p2l_loss_shell.h"   // Arena, RET_IF
 #include "p2l_sg2_k.h"
 
 namespace {
-
-struct Arena {
-  size_t off = 0;
-  size_t take(size_t n) { const size_t o = off; off += (n + 63) & ~(size_t)63; return o; }
-};
-#define RET_IF(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
 struct SgLayout {
   size_t s[P2L_SG2_MAX_CONVS], d[P2L_SG2_MAX_CONVS], y[P2L_SG2_MAX_CONVS];

@@ -93,39 +93,27 @@ def weight_regularization(orig_model, curr_model, reg='l1', weight_dict=None):
 # ---------------------------------------------------------------------------
 # native engine shared by Reconstruction / Perceptual / Projection losses
 # ---------------------------------------------------------------------------
-class _VggLpipsParams(object):
-    """packed VGG16 + LPIPS-lin parameters on the device (P2LVggLpips)."""
-    prefix = 'vgg'
+class _LpipsParams(object):
+    """packed backbone + LPIPS-lin parameters of one network on the device.  A subclass names its descriptor
+    struct and packs its backbone's weights into it (`_pack_backbone`); the scaling layer and the linear layers
+    are the same for every network."""
+    prefix, desc_cls, taps = None, None, 5
 
     def __init__(self, weights, device):
         self.lib = N.lib()
         self.dev = torch.device(device)
         self.keep = []
-        self.desc = N.P2LVggLpips()
-        self.wfmt = N.default_wfmt()       # all 13 convs are 3x3
-        thin = N.default_thin() and self.wfmt != N.WFMT_F32    # first conv: 3 real input channels
-        self.desc.wfmt = (self.wfmt | (N.WFMT_FLAG_THIN if thin else 0) |
-                          (N.WFMT_FLAG_NO_AMAX if N.default_no_amax() else 0))
-        inv_scale = torch.tensor([1.0 / s for s in LPIPS_SCALE])
-        for i, (cin, cout) in enumerate(synthetic.VGG_CONVS):
-            w = weights['vgg.conv%d.weight' % i].float()
-            if i == 0:
-                f0 = N.WFMT_BF16X3T if thin else None
-                self.desc.w[i] = self._pack(w, 9, cout, 16, False, f0)
-                # d scaled / d img = 1/scale per input channel: fold into the dgrad copy
-                self.desc.wt[i] = self._pack(w * inv_scale.view(1, 3, 1, 1), 9, 32, cout, True, f0)
-            else:
-                self.desc.w[i] = self._pack(w, 9, cout, cin, False)
-                self.desc.wt[i] = self._pack(w, 9, cin, cout, True)
-            self.desc.b[i] = self._t(weights['vgg.conv%d.bias' % i])
-        for k in range(5):
-            self.desc.lin[k] = self._t(weights['lpips.lin%d.weight' % k].reshape(-1))
+        d = self.desc = self.desc_cls()
+        # d scaled / d img = 1/scale per input channel: folded into the first conv's input-gradient copy
+        self._pack_backbone(d, weights, torch.tensor([1.0 / s for s in LPIPS_SCALE]).view(1, 3, 1, 1))
+        for k in range(self.taps):
+            d.lin[k] = self._t(weights['lpips.lin%d.weight' % k].reshape(-1))
         s16, t16 = torch.zeros(16), torch.zeros(16)
         for c in range(3):
             s16[c] = 1.0 / LPIPS_SCALE[c]
             t16[c] = -LPIPS_SHIFT[c] / LPIPS_SCALE[c]
-        self.desc.in_s = self._t(s16)
-        self.desc.in_t = self._t(t16)
+        d.in_s = self._t(s16)
+        d.in_t = self._t(t16)
 
     def _t(self, t):
         t = t.detach().to(self.dev, torch.float32).contiguous()
@@ -135,60 +123,64 @@ class _VggLpipsParams(object):
     def _pack(self, w, taps, n_pad, k_pad, flip, fmt=None):
         if fmt is None:
             fmt = getattr(self, 'wfmt', N.WFMT_F32) if taps == 9 else N.WFMT_F32
-        dst = N.pack_conv_weight(w.detach().to(self.dev, torch.float32), taps, n_pad, k_pad, flip, fmt)
+        return self._packed(N.pack_conv_weight(w.detach().to(self.dev, torch.float32), taps, n_pad, k_pad, flip, fmt))
+
+    def _gpack(self, w, taps, n_pad, k_pad, flip):
+        return self._packed(N.pack_gconv_weight(w.detach().to(self.dev, torch.float32), taps, n_pad, k_pad, flip))
+
+    def _packed(self, dst):
         torch.cuda.current_stream().synchronize()
         self.keep.append(dst)
         return dst.data_ptr()
 
 
-class _AlexLpipsParams(object):
-    """packed torchvision-AlexNet features + LPIPS-lin parameters (P2LAlexLpips)."""
-    prefix = 'alex'
+class _VggLpipsParams(_LpipsParams):
+    """VGG16 (P2LVggLpips)."""
+    prefix, desc_cls = 'vgg', N.P2LVggLpips
 
-    def __init__(self, weights, device):
-        self.lib = N.lib()
-        self.dev = torch.device(device)
-        self.keep = []
-        self.desc = N.P2LAlexLpips()
-        inv_scale = torch.tensor([1.0 / s for s in LPIPS_SCALE])
+    def _pack_backbone(self, d, weights, inv_scale):
+        self.wfmt = N.default_wfmt()       # all 13 convs are 3x3
+        thin = N.default_thin() and self.wfmt != N.WFMT_F32    # first conv: 3 real input channels
+        d.wfmt = (self.wfmt | (N.WFMT_FLAG_THIN if thin else 0) |
+                  (N.WFMT_FLAG_NO_AMAX if N.default_no_amax() else 0))
+        for i, (cin, cout) in enumerate(synthetic.VGG_CONVS):
+            w = weights['vgg.conv%d.weight' % i].float()
+            if i == 0:
+                f0 = N.WFMT_BF16X3T if thin else None
+                d.w[i] = self._pack(w, 9, cout, 16, False, f0)
+                d.wt[i] = self._pack(w * inv_scale, 9, 32, cout, True, f0)
+            else:
+                d.w[i] = self._pack(w, 9, cout, cin, False)
+                d.wt[i] = self._pack(w, 9, cin, cout, True)
+            d.b[i] = self._t(weights['vgg.conv%d.bias' % i])
+
+
+class _AlexLpipsParams(_LpipsParams):
+    """torchvision-AlexNet features (P2LAlexLpips)."""
+    prefix, desc_cls = 'alex', N.P2LAlexLpips
+
+    def _pack_backbone(self, d, weights, inv_scale):
         for i, (cin, cout, k) in enumerate(synthetic.ALEX_CONVS):
             w = weights['alex.conv%d.weight' % i].float()
             if i == 0:
-                self.desc.w[i] = self._pack(w, k * k, cout, 16, False)
-                # direct input-gradient kernel: [k*k][3][cout], 1/scale folded in
-                w3 = (w * inv_scale.view(1, 3, 1, 1)).permute(2, 3, 1, 0).reshape(k * k, 3, cout)
-                self.desc.wt[i] = self._t(w3)
+                d.w[i] = self._pack(w, k * k, cout, 16, False)
+                # direct input-gradient kernel: [k*k][3][cout]
+                d.wt[i] = self._t((w * inv_scale).permute(2, 3, 1, 0).reshape(k * k, 3, cout))
             else:
-                self.desc.w[i] = self._pack(w, k * k, cout, cin, False)
-                self.desc.wt[i] = self._pack(w, k * k, cin, cout, True)
-            self.desc.b[i] = self._t(weights['alex.conv%d.bias' % i])
-        for k in range(5):
-            self.desc.lin[k] = self._t(weights['lpips.lin%d.weight' % k].reshape(-1))
-        s16, t16 = torch.zeros(16), torch.zeros(16)
-        for c in range(3):
-            s16[c] = 1.0 / LPIPS_SCALE[c]
-            t16[c] = -LPIPS_SHIFT[c] / LPIPS_SCALE[c]
-        self.desc.in_s = self._t(s16)
-        self.desc.in_t = self._t(t16)
-
-    _t = _VggLpipsParams._t
-    _pack = _VggLpipsParams._pack
+                d.w[i] = self._pack(w, k * k, cout, cin, False)
+                d.wt[i] = self._pack(w, k * k, cin, cout, True)
+            d.b[i] = self._t(weights['alex.conv%d.bias' % i])
 
 
-class _SqueezeLpipsParams(object):
-    """packed torchvision-SqueezeNet1.1 features + LPIPS-lin parameters (P2LSqueezeLpips, csrc/p2l_plan_squeeze.hip)."""
-    prefix = 'squeeze'
+class _SqueezeLpipsParams(_LpipsParams):
+    """torchvision-SqueezeNet1.1 features (P2LSqueezeLpips, csrc/p2l_plan_squeeze.hip)."""
+    prefix, desc_cls, taps = 'squeeze', N.P2LSqueezeLpips, 7
 
-    def __init__(self, weights, device):
-        self.lib = N.lib()
-        self.dev = torch.device(device)
-        self.keep = []
-        d = self.desc = N.P2LSqueezeLpips()
-        inv_scale = torch.tensor([1.0 / s for s in LPIPS_SCALE])
+    def _pack_backbone(self, d, weights, inv_scale):
         w = weights['squeeze.conv0.weight'].float()
         d.w0 = self._gpack(w, 9, 64, 16, False)
         d.b0 = self._t(weights['squeeze.conv0.bias'])
-        d.wt0 = self._t((w * inv_scale.view(1, 3, 1, 1)).permute(2, 3, 1, 0).reshape(9, 3, 64))
+        d.wt0 = self._t((w * inv_scale).permute(2, 3, 1, 0).reshape(9, 3, 64))
         for i, (cin, sq, ex) in enumerate(synthetic.SQZ_FIRES):
             g = lambda part, what: weights['squeeze.fire%d.%s.%s' % (i, part, what)].float()
             # squeeze 1x1: output channels padded to one 64-wide tile (the launch stores `sq` of them)
@@ -201,34 +193,19 @@ class _SqueezeLpipsParams(object):
             d.e3_w[i] = self._gpack(g('expand3x3', 'weight'), 9, ex, sq, False)
             d.e3_b[i] = self._t(g('expand3x3', 'bias'))
             d.e3_wt[i] = self._gpack(g('expand3x3', 'weight'), 9, 64, ex, True)
-        for k in range(7):
-            d.lin[k] = self._t(weights['lpips.lin%d.weight' % k].reshape(-1))
-        s16, t16 = torch.zeros(16), torch.zeros(16)
-        for c in range(3):
-            s16[c] = 1.0 / LPIPS_SCALE[c]
-            t16[c] = -LPIPS_SHIFT[c] / LPIPS_SCALE[c]
-        d.in_s = self._t(s16)
-        d.in_t = self._t(t16)
-
-    _t = _VggLpipsParams._t
-
-    def _gpack(self, w, taps, n_pad, k_pad, flip):
-        dst = N.pack_gconv_weight(w.detach().to(self.dev, torch.float32), taps, n_pad, k_pad, flip)
-        torch.cuda.current_stream().synchronize()
-        self.keep.append(dst)
-        return dst.data_ptr()
 
 
 class _CacheSlot(object):
     """target-dependent state of one (target, weight, loss_mask) chunk."""
 
-    def __init__(self, cache_floats, B, H, W, dev, taps=5):
+    def __init__(self, cache_floats, cache_cls, B, H, W, dev):
+        taps = len(cache_cls().nft)
         nft_off = (C.c_size_t * taps)()
         wt_off = (C.c_size_t * taps)()
         wsum_off = C.c_size_t(0)
         n = cache_floats(B, H, W, nft_off, wt_off, C.byref(wsum_off))
         self.buf = torch.empty(n, device=dev, dtype=torch.float32)
-        self.desc = N.P2LLossCache() if taps == 5 else N.P2LLossCache7()
+        self.desc = cache_cls()
         base = self.buf.data_ptr()
         for k in range(taps):
             self.desc.nft[k] = base + 4 * nft_off[k]
@@ -296,6 +273,12 @@ def _lane_attr(name):
                     lambda self, v: setattr(self._lane(), name, v))
 
 
+# _LpipsParams.prefix -> (stem of *_ws_bytes / _prepare / _fwd / _bwd, its cache_floats, its cache struct)
+_LOSS_ABI = {'vgg': ('p2l_projloss', 'p2l_loss_cache_floats', N.P2LLossCache),
+             'alex': ('p2l_alexloss', 'p2l_alex_cache_floats', N.P2LLossCache),
+             'squeeze': ('p2l_sqzloss', 'p2l_sqz_cache_floats', N.P2LLossCache7)}
+
+
 class _LossEngine(object):
     """workspace + target caches for p2l_projloss_*; one per loss object.
 
@@ -309,21 +292,13 @@ class _LossEngine(object):
 
     def __init__(self, vgg_params):
         self.lib = N.lib()
-        self.vgg = vgg_params          # _VggLpipsParams or _AlexLpipsParams
+        self.vgg = vgg_params          # an _LpipsParams
         lib = self.lib
         self.prefix = getattr(vgg_params, 'prefix', 'vgg')     # None = L1-only engine
-        if self.prefix == 'alex':
-            self.f_ws, self.f_cache = lib.p2l_alexloss_ws_bytes, lib.p2l_alex_cache_floats
-            self.f_prepare, self.f_fwd, self.f_bwd = (lib.p2l_alexloss_prepare, lib.p2l_alexloss_fwd,
-                                                      lib.p2l_alexloss_bwd)
-        elif self.prefix == 'squeeze':
-            self.f_ws, self.f_cache = lib.p2l_sqzloss_ws_bytes, lib.p2l_sqz_cache_floats
-            self.f_prepare, self.f_fwd, self.f_bwd = (lib.p2l_sqzloss_prepare, lib.p2l_sqzloss_fwd,
-                                                      lib.p2l_sqzloss_bwd)
-        else:
-            self.f_ws, self.f_cache = lib.p2l_projloss_ws_bytes, lib.p2l_loss_cache_floats
-            self.f_prepare, self.f_fwd, self.f_bwd = (lib.p2l_projloss_prepare, lib.p2l_projloss_fwd,
-                                                      lib.p2l_projloss_bwd)
+        stem, cache_floats, self.cache_cls = _LOSS_ABI[self.prefix]
+        self.f_cache = getattr(lib, cache_floats)
+        self.f_ws, self.f_prepare, self.f_fwd, self.f_bwd = (
+            getattr(lib, stem + what) for what in ('_ws_bytes', '_prepare', '_fwd', '_bwd'))
         self.res = None          # (H, W) the caches were made at
         self._lanes = {}         # lane -> _EngineLane: arena + image staging of one stream (lanes.py)
         self.slots = {}          # key -> _CacheSlot (insertion order = LRU order; equal content shares a slot)
@@ -481,7 +456,7 @@ class _LossEngine(object):
                     # still be inside the forward / backward that uses the evicted chunk's slot)
                     slot.wait_for_readers()
             if slot is None:
-                slot = _CacheSlot(self.f_cache, B, H, W, out.device, taps=7 if self.prefix == 'squeeze' else 5)
+                slot = _CacheSlot(self.f_cache, self.cache_cls, B, H, W, out.device)
             vref = C.byref(self.vgg.desc) if use_lpips else None
             N.check(self.f_prepare(vref, N.ptr(target), N.ptr(weight), N.ptr(loss_mask), B, H, W,
                                    C.byref(slot.desc), N.ptr(self.ws), C.c_size_t(self.ws_bytes),
