@@ -10,8 +10,8 @@ instead of 520 per step on the host.
 Results are the same bits as one stream (a candidate's arithmetic does not depend on what runs beside it).
 
 A lane = a stream + its own workspaces in every object that keeps device scratch (the generator's arena
-and image staging, the loss's arena); objects advertise `lanes_ok = True` and look the current lane up
-here.  Lane 0 on the caller's stream is the only one unless closure.step opens more.
+and image staging, the loss's arena); objects advertise `lanes_ok = True` and keep that scratch in a
+`Scratch` (`_scratch`).  Lane 0 on the caller's stream is the only one unless closure.step opens more.
 """
 import os
 import threading
@@ -43,6 +43,77 @@ class use(object):
         _tls.lane = self.prev
 
 
+class LaneScratch(object):
+    """the device scratch of one execution lane: arena, image staging, forward ticket"""
+
+    def __init__(self):
+        self.ws, self.ws_bytes, self.cap = None, 0, -1
+        self.img16 = self.dimg16 = None
+        self.ticket, self.last_B = 0, 0
+
+
+class Scratch(object):
+    """The per-lane device scratch of ONE object (a generator, a loss engine): `lanes` (lane -> LaneScratch)
+    and `generation`.  The rule it keeps: whatever frees or moves a lane's buffers bumps `generation` --
+    captured HIP graphs hold the old pointers, and the graph cache keys on it (base_optimizer._graph_key)."""
+
+    def __init__(self):
+        self.lanes, self.generation = {}, 0
+
+    def here(self):
+        """the record of the current lane"""
+        k = current()
+        s = self.lanes.get(k)
+        if s is None:
+            s = self.lanes[k] = LaneScratch()
+        return s
+
+    def grow(self, B, H, W, sizing, device):
+        """the current lane's record with room for B images of H x W: arena of `sizing(B, H, W)` bytes and the two
+        16-channel staging tensors, re-allocated only when B exceeds what the lane holds (sized for the LARGEST
+        batch seen: a ragged last chunk must not re-allocate GBs twice per step).  A failed sizing or
+        allocation leaves the record as it was."""
+        s = self.here()
+        if B > s.cap:
+            nbytes = sizing(B, H, W)
+            ws = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+            img16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
+            dimg16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
+            s.ws, s.ws_bytes, s.cap, s.img16, s.dimg16 = ws, nbytes, B, img16, dimg16
+            self.generation += 1
+        return s
+
+    def drop_side(self):
+        """free what lanes > 0 hold"""
+        for k in [k for k in self.lanes if k != 0]:
+            del self.lanes[k]
+        self.generation += 1
+
+    def clear(self):
+        """free every lane (the loss engine at a new resolution)"""
+        self.lanes.clear()
+        self.generation += 1
+
+    def stamp(self):
+        """called by a forward that has filled the current lane: -> (lane, ticket) for its backward"""
+        s = self.here()
+        s.ticket += 1
+        return current(), s.ticket
+
+    def stale(self, stamp):
+        """has a later forward (or a drop) taken the scratch of the stamp's lane since?"""
+        s = self.lanes.get(stamp[0])
+        return s is None or s.ticket != stamp[1]
+
+
+def env_int(name, default):
+    """$name as an integer; unset, empty or not a number = default"""
+    try:
+        return int(os.environ.get(name, '') or default)
+    except ValueError:
+        return default
+
+
 _gave_up = []
 
 
@@ -55,12 +126,10 @@ def give_up(reason):
 
 
 def drop_side_scratch(*objs):
-    """free what lanes > 0 allocated in the objects that keep per-lane scratch"""
+    """free what lanes > 0 allocated in the objects that keep per-lane scratch (retires their captured graphs)"""
     for o in objs:
-        held = getattr(o, '_lanes', None)
-        if isinstance(held, dict):
-            for k in [k for k in held if k != 0]:
-                del held[k]
+        if isinstance(getattr(o, '_scratch', None), Scratch):
+            o._scratch.drop_side()
 
 
 def wanted(n_chunks, *objs):
@@ -68,10 +137,7 @@ def wanted(n_chunks, *objs):
     (default 2; 1 = off) when every object has per-lane workspaces.  Also while a HIP graph is being captured:
     the side streams fork from the capturing stream and join it again, the graph gets two branches and the
     replay runs them side by side (measured: 15.3 ms replayed, 15.5 eager, 19.6 replayed on one stream)"""
-    try:
-        want = int(os.environ.get('P2L_STREAMS', '2'))
-    except ValueError:
-        want = 2
+    want = env_int('P2L_STREAMS', 2)
     if n_chunks < 2 or want < 2 or _gave_up or not torch.cuda.is_available():
         return 1
     if not all(getattr(o, 'lanes_ok', False) for o in objs):

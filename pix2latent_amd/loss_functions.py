@@ -261,18 +261,6 @@ class _StreamGuard(object):
             self.seen.add(st.cuda_stream)
 
 
-class _EngineLane(object):
-    def __init__(self):
-        self.ws, self.ws_bytes, self.shape = None, 0, None
-        self.img16 = self.dimg16 = None
-        self.fwd_ticket = 0
-
-
-def _lane_attr(name):
-    return property(lambda self: getattr(self._lane(), name),
-                    lambda self, v: setattr(self._lane(), name, v))
-
-
 # _LpipsParams.prefix -> (stem of *_ws_bytes / _prepare / _fwd / _bwd, its cache_floats, its cache struct)
 _LOSS_ABI = {'vgg': ('p2l_projloss', 'p2l_loss_cache_floats', N.P2LLossCache),
              'alex': ('p2l_alexloss', 'p2l_alex_cache_floats', N.P2LLossCache),
@@ -300,54 +288,36 @@ class _LossEngine(object):
         self.f_ws, self.f_prepare, self.f_fwd, self.f_bwd = (
             getattr(lib, stem + what) for what in ('_ws_bytes', '_prepare', '_fwd', '_bwd'))
         self.res = None          # (H, W) the caches were made at
-        self._lanes = {}         # lane -> _EngineLane: arena + image staging of one stream (lanes.py)
+        self._scratch = lanes.Scratch()      # arena + image staging per lane (one per stream)
         self.slots = {}          # key -> _CacheSlot (insertion order = LRU order; equal content shares a slot)
         self.keep = {}           # key -> the tensors it identifies (kept alive)
         self.cache = None        # P2LLossCache of the slot bound by the last prepare()
         self._memo = {}
-        self.generation = 0
 
     # per-lane scratch (the cached target features are shared: read-only while steps run)
     lanes_ok = True
+    _lanes = property(lambda self: self._scratch.lanes)
+    # what the current lane holds, for readers outside (oracle/replay.py, tools/): the engine fetches the record once
+    ws = property(lambda self: self._scratch.here().ws)
+    ws_bytes = property(lambda self: self._scratch.here().ws_bytes)
+    img16 = property(lambda self: self._scratch.here().img16)
+    dimg16 = property(lambda self: self._scratch.here().dimg16)
+    shape = property(lambda self: None if self.img16 is None else tuple(self.img16.shape[:3]))
 
-    def _lane(self):
-        k = lanes.current()
-        st = self._lanes.get(k)
-        if st is None:
-            st = self._lanes[k] = _EngineLane()
-        return st
-
-    ws, ws_bytes, shape = _lane_attr('ws'), _lane_attr('ws_bytes'), _lane_attr('shape')
-    _img16, _dimg16, _fwd_ticket = _lane_attr('img16'), _lane_attr('dimg16'), _lane_attr('fwd_ticket')
-
-    def _alloc(self, B, H, W, dev):
-        """workspace + image staging sized for the LARGEST chunk seen at this resolution: a
-        ragged last chunk (32 samples = 9,9,9,5) alternates B every step, and re-allocating
-        would also drop the cached target features of every chunk"""
-        if self.res != (H, W):
-            # resolution changed: caches are void, and so is every lane's scratch
-            self.slots, self.keep, self._lanes, self.res = {}, {}, {}, (H, W)
-        if self.shape is not None and B <= self.shape[0]:
-            return
-        if self.shape is not None:
-            B = max(B, self.shape[0])
+    def _ws_bytes(self, B, H, W):
         nbytes = self.f_ws(B, H, W)
         if nbytes == 0:
             raise N.NativeError('loss workspace sizing rejected shape %s' % ((B, H, W),))
-        self.ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-        self.ws_bytes = nbytes
-        self._img16 = torch.empty(B, H, W, 16, device=dev, dtype=torch.float32)
-        self._dimg16 = torch.empty(B, H, W, 16, device=dev, dtype=torch.float32)
-        self.shape = (B, H, W)
-        self.generation += 1                         # captured HIP graphs hold the old pointers
+        return nbytes
 
-    @property
-    def img16(self):
-        return self._img16
-
-    @property
-    def dimg16(self):
-        return self._dimg16
+    def _alloc(self, B, H, W, dev):
+        """the lane's workspace + image staging, sized for the LARGEST chunk seen at this resolution (a ragged
+        last chunk, 32 samples = 9,9,9,5, alternates B every step)"""
+        if self.res != (H, W):
+            # resolution changed: caches are void, and so is every lane's scratch
+            self.slots, self.keep, self.res = {}, {}, (H, W)
+            self._scratch.clear()
+        return self._scratch.grow(B, H, W, self._ws_bytes, dev)
 
     @staticmethod
     def _ident(t):
@@ -439,7 +409,7 @@ class _LossEngine(object):
 
     def prepare(self, out, target, weight, loss_mask, use_lpips):
         B, _, H, W = out.shape
-        self._alloc(B, H, W, out.device)
+        s = self._alloc(B, H, W, out.device)
         key = (self._ident(target), self._ident(weight), self._ident(loss_mask), use_lpips)
         slot = self.slots.pop(key, None)
         if slot is None:
@@ -459,7 +429,7 @@ class _LossEngine(object):
                 slot = _CacheSlot(self.f_cache, self.cache_cls, B, H, W, out.device)
             vref = C.byref(self.vgg.desc) if use_lpips else None
             N.check(self.f_prepare(vref, N.ptr(target), N.ptr(weight), N.ptr(loss_mask), B, H, W,
-                                   C.byref(slot.desc), N.ptr(self.ws), C.c_size_t(self.ws_bytes),
+                                   C.byref(slot.desc), N.ptr(s.ws), C.c_size_t(s.ws_bytes),
                                    N.stream()), 'p2l_%sloss_prepare' % self.prefix)
             # what the slot was prepared FROM (content comparisons), with the versions of that moment
             slot.held = (target, weight, loss_mask)
@@ -511,16 +481,17 @@ class _ProjLossFn(torch.autograd.Function):
         use_lpips = 0 if mode == 1 else 1
         slot = eng.prepare(out_c, target, weight, loss_mask, use_lpips)
         ctx.slot = slot
-        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(eng.img16), B, H, W, N.stream()),
+        s = eng._scratch.here()
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, N.stream()),
                 'p2l_nchw3_to_nhwc16')
         loss = torch.empty(B, device=output.device, dtype=torch.float32)
         l1 = torch.empty_like(loss)
         lp = torch.empty_like(loss)
         vref = C.byref(eng.vgg.desc) if use_lpips else None
-        N.check(eng.f_fwd(vref, N.ptr(eng.img16), N.ptr(target), N.ptr(weight),
+        N.check(eng.f_fwd(vref, N.ptr(s.img16), N.ptr(target), N.ptr(weight),
                           N.ptr(loss_mask), C.byref(slot.desc), N.f32(beta),
-                          use_lpips, B, H, W, N.ptr(eng.ws),
-                          C.c_size_t(eng.ws_bytes), N.ptr(loss), N.ptr(l1),
+                          use_lpips, B, H, W, N.ptr(s.ws),
+                          C.c_size_t(s.ws_bytes), N.ptr(loss), N.ptr(l1),
                           N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
         if len(eng._lanes) > 1:          # (one stream: program order already protects an evicted slot)
             slot.used()
@@ -528,9 +499,7 @@ class _ProjLossFn(torch.autograd.Function):
         ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None
                               else torch.empty(0))
         ctx.has_mask = loss_mask is not None
-        eng._fwd_ticket += 1
-        ctx.ticket = eng._fwd_ticket
-        ctx.lane = lanes.current()
+        ctx.stamp = eng._scratch.stamp()
         eng.last_l1, eng.last_lpips = l1, lp
         if mode == 2:
             return lp
@@ -538,7 +507,7 @@ class _ProjLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        with lanes.use(ctx.lane):        # (autograd's thread: the scratch of the forward's lane)
+        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
             return _ProjLossFn._backward(ctx, gloss)
 
     @staticmethod
@@ -550,22 +519,23 @@ class _ProjLossFn(torch.autograd.Function):
             loss_mask = None
         B, _, H, W = out_c.shape
         use_lpips = 0 if ctx.mode == 1 else 1
-        if eng._fwd_ticket != ctx.ticket:
+        if eng._scratch.stale(ctx.stamp):
             raise N.NativeError('loss workspace was reused by a later forward before '
                                 'backward(); use one loss object per in-flight graph')
+        s = eng._scratch.here()
         g = gloss.contiguous().float()
         if ctx.mode == 2:
             use_lpips = 2          # the LPIPS term alone (L1 accumulation switched off)
         N.check(eng.f_bwd(C.byref(eng.vgg.desc) if use_lpips else None,
-                          N.ptr(eng.img16), N.ptr(target), N.ptr(weight),
+                          N.ptr(s.img16), N.ptr(target), N.ptr(weight),
                           N.ptr(loss_mask), C.byref(ctx.slot.desc), N.f32(ctx.beta),
-                          use_lpips, N.ptr(g), B, H, W, N.ptr(eng.ws),
-                          C.c_size_t(eng.ws_bytes), N.ptr(eng.dimg16), N.stream()),
+                          use_lpips, N.ptr(g), B, H, W, N.ptr(s.ws),
+                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()),
                 'p2l_%sloss_bwd' % eng.prefix)
         if len(eng._lanes) > 1:
             ctx.slot.used()
         dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
-        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(eng.dimg16), N.ptr(dout), B, H, W, N.stream()),
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dimg16), N.ptr(dout), B, H, W, N.stream()),
                 'p2l_nhwc16_to_nchw3')
         return dout, None, None, None, None, None, None
 

@@ -57,9 +57,7 @@ class _BigGANFn(torch.autograd.Function):
         z = z.contiguous().float()
         c = c.contiguous().float()
         out = model._run_forward(z, c)
-        ctx.model = model
-        ctx.lane = lanes.current()
-        ctx.ticket = model._ticket
+        ctx.model, ctx.stamp = model, model._scratch.stamp()
         ctx.save_for_backward(z, c)
         return out
 
@@ -67,27 +65,13 @@ class _BigGANFn(torch.autograd.Function):
     def backward(ctx, dout):
         model = ctx.model
         z, c = ctx.saved_tensors
-        with lanes.use(ctx.lane):        # (the saved activations live in the forward's lane)
-            if model._ticket != ctx.ticket:
+        with lanes.use(ctx.stamp[0]):    # (the saved activations live in the forward's lane)
+            if model._scratch.stale(ctx.stamp):
                 # another forward reused the workspace: rebuild the saved activations
                 model._run_forward(z, c)
-                ctx.ticket = model._ticket
+                ctx.stamp = model._scratch.stamp()
             dz, dc = model._run_backward(z.shape[0], dout)
         return dz, dc, None
-
-
-class _Lane(object):
-    """the device scratch of one execution lane (lanes.py): arena, image staging, forward ticket"""
-
-    def __init__(self):
-        self.ws, self.ws_bytes, self.ws_B = None, 0, -1
-        self.img16 = self.dimg16 = None
-        self.ticket, self.last_B = 0, 0
-
-
-def _lane_attr(name):
-    return property(lambda self: getattr(self._lane_state(), name),
-                    lambda self, v: setattr(self._lane_state(), name, v))
 
 
 class BigGAN(nn.Module):
@@ -144,8 +128,7 @@ class BigGAN(nn.Module):
                            (N.WFMT_FLAG_THIN if self._thin else 0) |
                            (N.WFMT_FLAG_ATTN_GEMM if N.default_attn_gemm() else 0) |
                            (N.WFMT_FLAG_NO_AMAX if N.default_no_amax() else 0))
-        self._lanes = {}         # lane -> _Lane (lanes.py: one per stream that runs chunks of a step)
-        self.ws_generation = 0
+        self._scratch = lanes.Scratch()      # arena + image staging per lane (one per stream that runs chunks of a step)
         self._pack(weights)
         self._set_truncation(1.0)
 
@@ -259,65 +242,52 @@ class BigGAN(nn.Module):
 
     # -------------------------------------------------------------- execution
     lanes_ok = True              # per-lane workspaces: chunks of one step may run on several streams
-    _ws, _ws_bytes, _ws_B = _lane_attr('ws'), _lane_attr('ws_bytes'), _lane_attr('ws_B')
-    _img16, _dimg16 = _lane_attr('img16'), _lane_attr('dimg16')
-    _ticket, _last_B = _lane_attr('ticket'), _lane_attr('last_B')
+    _lanes = property(lambda self: self._scratch.lanes)
 
-    def _lane_state(self):
-        k = lanes.current()
-        st = self._lanes.get(k)
-        if st is None:
-            st = self._lanes[k] = _Lane()
-        return st
+    def _ws_bytes(self, B, H, W):
+        nbytes = self._lib.p2l_biggan_ws_bytes(C.byref(self._desc), B)
+        if nbytes == 0:
+            raise N.NativeError('p2l_biggan_ws_bytes rejected batch %d' % B)
+        return nbytes
 
     def _workspace(self, B):
-        # sized for the largest batch seen: a ragged last chunk must not re-allocate GBs
-        # twice per step (the plan lays the arena out from the B of each call)
-        if B > self._ws_B:
-            nbytes = self._lib.p2l_biggan_ws_bytes(C.byref(self._desc), B)
-            if nbytes == 0:
-                raise N.NativeError('p2l_biggan_ws_bytes rejected batch %d' % B)
-            self._ws = torch.empty(nbytes // 4, device=self._dev, dtype=torch.float32)
-            self._ws_bytes = nbytes
-            self._ws_B = B
-            self.ws_generation += 1          # captured HIP graphs hold the old pointers
-            self._img16 = torch.empty(B, 256, 256, 16, device=self._dev, dtype=torch.float32)
-            self._dimg16 = torch.empty(B, 256, 256, 16, device=self._dev, dtype=torch.float32)
-        return self._ws
+        # (the plan lays the arena out from the B of each call)
+        return self._scratch.grow(B, 256, 256, self._ws_bytes, self._dev)
 
     def _run_forward(self, z, c):
         B = z.shape[0]
-        ws = self._workspace(B)
-        self._last_B = B
-        self._ticket += 1
+        s = self._workspace(B)
+        s.last_B = B
         N.check(self._lib.p2l_biggan_fwd(C.byref(self._desc), N.ptr(z), N.ptr(c), B,
-                                         N.ptr(ws), C.c_size_t(self._ws_bytes),
-                                         N.ptr(self._img16), N.stream()), 'p2l_biggan_fwd')
+                                         N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                                         N.ptr(s.img16), N.stream()), 'p2l_biggan_fwd')
         out = torch.empty(B, 3, 256, 256, device=self._dev, dtype=torch.float32)
-        N.check(self._lib.p2l_nhwc16_to_nchw3(N.ptr(self._img16), N.ptr(out), B, 256, 256,
+        N.check(self._lib.p2l_nhwc16_to_nchw3(N.ptr(s.img16), N.ptr(out), B, 256, 256,
                                               N.stream()), 'p2l_nhwc16_to_nchw3')
         return out
 
     def _run_backward(self, B, dout):
+        s = self._scratch.here()
         dout = dout.contiguous().float()
-        N.check(self._lib.p2l_nchw3_to_nhwc16(N.ptr(dout), N.ptr(self._dimg16), B, 256, 256,
+        N.check(self._lib.p2l_nchw3_to_nhwc16(N.ptr(dout), N.ptr(s.dimg16), B, 256, 256,
                                               N.stream()), 'p2l_nchw3_to_nhwc16')
         dz = torch.empty(B, self.z_dim, device=self._dev, dtype=torch.float32)
         dc = torch.empty(B, self.z_dim, device=self._dev, dtype=torch.float32)
-        N.check(self._lib.p2l_biggan_bwd(C.byref(self._desc), B, N.ptr(self._ws),
-                                         C.c_size_t(self._ws_bytes), N.ptr(self._img16),
-                                         N.ptr(self._dimg16), N.ptr(dz), N.ptr(dc),
+        N.check(self._lib.p2l_biggan_bwd(C.byref(self._desc), B, N.ptr(s.ws),
+                                         C.c_size_t(s.ws_bytes), N.ptr(s.img16),
+                                         N.ptr(s.dimg16), N.ptr(dz), N.ptr(dc),
                                          N.stream()), 'p2l_biggan_bwd')
         return dz, dc
 
     def saved_activation(self, what, layer=0):
         """test hook: view of a saved NHWC activation inside the workspace."""
+        s = self._scratch.here()
         off = C.c_size_t(0)
         shape = (C.c_int32 * 4)()
-        N.check(self._lib.p2l_biggan_ws_lookup(C.byref(self._desc), self._last_B, what, layer,
+        N.check(self._lib.p2l_biggan_ws_lookup(C.byref(self._desc), s.last_B, what, layer,
                                                C.byref(off), shape), 'p2l_biggan_ws_lookup')
         n = shape[0] * shape[1] * shape[2] * shape[3]
-        return self._ws[off.value:off.value + n].view(*list(shape))
+        return s.ws[off.value:off.value + n].view(*list(shape))
 
     # ------------------------------------------------------------- public API
     def get_class_embedding(self, cls):

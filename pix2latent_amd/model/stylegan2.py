@@ -30,20 +30,6 @@ IM_DIM = {'cars': 512, 'ffhq': 1024}
 LR_MLP = 0.01
 
 
-class _Lane(object):
-    """the device scratch of one execution lane (lanes.py)"""
-
-    def __init__(self):
-        self.ws, self.ws_bytes, self.ws_B = None, 0, -1
-        self.img16 = self.dimg16 = None
-        self.ticket = 0
-
-
-def _lane_attr(name):
-    return property(lambda self: getattr(self._lane_state(), name),
-                    lambda self, v: setattr(self._lane_state(), name, v))
-
-
 class _SynthFn(torch.autograd.Function):
     """latent [B, n_latent, 512] (+ layer-major noise) -> image [B,3,S,S]"""
 
@@ -52,40 +38,39 @@ class _SynthFn(torch.autograd.Function):
         B = latent.shape[0]
         latent = latent.contiguous().float()
         noise_lm = noise_lm.contiguous().float()
-        model._ensure_ws(B)
         lib, S = model._lib, model.im_res
-        model._ticket += 1
+        s = model._ensure_ws(B)
         N.check(lib.p2l_sg2_synthesis_fwd(C.byref(model._desc), N.ptr(latent), N.ptr(noise_lm), B,
-                                          N.ptr(model._ws), C.c_size_t(model._ws_bytes),
-                                          N.ptr(model._img16), N.stream()), 'p2l_sg2_synthesis_fwd')
+                                          N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                                          N.ptr(s.img16), N.stream()), 'p2l_sg2_synthesis_fwd')
         out = torch.empty(B, 3, S, S, device=latent.device, dtype=torch.float32)
-        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(model._img16), N.ptr(out), B, S, S, N.stream()),
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.img16), N.ptr(out), B, S, S, N.stream()),
                 'p2l_nhwc16_to_nchw3')
-        ctx.model, ctx.ticket, ctx.want_dnoise = model, model._ticket, want_dnoise
-        ctx.lane = lanes.current()
+        ctx.model, ctx.stamp, ctx.want_dnoise = model, model._scratch.stamp(), want_dnoise
         ctx.save_for_backward(latent, noise_lm)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        with lanes.use(ctx.lane):        # (the saved activations live in the forward's lane)
+        with lanes.use(ctx.stamp[0]):    # (the saved activations live in the forward's lane)
             return _SynthFn._backward(ctx, dout)
 
     @staticmethod
     def _backward(ctx, dout):
         model = ctx.model
         latent, noise_lm = ctx.saved_tensors
-        if model._ticket != ctx.ticket:
+        if model._scratch.stale(ctx.stamp):
             raise N.NativeError('StyleGAN2 workspace was reused by a later forward before '
                                 'backward(); use one model object per in-flight graph')
+        s = model._scratch.here()
         B, S, lib = latent.shape[0], model.im_res, model._lib
-        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(dout.contiguous().float()), N.ptr(model._dimg16), B, S,
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(dout.contiguous().float()), N.ptr(s.dimg16), B, S,
                                         S, N.stream()), 'p2l_nchw3_to_nhwc16')
         dlatent = torch.empty_like(latent)
         dnoise = torch.empty_like(noise_lm) if ctx.want_dnoise else None
         N.check(lib.p2l_sg2_synthesis_bwd(C.byref(model._desc), N.ptr(latent), N.ptr(noise_lm), B,
-                                          N.ptr(model._ws), C.c_size_t(model._ws_bytes),
-                                          N.ptr(model._dimg16), N.ptr(dlatent), N.ptr(dnoise),
+                                          N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                                          N.ptr(s.dimg16), N.ptr(dlatent), N.ptr(dnoise),
                                           N.stream()), 'p2l_sg2_synthesis_bwd')
         return dlatent, dnoise, None, None
 
@@ -165,8 +150,7 @@ class StyleGAN2(nn.Module):
         self._wfmt = N.default_wfmt() if wfmt is None else wfmt
         # (P2L_AMAX=0: every fp16 x 2 launch reduces the maxima of its input itself -- model descriptor flag)
         self._desc.wfmt = self._wfmt | (N.WFMT_FLAG_NO_AMAX if N.default_no_amax() else 0)
-        self._lanes = {}         # lane -> _Lane: arena + image staging of one stream (lanes.py)
-        self.ws_generation = 0
+        self._scratch = lanes.Scratch()      # arena + image staging per lane (one per stream)
         self._pack(weights)
         self.search = search
         with torch.no_grad():
@@ -250,29 +234,17 @@ class StyleGAN2(nn.Module):
         self._noise_sizes = [s[-1] * s[-2] for s in self.noise_shape]
 
     lanes_ok = True              # per-lane workspaces: chunks of one step may run on several streams
-    _ws, _ws_bytes, _ws_B = _lane_attr('ws'), _lane_attr('ws_bytes'), _lane_attr('ws_B')
-    _img16, _dimg16, _ticket = _lane_attr('img16'), _lane_attr('dimg16'), _lane_attr('ticket')
+    _lanes = property(lambda self: self._scratch.lanes)
 
-    def _lane_state(self):
-        k = lanes.current()
-        st = self._lanes.get(k)
-        if st is None:
-            st = self._lanes[k] = _Lane()
-        return st
+    def _ws_bytes(self, B, H, W):
+        nbytes = self._lib.p2l_sg2_ws_bytes(C.byref(self._desc), B)
+        if nbytes == 0:
+            raise N.NativeError('p2l_sg2_ws_bytes rejected batch %d' % B)
+        return nbytes
 
     def _ensure_ws(self, B):
-        # sized for the largest batch seen (32 samples = chunks of 9,9,9,5 alternate B)
-        if B > self._ws_B:
-            nbytes = self._lib.p2l_sg2_ws_bytes(C.byref(self._desc), B)
-            if nbytes == 0:
-                raise N.NativeError('p2l_sg2_ws_bytes rejected batch %d' % B)
-            self._ws = torch.empty(nbytes // 4, device=self._dev, dtype=torch.float32)
-            self._ws_bytes = nbytes
-            S = self.im_res
-            self._img16 = torch.empty(B, S, S, 16, device=self._dev, dtype=torch.float32)
-            self._dimg16 = torch.empty(B, S, S, 16, device=self._dev, dtype=torch.float32)
-            self._ws_B = B
-            self.ws_generation += 1          # captured HIP graphs hold the old pointers
+        # (32 samples = chunks of 9,9,9,5 alternate B)
+        return self._scratch.grow(B, self.im_res, self.im_res, self._ws_bytes, self._dev)
 
     def saved_activation(self, layer, B):
         """test hook: view of the post-activation output of styled conv `layer` inside the workspace
@@ -282,7 +254,7 @@ class StyleGAN2(nn.Module):
         N.check(self._lib.p2l_sg2_ws_lookup(C.byref(self._desc), B, layer, C.byref(off), shape),
                 'p2l_sg2_ws_lookup')
         n = shape[0] * shape[1] * shape[2] * shape[3]
-        return self._ws[off.value:off.value + n].view(*list(shape))
+        return self._scratch.here().ws[off.value:off.value + n].view(*list(shape))
 
     # -------------------------------------------------------------- pieces
     def mapping(self, z):

@@ -320,26 +320,31 @@ class _BaseOptimizer(SearchLoopMixin):
         # larger than the reference chunk (exec_batch_size: one stream by request)
         return local_n <= self.max_batch_size and lanes.sub_wanted(local_n, *objs)
 
+    def _graph_key(self, variables, lo, hi):
+        """identity of everything the captured launches point at: the variable buffers, and for
+        the output variables (targets, weights) also their version - the loss keeps target
+        features cached per version, a transform that rewrites the targets must re-capture
+        ... and WHICH optimizer / workspaces they belong to: the caching allocator hands the
+        addresses of freed buffers out again (vm.initialize() in a loop gives new variables
+        and a new Adam state at the old addresses), and a model or loss that frees or re-allocates
+        a lane's workspace (lanes.Scratch.generation) leaves the old pointers baked into the
+        captured launches"""
+        owners = (self.model, getattr(self.loss_fn, '_engine', None))
+        return (variables.num_samples, lo, hi, self.max_batch_size, self.exec_batch_size,
+                variables.opt.state_key()) + tuple(
+            getattr(getattr(o, '_scratch', None), 'generation', 0) for o in owners) + tuple(
+            (name, v.buf.data_ptr()) for name, v in sorted(variables.input.items())
+            if v.get('buf', None) is not None) + tuple(
+            (name, v.buf.data_ptr(), v.buf._version) for name, v in sorted(variables.output.items())
+            if v.get('buf', None) is not None)
+
     def _graphed_step(self, variables, optimize, transform, lo, hi):
         """optimize steps without a transform, on variables whose device buffers were seen
         before: replay the captured graph (capturing it on the second sighting).  Returns
         None when the step has to run eagerly."""
         if not optimize or transform or hi == lo or not self._graph_wanted(variables, hi - lo):
             return None
-        # identity of everything the captured launches point at: the variable buffers, and for
-        # the output variables (targets, weights) also their version - the loss keeps target
-        # features cached per version, a transform that rewrites the targets must re-capture
-        # ... and WHICH optimizer / workspaces they belong to: the caching allocator hands the
-        # addresses of freed buffers out again (vm.initialize() in a loop gives new variables
-        # and a new Adam state at the old addresses), and a model or loss that re-allocates its
-        # workspace for a larger batch leaves the old pointers baked into the captured launches
-        key = (variables.num_samples, lo, hi, self.max_batch_size, self.exec_batch_size,
-               variables.opt.state_key(), getattr(self.model, 'ws_generation', 0),
-               getattr(getattr(self.loss_fn, '_engine', None), 'generation', 0)) + tuple(
-            (name, v.buf.data_ptr()) for name, v in sorted(variables.input.items())
-            if v.get('buf', None) is not None) + tuple(
-            (name, v.buf.data_ptr(), v.buf._version) for name, v in sorted(variables.output.items())
-            if v.get('buf', None) is not None)
+        key = self._graph_key(variables, lo, hi)
         entry = self._graphs.get(key)
         if entry is None:                 # first sighting: run eagerly (this is the warm-up)
             self._graphs = {key: 'warm'}  # (a new set of buffers retires the old graphs)

@@ -21,8 +21,6 @@ Two execution paths:
     -- stack the per-sample leaves, `opt.step(closure)` -- used by the golden
     trace tests and for user-supplied optimizers.
 """
-import os
-
 import numpy as np
 import torch
 
@@ -130,7 +128,7 @@ def _step_fused(model, vars, loss_fn, optimize, max_batch_size, grad_scale, popu
         if grad_scale is None:
             grad_scale = _const_scale(n, next(iter(vars.input.values())).data[0].device)
         chunks, offsets = [slice_vars(vars, 0, h), slice_vars(vars, h, n)], [0, h]
-    split = int(os.environ.get('P2L_LANE_SPLIT', '1') or 1)
+    split = lanes.env_int('P2L_LANE_SPLIT', 1)
     if split > 1 and len(chunks) >= 2 and not one_pass:
         # (measurement, tools/ab_lanes.sh) every reference chunk in `split` parts on as many lanes as P2L_STREAMS
         # allows, each part with the gradient factor of its chunk
@@ -192,17 +190,22 @@ def _step_fused(model, vars, loss_fn, optimize, max_batch_size, grad_scale, popu
                 losses[-1].record_stream(main)
 
     for ci, _vars in enumerate(chunks):
+        failed = None
         try:
             run_chunk(ci, _vars, n_lanes)
         except torch.cuda.OutOfMemoryError as e:
             if n_lanes == 1 or ci % n_lanes == 0:
                 raise
+            failed = '%s in lane %d of %d' % (str(e).split('.')[0], ci % n_lanes, n_lanes)
+        if failed:
             # The second lane's set of workspaces (generator arena + image staging + loss arena: 5 GB for
             # BigGAN-256 at 9 candidates, 17 GB per lane for StyleGAN2-1024) did not fit beside the first.
             # Nothing of THIS chunk has been updated yet (its Adam update follows its backward), the chunks
             # before it are complete: give the side lanes' memory back, and run this chunk and every later
-            # one on lane 0, behind whatever the side streams still hold.
-            lanes.give_up('%s in lane %d of %d' % (str(e).split('.')[0], ci % n_lanes, n_lanes))
+            # one on lane 0, behind whatever the side streams still hold.  Out here, behind the
+            # `except` block, the traceback and with it the failed chunk's tensors are gone before the cache
+            # is emptied; dropping bumps the owners' generation, which retires graphs captured on two lanes.
+            lanes.give_up(failed)
             for s_ in streams:
                 main.wait_stream(s_)
             torch.cuda.current_stream().synchronize()

@@ -35,8 +35,8 @@ def _problem(dev, n):
     return opt, vm.initialize(num_samples=n), model, loss_fn
 
 
-def _run(dev, n, steps=2):
-    opt, variables, model, loss_fn = _problem(dev, n)
+def _run(dev, n, steps=2, problem=None):
+    opt, variables, model, loss_fn = problem or _problem(dev, n)
     losses = []
     for i in range(steps):
         opt.step(variables, optimize=True, transform=(i == 0))
@@ -123,15 +123,20 @@ def test_second_lane_out_of_memory_falls_back_to_one_lane(monkeypatch):
 
     def failing_workspace(self, B):
         if lanes.current() == 1 and not fired:
-            fired.append(1)
+            fired.append(tuple(o.generation for o in owners))
             raise torch.cuda.OutOfMemoryError('HIP out of memory (injected). Tried to allocate 3.4 GiB')
         return real_ws(self, B)
     monkeypatch.setattr(BG.BigGAN, '_workspace', failing_workspace)
-    model, eng, l2, z2 = _run(dev, 7)
+    problem = _problem(dev, 7)
+    owners = problem[2]._scratch, problem[3]._engine._scratch
+    model, eng, l2, z2 = _run(dev, 7, problem=problem)
     assert fired and lanes._gave_up and 'out of memory' in lanes._gave_up[0]
     assert lanes.wanted(2, model, eng) == 1
     assert sorted(model._lanes) == [0] and sorted(eng._lanes) == [0]
     assert torch.equal(l1, l2) and torch.equal(z1, z2)
+    # freeing lane 1's arenas retires the graphs captured on two lanes: both owners moved on from where they
+    # stood when the allocation failed (lane 0 allocated nothing after that: its chunk had run before)
+    assert owners[0].generation > fired[0][0] and owners[1].generation > fired[0][1]
 
 
 def test_replayed_step_hands_out_independent_tensors(monkeypatch):
@@ -154,3 +159,53 @@ def test_replayed_step_hands_out_independent_tensors(monkeypatch):
         assert torch.equal(out, out_then)
         assert torch.equal(torch.as_tensor([float(x) for x in loss]), loss_then)
     assert not torch.equal(kept[-1][0], kept[-2][0])
+
+
+def test_dropped_side_scratch_retires_the_captured_graph(monkeypatch):
+    """A two-lane step captured as a HIP graph points into lane 1's arenas.  Dropping the side scratch, as the
+    out-of-memory fall-back of closure._step_fused does, bumps the owners' generation, so the next step finds no
+    graph under its key: it runs eagerly (lane 1 allocates again), and a new graph is captured over the new
+    arenas.  The bits are those of six eager steps on one stream."""
+    if not torch.cuda.is_available():
+        pytest.skip('needs a GPU')
+    from pix2latent_amd import lanes
+    dev = torch.device('cuda:0')
+
+    def captured(opt):
+        return [k for k, v in opt._graphs.items() if isinstance(v, tuple)]
+
+    def steps(opt, variables, first, n, losses):
+        for i in range(first, first + n):
+            opt.step(variables, optimize=True, transform=(i == 0))
+            losses.append(torch.as_tensor([float(x) for x in opt.loss]))
+
+    monkeypatch.setenv('P2L_STREAMS', '1')
+    opt1, variables1, _, _ = _problem(dev, 6)
+    opt1.use_graph = False
+    l1 = []
+    steps(opt1, variables1, 0, 6, l1)
+    torch.cuda.synchronize()
+    assert not opt1._graphs
+
+    monkeypatch.setenv('P2L_STREAMS', '2')
+    opt, variables, model, loss_fn = _problem(dev, 6)
+    eng = loss_fn._engine
+    opt.use_graph = True
+    l2 = []
+    steps(opt, variables, 0, 3, l2)
+    old = captured(opt)
+    assert len(old) == 1 and sorted(model._lanes) == [0, 1] and sorted(eng._lanes) == [0, 1]
+    torch.cuda.synchronize()
+    lanes.drop_side_scratch(model, eng)                   # (no empty_cache: the old arenas stay mapped)
+    assert sorted(model._lanes) == [0] and sorted(eng._lanes) == [0]
+    key = opt._graph_key(variables, 0, 6)
+    assert key != old[0] and opt._graphs.get(key) in (None, 'warm')
+    steps(opt, variables, 3, 1, l2)
+    assert not captured(opt), 'the first step after the drop replayed a graph'
+    assert sorted(model._lanes) == [0, 1] and sorted(eng._lanes) == [0, 1]
+    steps(opt, variables, 4, 2, l2)
+    assert len(captured(opt)) == 1 and captured(opt)[0] != old[0]
+    torch.cuda.synchronize()
+    assert torch.equal(torch.stack(l1), torch.stack(l2)), 'losses differ from six eager steps on one stream'
+    assert torch.equal(variables1.input.z.buf, variables.input.z.buf)
+    assert torch.equal(variables1.input.c.buf, variables.input.c.buf)

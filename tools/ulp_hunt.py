@@ -24,7 +24,7 @@ lib = N.lib()
 
 
 def gen_regions():
-    B = model._last_B
+    B = model._scratch.here().last_B
     regs = []
 
     def look(what, L, name):
@@ -65,8 +65,9 @@ _fwd0, _lfwd0 = model._run_forward, eng.f_fwd
 def _fwd(z, c):
     out = _fwd0(z, c)
     torch.cuda.synchronize()
-    cur['gen'].append(model._ws.view(torch.int32).clone())
-    cur['img'].append(model._img16.view(torch.int32).clone())
+    s = model._scratch.here()
+    cur['gen'].append(s.ws.view(torch.int32).clone())
+    cur['img'].append(s.img16.view(torch.int32).clone())
     return out
 
 
@@ -120,7 +121,7 @@ for i in range(reps):
         first = s
         gr, lr = gen_regions(), loss_regions()
         print('chunks per re-score: %d of %d candidates; generator arena %.2f GB, %d named regions; loss arena %.2f GB' %
-              (len(s['gen']), model._last_B, s['gen'][0].numel() * 4e-9, len(gr), s['loss'][0].numel() * 4e-9))
+              (len(s['gen']), model._scratch.here().last_B, s['gen'][0].numel() * 4e-9, len(gr), s['loss'][0].numel() * 4e-9))
         continue
     rep = []
     for ch in range(len(s['gen'])):
