@@ -1023,6 +1023,32 @@ int p2l_sg2_mapping_fwd(const P2LStyleGAN2* m, const float* z, float* w, float* 
 int p2l_sg2_mapping_bwd(const P2LStyleGAN2* m, const float* z, const float* acts, const float* dw,
                         float* dz, float* scratch /* 2*B*512 */, int Bn, void* stream);
 
+/* Noise regulariser and per-layer noise normalisation of the StyleGAN2 projector, on the flat noise variable
+ * (csrc/p2l_noise_reg.hip).  noises [Bn][T] fp32, T = sum res_l^2; layer l is the res_l x res_l
+ * row-major map at offset sum_{j<l} res_j^2.  res: HOST array of n_layers (1 .. 32) powers of two in 4 .. 1024;
+ * the entry points do not need a P2LStyleGAN2.  Level 0 of a layer is the map; while its side s_k > 8, level k+1 has
+ * side s_k / 2 and n'[y,x] = ((n[2y,2x] + n[2y,2x+1]) + (n[2y+1,2x] + n[2y+1,2x+1])) * 0.25f in fp32.  Per candidate
+ * and level, indices wrapping: ax = mean n[y,x] n[y,x-1], ay = mean n[y,x] n[y-1,x]; loss[b] = sum over layers and
+ * levels of ax^2 + ay^2, rounded once to fp32.  corr (fp64 [Bn][levels][2] = ax, ay; levels layer-major, finest first;
+ * NULL = not wanted).  Products are exact fp64, all sums fp64 in an order that follows from res alone: a candidate's
+ * results do not depend on Bn, on its row, or on the call.  No atomics, no memset.
+ * _bwd: dnoises[b] = gloss[b] (NULL = 1) * dR_b/dnoises, closed form evaluated in fp64 per pixel and rounded once;
+ * it reads noises and the workspace AS THE FORWARD LEFT IT (pooled levels, ax / ay), nothing else.
+ * _normalize: every layer of every candidate n <- (n - mean) / std in place, unbiased std, two-pass fp64, rounded
+ * once; a constant map yields the non-finite values of the same torch expression.  Its workspace has the same size
+ * and it overwrites what a forward left there.
+ * Launches: forward 3, backward 1, normalise 3, whatever Bn and n_layers are.  noises, dnoises and ws 16-byte
+ * aligned.  P2L_EINVAL (NULL noises / loss / dnoises / res, Bn < 1 or > 65535, a bad res entry or count,
+ * misalignment) and P2L_EWS (NULL, misaligned or short workspace) are returned before any launch;
+ * p2l_sg2_noise_reg_ws_bytes is host-only and 0 for what it refuses. */
+size_t p2l_sg2_noise_reg_ws_bytes(const int32_t* res, int n_layers, int Bn);
+int p2l_sg2_noise_reg_fwd(const float* noises, const int32_t* res, int n_layers, int Bn, float* loss, double* corr,
+                          void* ws, size_t ws_bytes, void* stream);
+int p2l_sg2_noise_reg_bwd(const float* noises, const int32_t* res, int n_layers, int Bn, const float* gloss,
+                          float* dnoises, const void* ws, size_t ws_bytes, void* stream);
+int p2l_sg2_noise_normalize(float* noises, const int32_t* res, int n_layers, int Bn, void* ws, size_t ws_bytes,
+                            void* stream);
+
 
 #ifdef __cplusplus
 }

@@ -311,6 +311,7 @@ EXPORTS = [
     'p2l_color_adjust_ws_bytes', 'p2l_color_adjust',
     'p2l_gram_f64_ws_bytes', 'p2l_gram_f64', 'p2l_gram_f64_wide_ws_bytes', 'p2l_gram_f64_wide',
     'p2l_poisson_blend_ws_bytes', 'p2l_poisson_blend',
+    'p2l_sg2_noise_reg_ws_bytes', 'p2l_sg2_noise_reg_fwd', 'p2l_sg2_noise_reg_bwd', 'p2l_sg2_noise_normalize',
 ]
 
 _lib = None
@@ -346,7 +347,8 @@ def lib():
                      'p2l_alexloss_ws_bytes', 'p2l_alex_cache_floats', 'p2l_sqzloss_ws_bytes', 'p2l_sqz_cache_floats', 'p2l_gemm_ws_bytes',
                      'p2l_packed_weight_floats', 'p2l_packed_subpix_weight_floats', 'p2l_attn_fwd_ws_bytes', 'p2l_affine_grid_sample_bwd_ws_bytes',
                      'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes',
-                     'p2l_gram_f64_ws_bytes', 'p2l_gram_f64_wide_ws_bytes', 'p2l_poisson_blend_ws_bytes'):
+                     'p2l_gram_f64_ws_bytes', 'p2l_gram_f64_wide_ws_bytes', 'p2l_poisson_blend_ws_bytes',
+                     'p2l_sg2_noise_reg_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
         # (64-bit sizes: without argtypes ctypes would pass them as C int)
         # the small entry points that take an int64_t count or a float: a bare Python number would travel as C int
@@ -375,6 +377,10 @@ def lib():
         _lib.p2l_poisson_blend.argtypes = [vp, i64_, vp, i64_, vp, vp, i32, i32, i32, i32, C.c_double, i32,
                                            vp, vp, vp, C.c_size_t, vp]
         _lib.p2l_poisson_blend.restype = i32
+        _lib.p2l_sg2_noise_reg_ws_bytes.argtypes = [vp, i32, i32]
+        _lib.p2l_sg2_noise_reg_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_size_t, vp]
+        _lib.p2l_sg2_noise_reg_bwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_size_t, vp]
+        _lib.p2l_sg2_noise_normalize.argtypes = [vp, vp, i32, i32, vp, C.c_size_t, vp]
     return _lib
 
 

@@ -91,6 +91,94 @@ def weight_regularization(orig_model, curr_model, reg='l1', weight_dict=None):
 
 
 # ---------------------------------------------------------------------------
+# StyleGAN2 noise regulariser (the projector's noise_regularize)
+# ---------------------------------------------------------------------------
+def _flat_noises(noises):
+    """the reference's [B, T] variable, or the list of [B,1,h,w] maps `reshape_noise` makes of it"""
+    if torch.is_tensor(noises):
+        return noises
+    return torch.cat([n.reshape(n.size(0), -1) for n in noises], 1)
+
+
+def noise_regularize_torch(noises, noise_shape):
+    """The definition in torch ops, on any device: per layer a pyramid of 2x2 means in fp32,
+    ((a + b) + (c + d)) * 0.25, down to side 8; per level ax = mean n[y,x] n[y,x-1] and
+    ay = mean n[y,x] n[y-1,x] with wrap-around, in fp64; R = sum of ax^2 + ay^2.  The CPU path of
+    `noise_regularize` and the comparison point of tools/bench_noise_reg.py."""
+    from . import ops
+    noises = _flat_noises(noises)
+    B = noises.size(0)
+    total = torch.zeros(B, dtype=torch.float64, device=noises.device)
+    off = 0
+    for s in ops.noise_sizes(noise_shape):
+        n = noises[:, off:off + s * s].reshape(B, s, s)
+        off += s * s
+        while True:
+            d = n.double()
+            ax = (d * torch.roll(d, 1, 2)).mean((1, 2))
+            ay = (d * torch.roll(d, 1, 1)).mean((1, 2))
+            total = total + ax * ax + ay * ay
+            if s <= 8:
+                break
+            n = ((n[:, 0::2, 0::2] + n[:, 0::2, 1::2]) + (n[:, 1::2, 0::2] + n[:, 1::2, 1::2])) * 0.25
+            s //= 2
+    assert off == noises.size(1), 'noises is [B, sum res^2]'
+    return total.float()
+
+
+class _NoiseRegFn(torch.autograd.Function):
+    """R [B] of noises [B, T] through p2l_sg2_noise_reg_fwd / _bwd.  The workspace is a tensor of this call,
+    saved for the backward: nothing is shared between lanes or with a captured graph, nothing waits for the host."""
+
+    @staticmethod
+    def forward(ctx, noises, sizes):
+        from . import ops
+        x = noises.detach()
+        loss, _, ws = ops.noise_reg_fwd(x, sizes)
+        ctx.save_for_backward(x, ws)
+        ctx.sizes = sizes
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        from . import ops
+        x, ws = ctx.saved_tensors
+        return ops.noise_reg_bwd(x, ctx.sizes, ws, gloss.float().contiguous()), None
+
+
+def noise_regularize(noises, noise_shape):
+    """R [B] fp32: the sum over layers and pyramid levels of the squared mean products of horizontally and
+    vertically adjacent noise pixels (wrap-around), differentiable in `noises` ([B, T], or the list of
+    [B,1,h,w] maps).  Device tensors run the HIP kernels, CPU tensors `noise_regularize_torch`."""
+    from . import ops
+    noises = _flat_noises(noises)
+    if not noises.is_cuda:
+        return noise_regularize_torch(noises, noise_shape)
+    if noises.dtype != torch.float32 or not noises.is_contiguous():
+        noises = noises.float().contiguous()
+    return _NoiseRegFn.apply(noises, ops.noise_sizes(noise_shape))
+
+
+class NoiseRegularizer(object):
+    """`weight * noise_regularize(noises)` per candidate: the `regularizer=` of the noise variable
+    (`var_manager.register('noises', ..., regularizer=LF.NoiseRegularizer(model.noise_shape))`).
+    `weight` defaults to the StyleGAN2 projector's 1e5."""
+
+    def __init__(self, noise_shape, weight=1e5):
+        from . import ops
+        self.noise_shape = ops.noise_sizes(noise_shape)
+        self.weight = float(weight)
+
+    def graph_key(self):
+        """what a captured step bakes in of this term (optimizer/base_optimizer.py `_graph_key`)"""
+        return ('NoiseRegularizer', self.noise_shape, self.weight)
+
+    def __call__(self, noises):
+        return self.weight * noise_regularize(noises, self.noise_shape)
+
+
+# ---------------------------------------------------------------------------
 # native engine shared by Reconstruction / Perceptual / Projection losses
 # ---------------------------------------------------------------------------
 class _LpipsParams(object):

@@ -373,3 +373,93 @@ def conv1_dgrad(g, w_t3, H, W, K, S, pad):
     N.check(_lib().p2l_conv1_dgrad(N.ptr(g), N.ptr(w_t3), N.ptr(d), B, H, W, Co, K, S, pad, N.stream()),
             'conv1_dgrad')
     return d
+
+
+# ---- StyleGAN2 noise regulariser / per-layer normalisation (csrc/p2l_noise_reg.hip) ----
+_NOISE_RES = {}
+
+
+def noise_sizes(noise_shape):
+    """sides of the square noise maps: `model.noise_shape` ([1, 1, res, res] per layer) or plain ints"""
+    sizes = []
+    for s in noise_shape:
+        if hasattr(s, '__len__'):
+            assert int(s[-1]) == int(s[-2]), 'noise maps are square'
+            s = s[-1]
+        sizes.append(int(s))
+    return tuple(sizes)
+
+
+def _noise_res(sizes):
+    if sizes not in _NOISE_RES:
+        _NOISE_RES[sizes] = (C.c_int32 * len(sizes))(*sizes)
+    return _NOISE_RES[sizes]
+
+
+def noise_reg_ws_bytes(sizes, B):
+    sizes = noise_sizes(sizes)
+    return _lib().p2l_sg2_noise_reg_ws_bytes(_noise_res(sizes), len(sizes), int(B))
+
+
+def _noise_ws(sizes, B, device, what):
+    nbytes = noise_reg_ws_bytes(sizes, B)
+    if nbytes == 0:
+        raise N.NativeError('%s: layer list %s / batch %d refused (powers of two in 4..1024, at most 32 layers)'
+                            % (what, list(sizes), B))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def noise_reg_fwd(noises, sizes, want_corr=False):
+    """noises [B, T] fp32 device -> (R [B] fp32, corr [B, levels, 2] fp64 or None, workspace for noise_reg_bwd)"""
+    sizes = noise_sizes(sizes)
+    B = noises.size(0)
+    assert noises.dim() == 2 and noises.size(1) == sum(s * s for s in sizes), 'noises is [B, sum res^2]'
+    ws = _noise_ws(sizes, B, noises.device, 'p2l_sg2_noise_reg_fwd')
+    loss = torch.empty(B, dtype=torch.float32, device=noises.device)
+    corr = None
+    if want_corr:
+        n_levels = sum(1 if s <= 8 else s.bit_length() - 3 for s in sizes)
+        corr = torch.empty(B, n_levels, 2, dtype=torch.float64, device=noises.device)
+    N.check(_lib().p2l_sg2_noise_reg_fwd(N.ptr(noises), _noise_res(sizes), len(sizes), B, N.ptr(loss),
+                                         C.c_void_p(corr.data_ptr() if want_corr else 0), N.ptr(ws),
+                                         ws.numel() * 4, N.stream()), 'p2l_sg2_noise_reg_fwd')
+    return loss, corr, ws
+
+
+def noise_reg_bwd(noises, sizes, ws, gloss=None):
+    """gloss [B] (None = ones) times dR/dnoises, from noises and the workspace noise_reg_fwd left"""
+    sizes = noise_sizes(sizes)
+    dn = torch.empty_like(noises)
+    N.check(_lib().p2l_sg2_noise_reg_bwd(N.ptr(noises), _noise_res(sizes), len(sizes), noises.size(0),
+                                         N.ptr(gloss), N.ptr(dn), N.ptr(ws), ws.numel() * 4, N.stream()),
+            'p2l_sg2_noise_reg_bwd')
+    return dn
+
+
+def noise_normalize_(noises, sizes):
+    """every layer of every row of noises [B, T] to zero mean / unit unbiased deviation, in place"""
+    sizes = noise_sizes(sizes)
+    B = noises.size(0)
+    assert noises.dim() == 2 and noises.size(1) == sum(s * s for s in sizes), 'noises is [B, sum res^2]'
+    ws = _noise_ws(sizes, B, noises.device, 'p2l_sg2_noise_normalize')
+    N.check(_lib().p2l_sg2_noise_normalize(N.ptr(noises), _noise_res(sizes), len(sizes), B, N.ptr(ws),
+                                           ws.numel() * 4, N.stream()), 'p2l_sg2_noise_normalize')
+    return noises
+
+
+def noise_reg_ws_pooled(ws, sizes, B):
+    """test hook: the pooled levels [B, P] inside the workspace a forward left (per candidate: the levels >= 1 of
+    every layer, layer-major, finest first)"""
+    sizes = noise_sizes(sizes)
+    levels = items = P = 0
+    for s in sizes:
+        k = 0
+        while True:
+            levels += 1
+            items += max(1, (s * s) >> 12)
+            P += s * s if k else 0
+            if s <= 8:
+                break
+            s, k = s // 2, k + 1
+    first = B * (levels + items) * 4            # fp64 pairs, counted in floats
+    return ws[first:first + B * P].view(B, P)

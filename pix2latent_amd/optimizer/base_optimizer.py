@@ -23,6 +23,12 @@ from ..utils.image import to_image, to_grid, binarize, resize_area
 from ..variable_manager import slice_vars, FusedAdam
 
 
+def _regularizer_key(reg):
+    """what tells two regularisers apart in a graph key: their own `graph_key()` (what a capture bakes in of
+    them), else the object itself (pinned by the graph entry through `variables`)"""
+    return reg.graph_key() if hasattr(reg, 'graph_key') else id(reg)
+
+
 class _BaseOptimizer(SearchLoopMixin):
     """ Base template for gradient optimization """
 
@@ -328,13 +334,17 @@ class _BaseOptimizer(SearchLoopMixin):
         addresses of freed buffers out again (vm.initialize() in a loop gives new variables
         and a new Adam state at the old addresses), and a model or loss that frees or re-allocates
         a lane's workspace (lanes.Scratch.generation) leaves the old pointers baked into the
-        captured launches"""
+        captured launches
+        ... and the regularisers of the input variables: their launches and constants (layer list, weight)
+        are part of the capture"""
         owners = (self.model, getattr(self.loss_fn, '_engine', None))
         return (variables.num_samples, lo, hi, self.max_batch_size, self.exec_batch_size,
                 variables.opt.state_key()) + tuple(
             getattr(getattr(o, '_scratch', None), 'generation', 0) for o in owners) + tuple(
             (name, v.buf.data_ptr()) for name, v in sorted(variables.input.items())
             if v.get('buf', None) is not None) + tuple(
+            (name, _regularizer_key(v.get('regularizer', None))) for name, v in sorted(variables.input.items())
+            if v.get('regularizer', None) is not None) + tuple(
             (name, v.buf.data_ptr(), v.buf._version) for name, v in sorted(variables.output.items())
             if v.get('buf', None) is not None)
 

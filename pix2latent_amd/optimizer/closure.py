@@ -9,6 +9,9 @@ semantics listed in SURVEY.md §3.2 kept:
     loss with keyword arguments named after the output variables;
   * per-sample loss = loss_fn(...).view(b, -1).mean(1); the back-propagated
     scalar is the MEAN over the chunk (gradient factor 1/b_chunk);
+  * (not in the reference) an input variable registered with `regularizer=r` adds
+    r(x) [b] to the per-sample loss -- the value of x after the hooks, on
+    forward-only passes too -- so the reported / told losses contain the term;
   * returns (out [N,3,H,W] detached, per-sample losses, {}).
 
 Two execution paths:
@@ -81,6 +84,15 @@ def apply_hooks(vars, population=None, chunk=None):
                                               HookSpan(s, e, c0, c1))
                 elif e > s:
                     var.hook_fn(var.data[s - lo:e - lo])
+
+
+def _add_regularizers(loss, vars, input_args):
+    """per-sample loss [b] plus r(x) [b] of every input variable registered with a regularizer"""
+    for k, var in vars.input.items():
+        reg = var.get('regularizer', None)
+        if reg is not None:
+            loss = loss + reg(input_args[k]).view(loss.size(0))
+    return loss
 
 
 _SCALES = {}
@@ -169,6 +181,7 @@ def _step_fused(model, vars, loss_fn, optimize, max_batch_size, grad_scale, popu
             with torch.set_grad_enabled(bool(optimize)):
                 out = model(**input_args)
                 loss = loss_fn(out, **target_args).view(b_sz, -1).mean(1)
+                loss = _add_regularizers(loss, _vars, input_args)
                 if optimize:
                     if gs is None:
                         loss.mean().backward()
@@ -237,6 +250,7 @@ def _step_generic(model, vars, loss_fn, optimize, max_batch_size, grad_scale, po
             out = model(**input_args)
             # (3) loss
             loss = loss_fn(out, **target_args).view(b_sz, -1).mean(1)
+            loss = _add_regularizers(loss, _vars, input_args)
             if optimize:
                 if gs is None:
                     loss.mean().backward()

@@ -1,5 +1,5 @@
 """In-place latent hooks (API of reference pix2latent/utils/function_hooks.py:10-126:
-`Clamp`, `Normalize`, `NormalPerturb`, `ScheduledNormalPerturb`, `Compose`; a hook is
+`Clamp`, `Normalize`, `NormalPerturb`, `ScheduledNormalPerturb`, `Compose`, plus `NoiseNormalize`; a hook is
 called as `hook(list_of_per_sample_tensors)` before every forward pass and mutates the
 tensors in place).
 
@@ -95,6 +95,32 @@ class Normalize(_Hook):
         flat = rows.reshape(rows.size(0), -1)
         mean, std = flat.mean(1, keepdim=True), flat.std(1, keepdim=True)
         flat.sub_(mean).div_(std)
+
+
+class NoiseNormalize(_Hook):
+    """ standardises every noise map of every sample on its own -- the StyleGAN2 projector's
+    noise_normalize_: n <- (n - mean) / std per layer, unbiased std.  The variable is the flat
+    [sum res^2] noise vector, `noise_shape` the generator's (`model.noise_shape`).  One native call
+    on the device (fp64 statistics, rounded once), the torch expression on the CPU. """
+
+    def __init__(self, noise_shape):
+        from .. import ops
+        self.noise_shape = ops.noise_sizes(noise_shape)
+
+    def on_rows(self, rows):
+        flat = rows.reshape(rows.size(0), -1)
+        if flat.is_cuda:
+            from .. import ops
+            assert flat.data_ptr() == rows.data_ptr() and flat.is_contiguous(), 'rows of one contiguous buffer'
+            ops.noise_normalize_(flat, self.noise_shape)
+            return
+        off = 0
+        for s in self.noise_shape:
+            n = flat[:, off:off + s * s]
+            mean, std = n.mean(1, keepdim=True), n.std(1, keepdim=True)
+            n.sub_(mean).div_(std)
+            off += s * s
+        assert off == flat.size(1), 'rows are [B, sum res^2]'
 
 
 class NormalPerturb(_Hook):

@@ -109,7 +109,7 @@ def _slice_var(var_data, lo, hi):
     if 'buf' in var_data and var_data.buf is not None:
         sub['buf'] = var_data.buf[lo:hi]
         sub['offset'] = var_data.get('offset', 0) + lo
-    for k in ('grad_free', 'requires_grad', 'name'):
+    for k in ('grad_free', 'requires_grad', 'name', 'regularizer'):
         if k in var_data:
             sub[k] = var_data[k]
     return sub
@@ -185,10 +185,13 @@ class VariableManager():
                  learning_rate=0.05,
                  hook_fn=None,
                  grad_free=False,
+                 regularizer=None,
                  ):
         """
         Registers a variable; the specs are used at `initialize`.  Arguments as
-        in the reference (variable_manager.py:83-146).
+        in the reference (variable_manager.py:83-146), plus `regularizer`: a callable
+        `r(x [b, *shape]) -> [b]` the closure adds to the per-sample loss of an input
+        variable (after the hooks, before the backward; e.g. `LF.NoiseRegularizer`).
         """
         if variable_name in self.variable_info:
             print('variable `{}`` already exists.'.format(variable_name))
@@ -209,6 +212,7 @@ class VariableManager():
             'learning_rate': learning_rate,
             'hook_fn': hook_fn,
             'grad_free': grad_free,
+            'regularizer': regularizer,
         }
         return True
 
@@ -286,7 +290,8 @@ class VariableManager():
                  'name': v,
                  'hook_fn': spec['hook_fn'],
                  'grad_free': spec['grad_free'],
-                 'requires_grad': spec['requires_grad']}
+                 'requires_grad': spec['requires_grad'],
+                 'regularizer': spec.get('regularizer')}
 
             if not spec['requires_grad']:
                 continue
