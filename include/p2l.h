@@ -571,7 +571,9 @@ int p2l_l1_loss_bwd(const float* img16, const float* target, const float* weight
 /* wt = adjoint-bilinear-resized per-pixel weight map, so that the sum equals */
 /* the spatially weighted sum of the bilinearly upsampled distance map.       */
 /* nft = cached normalised target features (bstride 0 = one shared target).   */
-/* C in {64,128,256,512}.  Finish with p2l_reduce_rows(div = wsum).           */
+/* C in {64,128,192,256,384,512} (VGG16, AlexNet and SqueezeNet tap widths);  */
+/* any other C: P2L_EUNSUP, nothing launched.                                 */
+/* Finish with p2l_reduce_rows(div = wsum).                                   */
 int p2l_lpips_normalize(const float* f, float* nf, int64_t P, int C,
                         void* stream);
 int p2l_lpips_tap_nblk(int P, int C);
@@ -579,7 +581,12 @@ int p2l_lpips_tap_fwd(const float* f, const float* nft, int64_t nft_bstride,
                       const float* lin, const float* wt, int64_t wt_bstride,
                       float* loss_partial, int Bn, int P, int C, void* stream);
 /* df[b,p,c] = gscale[b] * wt[b,p] * d d[p] / d f[c]  (gscale already holds   */
-/* beta / wsum[b] * upstream grad)                                            */
+/* beta / wsum[b] * upstream grad).  With nrm = ||f||_2, inv = 1/(nrm+1e-10)  */
+/* and u = 2 lin (nf_o - nf_t):  df = gscale wt (u inv - c2 f),               */
+/* c2 = (u . f) inv^2 / nrm.  Where ||f|| == 0 (an all-zero feature vector:   */
+/* black or masked image regions) d nrm / d f does not exist and autograd     */
+/* gives NaN; the kernels take c2 = 0 there, i.e. the FINITE                  */
+/* df = gscale wt u / 1e-10 (f = 0 removes the c2 term in any case).          */
 int p2l_lpips_tap_bwd(const float* f, const float* nft, int64_t nft_bstride,
                       const float* lin, const float* wt, int64_t wt_bstride,
                       const float* gscale, float* df, int Bn, int P, int C,

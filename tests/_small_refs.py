@@ -2,7 +2,9 @@
 losses and the optimiser), written from the formulas in the header comments and the reference arithmetic they cite
 -- not from the kernels.  Forwards are direct restatements; every backward is autograd through its forward in
 float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks these functions against
-independent formulations, tests/test_small_kernels_gpu.py holds the kernels to them.
+independent formulations, tests/test_small_kernels_gpu.py and tests/test_loss_kernels_gpu.py hold the kernels to
+them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
 Every function takes tensors of any float dtype and computes in the dtype of its first argument, so that the same
@@ -207,6 +209,85 @@ def reduce_rows(partial, scale, div=None):
 
 def vec_scale_div(a, scale, div=None):
     return a * scale if div is None else a * scale / div.to(a.dtype)
+
+
+# ---- LPIPS loss path (tests/test_loss_kernels_gpu.py) -------------------------------------------------------------
+# features are NHWC: f, nft [B, P, C] (or [B, H, W, C]); a target shared by the batch is nft [P, C] / wt [P]
+def lpips_normalize(f):                             # nf = f / (||f||_2 + 1e-10), the norm over the channels
+    return f / (torch.sqrt((f * f).sum(dim=-1, keepdim=True)) + 1e-10)
+
+
+def lpips_tap(f, nft, lin, wt):
+    """[B]: sum_p wt[p] * sum_c lin_c (nf - nft)^2"""
+    d = (lin.to(f.dtype) * (lpips_normalize(f) - nft.to(f.dtype)) ** 2).sum(dim=-1)
+    return (d * wt.to(f.dtype)).sum(dim=-1)
+
+
+def lpips_tap_bwd(f, nft, lin, wt, gscale):
+    """df[b,p,:] = gscale[b] * wt[b,p] * d(sum_c lin_c (nf - nft)^2) / df in closed form: with u = 2 lin (nf - nft)
+    and inv = 1 / (nrm + 1e-10), df = gscale wt (u inv - c2 f), c2 = (u . f) inv^2 / nrm -- and c2 = 0 where
+    nrm == 0, where d nrm / df does not exist (autograd: NaN) and f = 0 removes the term: df = gscale wt u / 1e-10"""
+    nrm = torch.sqrt((f * f).sum(dim=-1, keepdim=True))
+    inv = 1.0 / (nrm + 1e-10)
+    u = 2.0 * lin.to(f.dtype) * (f * inv - nft.to(f.dtype))
+    uf = (u * f).sum(dim=-1, keepdim=True)
+    c2 = torch.where(nrm > 0, uf * inv * inv / torch.where(nrm > 0, nrm, torch.ones_like(nrm)), torch.zeros_like(nrm))
+    gsw = gscale.to(f.dtype).view(-1, 1) * wt.to(f.dtype)
+    return gsw[..., None] * (u * inv - c2 * f)
+
+
+def _pool_vjp(x, gp, k, s):
+    """gradient of sum(max_pool2d(x, k, s) * gp) w.r.t. x, NHWC in and out: ATen sends the gradient of a window to
+    its first maximum in scan order"""
+    g = vjp(lambda x_: F.max_pool2d(x_.permute(0, 3, 1, 2), k, s), [x], gp.to(x.dtype).permute(0, 3, 1, 2))
+    return g
+
+
+def maxpool2_bwd(y, dyp, add=None, relu_mask=False):
+    """y [B,H,W,C], dyp [B,H/2,W/2,C]: pool backward, then + add, then * (y > 0)"""
+    dy = _pool_vjp(y, dyp, 2, 2)
+    if add is not None:
+        dy = dy + add.to(y.dtype)
+    return dy * (y > 0).to(y.dtype) if relu_mask else dy
+
+
+def maxpool3s2(x):                                  # [B,Hi,Wi,C] -> [B,Ho,Wo,C], 3x3 windows, stride 2, no padding
+    return F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2).permute(0, 2, 3, 1).contiguous()
+
+
+def maxpool3s2_bwd(x, gp, gtap=None):
+    """(pool backward of gp + gtap) * (x > 0)"""
+    dx = _pool_vjp(x, gp, 3, 2)
+    if gtap is not None:
+        dx = dx + gtap.to(x.dtype)
+    return dx * (x > 0).to(x.dtype)
+
+
+def lpips_tap_pool_bwd(f, nft, lin, wt, gscale, dyp):
+    """f [B,H,W,C] is a tap and the input of relu -> 2x2 max pool: tap backward, then the pool backward with the tap
+    gradient as the additive term and the ReLU mask"""
+    B, H, W, C = f.shape
+    tap = lpips_tap_bwd(f.reshape(B, H * W, C), nft, lin, wt, gscale).view(B, H, W, C)
+    return maxpool2_bwd(f, dyp, tap, True)
+
+
+def bilinear_adjoint(wsrc, h, w):
+    """wsrc [B,H,W] -> [B,h,w]: the adjoint of F.interpolate(bilinear, align_corners=False) from h x w up to H x W"""
+    B, H, W = wsrc.shape
+    up = lambda m: F.interpolate(m, size=(H, W), mode='bilinear', align_corners=False)
+    return vjp(up, [wsrc.new_zeros(B, 1, h, w)], wsrc[:, None])[:, 0]
+
+
+def conv1_dgrad(g, w_t3, H, W, K, S, pad):
+    """g [B,Ho,Wo,Co], w_t3 [K*K][3][Co] -> NHWC16 gradient of the H x W input of the stride-S KxK conv; pixels past
+    the last window get nothing (output_padding), channels 3..15 are zero"""
+    B, Ho, Wo, Co = g.shape
+    wgt = w_t3.to(g.dtype).view(K, K, 3, Co).permute(3, 2, 0, 1)                      # [Co, 3, K, K]
+    opad = (H + 2 * pad - K - (Ho - 1) * S, W + 2 * pad - K - (Wo - 1) * S)
+    d = F.conv_transpose2d(g.permute(0, 3, 1, 2), wgt, stride=S, padding=pad, output_padding=opad)
+    out = g.new_zeros(B, H, W, 16)
+    out[..., :3] = d.permute(0, 2, 3, 1)
+    return out
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

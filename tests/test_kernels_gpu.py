@@ -867,8 +867,9 @@ def test_lpips_tap(dev, O, C):
 def test_lpips_tap_pool_bwd(dev, O, C):
     """Round 5: the gradient of a VGG tap that relu -> 2x2 max pool follows, in ONE pass
     (p2l_lpips_tap_pool_bwd) = tap backward, then pool backward + ReLU mask (the two kernels of rounds 1-4)
-    bit for bit, and = autograd of the torch composition; ties inside a quad (ReLU zeros) go to the first
-    maximum in scan order as ATen's max_pool2d does; the partial maxima cover what was written."""
+    bit for bit, and = autograd of the torch composition; the partial maxima cover what was written.  (The only ties
+    in this data are quads of ReLU zeros, and the f > 0 mask erases whichever pixel won them: the first-maximum rule
+    is pinned with equal POSITIVE maxima in tests/test_loss_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(12)
     B, h = 3, 32
     pre = torch.randn(B, C, h, h, generator=g).requires_grad_(True)     # conv output before the ReLU

@@ -159,3 +159,146 @@ def test_layout_and_misc():
     W = torch.randn(8, 6, generator=g, dtype=D)
     dy = torch.randn(3, 6, generator=g, dtype=D)
     assert (R.linear_bwd(dy, W) - dy @ W.t()).abs().max().item() < 1e-13
+
+
+# ---- LPIPS loss path ---------------------------------------------------------------------------------------------
+def test_lpips_tap_bwd_closed_form_is_autograd_and_finite_at_zero():
+    g = _g(20)
+    B, P, C = 3, 11, 8
+    f = F.relu(torch.randn(B, P, C, generator=g, dtype=D))
+    f[1, 4] *= 1e-10                                                     # the eps matters here
+    f[2, 0] = 0
+    f[2, 0, 3] = 1e-10
+    ft = F.relu(torch.randn(B, P, C, generator=g, dtype=D))
+    ft[0, 2] = 0
+    nft = R.lpips_normalize(ft)
+    assert torch.equal(nft[0, 2], torch.zeros(C, dtype=D))               # 0 / (0 + 1e-10)
+    assert abs(nft[1, 1].norm().item() - 1) < 1e-9
+    lin, wt = torch.rand(C, generator=g, dtype=D), torch.rand(B, P, generator=g, dtype=D)
+    gs = torch.tensor([0.7, -1.3, 0.4], dtype=D)
+    # the forward is the oracle's expression (lpips_ref.normalize_tensor over the channel axis of NCHW)
+    nchw = lambda t: t.view(B, 1, P, C).permute(0, 3, 1, 2)
+    d = ((lpips_ref.normalize_tensor(nchw(f)) - nchw(nft)) ** 2 * lin.view(1, C, 1, 1)).sum(1)[:, 0]
+    assert (R.lpips_tap(f, nft, lin, wt) - (d * wt).sum(1)).abs().max().item() < 1e-14
+    got = R.lpips_tap_bwd(f, nft, lin, wt, gs)
+    auto = R.vjp(lambda f_: R.lpips_tap(f_, nft, lin, wt), [f], gs)
+    assert bool(torch.isfinite(auto).all())
+    scale = auto.abs().amax(dim=2, keepdim=True) + 1e-300
+    assert ((got - auto).abs() / scale).max().item() < 1e-9
+    # a shared target: nft [P, C], wt [P]
+    shared = R.lpips_tap_bwd(f, nft[0], lin, wt[0], gs)
+    assert torch.equal(shared, R.lpips_tap_bwd(f, nft[:1].expand(B, P, C), lin, wt[:1].expand(B, P), gs))
+    # an all-zero pixel: autograd is NaN there (and only there), the closed form is gscale wt u / eps
+    f[0, 5] = 0
+    auto = R.vjp(lambda f_: R.lpips_tap(f_, nft, lin, wt), [f], gs)
+    nan = torch.isnan(auto).any(dim=2)
+    assert bool(nan[0, 5]) and int(nan.sum()) == 1
+    got = R.lpips_tap_bwd(f, nft, lin, wt, gs)
+    assert bool(torch.isfinite(got).all())
+    want = gs[0] * wt[0, 5] * 2 * lin * (0 - nft[0, 5]) / 1e-10
+    assert torch.allclose(got[0, 5], want, rtol=1e-14, atol=0)
+    keep = ~nan
+    assert ((got - auto).abs() / scale)[keep].max().item() < 1e-9
+
+
+def _upsample_matrix(n_out, n_in):
+    """[n_out, n_in] weights of bilinear interpolation along one axis, align_corners=False"""
+    U = torch.zeros(n_out, n_in, dtype=D)
+    for p in range(n_out):
+        src = max((p + 0.5) * n_in / n_out - 0.5, 0.0)
+        i0 = int(src)
+        i1 = min(i0 + 1, n_in - 1)
+        U[p, i0] += 1 - (src - i0)
+        U[p, i1] += src - i0
+    return U
+
+
+@pytest.mark.parametrize('H,W,h,w', [(8, 8, 8, 8), (16, 8, 4, 4), (64, 48, 7, 3), (37, 53, 9, 20), (16, 16, 1, 1)])
+def test_bilinear_adjoint_is_the_transposed_dense_matrix(H, W, h, w):
+    wsrc = torch.randn(2, H, W, generator=_g(21), dtype=D)
+    Uy, Ux = _upsample_matrix(H, h), _upsample_matrix(W, w)
+    m = torch.randn(2, 1, h, w, generator=_g(22), dtype=D)
+    up = F.interpolate(m, size=(H, W), mode='bilinear', align_corners=False)[:, 0]
+    assert (up - Uy @ m[:, 0] @ Ux.t()).abs().max().item() < 1e-13       # the matrix is the upsampling
+    want = Uy.t() @ wsrc @ Ux
+    got = R.bilinear_adjoint(wsrc, h, w)
+    assert got.shape == (2, h, w) and (got - want).abs().max().item() < 1e-12
+
+
+@pytest.mark.parametrize('H,W,Co,K,S,pad', [(3, 3, 4, 3, 2, 0), (19, 16, 8, 3, 2, 0), (37, 50, 4, 11, 4, 2), (5, 5, 4, 1, 2, 0)])
+def test_conv1_dgrad_is_autograd_of_conv2d(H, W, Co, K, S, pad):
+    g = _g(23)
+    w = torch.randn(Co, 3, K, K, generator=g, dtype=D)
+    x = torch.randn(2, 3, H, W, generator=g, dtype=D)
+    y = F.conv2d(x, w, None, stride=S, padding=pad)
+    dy = torch.randn(y.shape, generator=g, dtype=D)
+    want = R.vjp(lambda x_: F.conv2d(x_, w, None, stride=S, padding=pad), [x], dy)
+    w_t3 = w.permute(2, 3, 1, 0).reshape(K * K, 3, Co).contiguous()
+    got = R.conv1_dgrad(dy.permute(0, 2, 3, 1).contiguous(), w_t3, H, W, K, S, pad)
+    assert got.shape == (2, H, W, 16) and torch.equal(got[..., 3:], torch.zeros(2, H, W, 13, dtype=D))
+    assert (got[..., :3] - want.permute(0, 2, 3, 1)).abs().max().item() < 1e-12
+    # pixels that no window covers: exactly zero
+    cov_y = torch.zeros(H + 2 * pad, dtype=torch.bool)
+    cov_x = torch.zeros(W + 2 * pad, dtype=torch.bool)
+    for o in range(y.shape[2]):
+        cov_y[o * S:o * S + K] = True
+    for o in range(y.shape[3]):
+        cov_x[o * S:o * S + K] = True
+    cov = cov_y[pad:pad + H, None] & cov_x[None, pad:pad + W]
+    assert bool((got[:, ~cov] == 0).all())
+    if (H + 2 * pad - K) % S or K < S:
+        assert not bool(cov.all())
+
+
+def test_pool_references_on_hand_written_ties():
+    """ATen's rule, written out: the first maximum in row-major scan order of the window takes the gradient"""
+    # 2x2: one quad per channel; value 5 at the listed positions, 1 elsewhere; expected winner = the first listed
+    pats = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3), (0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3), (0, 1, 2, 3)]
+    y = torch.ones(1, 2, 2, len(pats), dtype=D)
+    for c, pat in enumerate(pats):
+        for s in pat:
+            y[0, s >> 1, s & 1, c] = 5.0
+    dyp = torch.arange(1, len(pats) + 1, dtype=D).view(1, 1, 1, -1)
+    got = R.maxpool2_bwd(y, dyp)
+    want = torch.zeros_like(y)
+    for c, pat in enumerate(pats):
+        want[0, pat[0] >> 1, pat[0] & 1, c] = c + 1
+    assert torch.equal(got, want)
+    add = torch.full_like(y, 0.5)
+    assert torch.equal(R.maxpool2_bwd(y, dyp, add), want + 0.5)
+    y0 = y.clone()
+    y0[0, 0, 0, :] = 0.0                                                 # masked where y == 0, after the add
+    got = R.maxpool2_bwd(y0, dyp, add, True)
+    assert torch.equal(got[0, 0, 0], torch.zeros(len(pats), dtype=D)) and torch.equal(got[0, 1, 1], R.maxpool2_bwd(y0, dyp, add)[0, 1, 1])
+    # 3x3 / stride 2 on an all-equal 5x5: four windows, each sends its gradient to its first element
+    x = torch.full((1, 5, 5, 1), 2.0, dtype=D)
+    gp = torch.tensor([[1.0, 2.0], [4.0, 8.0]], dtype=D).view(1, 2, 2, 1)
+    assert torch.equal(R.maxpool3s2(x), torch.full((1, 2, 2, 1), 2.0, dtype=D))
+    want = torch.zeros(5, 5, dtype=D)
+    want[0, 0], want[0, 2], want[2, 0], want[2, 2] = 1, 2, 4, 8
+    assert torch.equal(R.maxpool3s2_bwd(x, gp)[0, :, :, 0], want)
+    # ties at scan positions 4 and 8 of window (0, 0); position 8 is position 0 of window (1, 1) and its only maximum
+    x = torch.ones(1, 5, 5, 1, dtype=D)
+    x[0, 1, 1, 0] = x[0, 2, 2, 0] = 3.0
+    want = torch.zeros(5, 5, dtype=D)
+    want[1, 1], want[2, 2] = 1, 8                                        # windows (0,1) and (1,0) hold (2,2) alone
+    want[2, 2] += 2 + 4
+    assert torch.equal(R.maxpool3s2_bwd(x, gp)[0, :, :, 0], want)
+    gt = torch.full((1, 5, 5, 1), 0.25, dtype=D)
+    x[0, 2, 2, 0] = 0.0                                                  # (1,1) now wins all of window (0,0); (2,2) is masked
+    got = R.maxpool3s2_bwd(x, gp, gt)[0, :, :, 0]
+    assert got[1, 1].item() == 1.25 and got[2, 2].item() == 0.0 and got[4, 4].item() == 0.25
+    # even sizes: the last row / column lies in no window and receives gtap only
+    x = torch.rand(1, 6, 8, 2, generator=_g(24), dtype=D) + 0.1
+    gp = torch.randn(1, 2, 3, 2, generator=_g(25), dtype=D)
+    gt = torch.randn(1, 6, 8, 2, generator=_g(26), dtype=D)
+    got = R.maxpool3s2_bwd(x, gp, gt)
+    assert torch.equal(got[:, 5], gt[:, 5]) and torch.equal(got[:, :, 7], gt[:, :, 7])
+    # the composition: tap backward + pool backward + mask
+    f = F.relu(torch.randn(2, 4, 6, 8, generator=_g(27), dtype=D))
+    nft = R.lpips_normalize(F.relu(torch.randn(2, 24, 8, generator=_g(28), dtype=D)))
+    lin, wt = torch.rand(8, generator=_g(29), dtype=D), torch.rand(2, 24, generator=_g(30), dtype=D)
+    gs, dyp = torch.tensor([0.5, -2.0], dtype=D), torch.randn(2, 2, 3, 8, generator=_g(31), dtype=D)
+    tap = R.lpips_tap_bwd(f.view(2, 24, 8), nft, lin, wt, gs).view(2, 4, 6, 8)
+    pooled = R.vjp(lambda f_: F.max_pool2d(f_.permute(0, 3, 1, 2), 2), [f], dyp.permute(0, 3, 1, 2))
+    assert torch.equal(R.lpips_tap_pool_bwd(f, nft, lin, wt, gs, dyp), (pooled + tap) * (f > 0))
