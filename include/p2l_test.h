@@ -14,7 +14,7 @@ extern "C" {
 #endif
 
 /* test hook, host logic only: the bookkeeping rules of the plans' per-run maxima registry
- * (csrc/p2l_plan.hip AmaxReg); 0 = all hold */
+ * (csrc/p2l_plan.hip AmaxReg, a member of the run context PlanRun); 0 = all hold */
 int p2l_selftest_amaxreg(void);
 
 /* debug/test hook: float offset + shape of a saved activation in ws.        */
@@ -33,7 +33,8 @@ int p2l_biggan_ws_lookup(const P2LBigGAN* m, int Bn, int what, int L,
                          size_t* float_off, int32_t shape[4]);
 
 /* debug/test hook: float offset + shape [B,h,w,C] of the post-ReLU output of VGG conv idx
- * (0..12) inside ws after p2l_projloss_fwd */
+ * (0..12) inside ws after p2l_projloss_fwd (the same for every weight format: what follows the format lies
+ * behind the conv outputs) */
 int p2l_projloss_ws_lookup(int Bn, int H, int W, int idx, size_t* float_off, int32_t shape[4]);
 
 /* debug/test hook: the saved activations of the LPIPS-SqueezeNet pass inside ws after p2l_sqzloss_fwd, [B,h,w,C]:

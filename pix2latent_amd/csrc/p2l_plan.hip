@@ -51,35 +51,19 @@ struct ConvCall {
   // are then recorded as max|y*s + t| (P2LAmax.next_s) and the reader needs no bound
   const float* next_ps = nullptr; const float* next_pt = nullptr; int next_bstride = 0;
 };
-// weight format of the 3x3 convs of the model whose plan is running on this thread
-// (set at every extern "C" entry from the model struct's wfmt)
-thread_local int g_plan_wfmt = P2L_WFMT_F32;
-// P2LConv.form bits every conv of the running plan gets (A/B builds: -DP2L_AB_BWD_BF3 / _BG / _PL keep the
-// backward passes -- both / generator / loss network -- in the bf16 x 3 arithmetic)
-thread_local int g_plan_form = 0;
-
-ConvCall mk_conv(int B, int H, int W, int Cin, int Cout, int taps) {
-  ConvCall c;
-  c.d.wfmt = (taps == 9) ? (g_plan_wfmt & 0xF)
-                         : ((g_plan_wfmt & P2L_WFMT_FLAG_PW) ? P2L_WFMT_PW : P2L_WFMT_F32);
-  c.d.ext = 0;
-  c.d.form = g_plan_form;
-  c.d.B = B; c.d.H = H; c.d.W = W; c.d.Cin = Cin; c.d.Cout = Cout; c.d.taps = taps;
-  c.d.ups = 0; c.d.x_ld = Cin; c.d.pro = P2L_PRO_NONE; c.d.pro_bstride = 0;
-  c.d.alpha = 1.f; c.d.act = P2L_ACT_NONE; c.d.pool = P2L_POOL_NONE;
-  c.d.y_ld = Cout; c.d.yp_ld = Cout; c.d.n_store = Cout; c.d.res_ld = 0;
-  c.d.res_ups = 0; c.d.mask_ld = 0; c.d.splitk = 1; c.d.algo_flops = 0.0;
-  return c;
-}
-size_t conv_ws_floats(ConvCall& c) {
+// split-K workspace floats and maxima slots per image a plan has to provide for this conv (arena sizing)
+void conv_sizes(ConvCall c, size_t& max_sk, int& max_slots) {
   c.d.splitk = p2l_conv_suggest_splitk(&c.d);
-  return p2l_conv_workspace_bytes(&c.d) / sizeof(float);
+  const size_t f = p2l_conv_workspace_bytes(&c.d) / sizeof(float);
+  if (f > max_sk) max_sk = f;
+  const int ns = p2l_conv_amax_slots(&c.d);
+  if (ns > max_slots) max_slots = ns;
 }
 
 // ---------------------------------------------------------------------------
 // Maxima handed from the conv that writes a tensor to the conv that reads it (P2LAmax): the
-// bookkeeping of ONE plan run, on the stack of the entry point (thread_local pointer: a plan runs
-// on the calling thread).  A tensor is known by its address and extents; its entry dies when
+// bookkeeping of ONE plan run, inside the run context (PlanRun) on the stack of the entry
+// point.  A tensor is known by its address and extents; its entry dies when
 // another conv writes the buffer (run_conv), when a non-conv kernel writes it (amax_drop at that
 // call site) or when its slot set comes round again in the ring.
 // ---------------------------------------------------------------------------
@@ -149,25 +133,69 @@ struct AmaxReg {
     return false;
   }
 };
-thread_local AmaxReg* g_amax = nullptr;
-struct AmaxScope {                                     // one per plan entry point
-  AmaxReg reg;
-  AmaxScope(float* ring, size_t set_floats, size_t set_stride) {
+// ---------------------------------------------------------------------------
+// What ONE plan run hands to its helpers, built on the stack of an entry point and passed by reference:
+// nothing of a run outlives the call, and a size query (which builds one without a workspace) leaves nothing.
+// ---------------------------------------------------------------------------
+struct ArbArgs;
+struct PlanRun {
+  const int wfmt;            // the model descriptor's wfmt: format of the 3x3 convs | P2L_WFMT_FLAG_*
+  // P2LConv.form bits every conv of the run gets (A/B builds: -DP2L_AB_BWD_BF3 / _BG / _PL keep the
+  // backward passes -- both / generator / loss network -- in the bf16 x 3 arithmetic)
+  const int form;
+  float* const skws; const size_t skws_floats;   // the split-K workspace every launch of the run shares
+  void* const st;
+  AmaxReg reg; bool hand = false;                // hand: the maxima hand-over is on (reg has a ring)
+  AmaxReg* amax() { return hand ? &reg : nullptr; }   // the registry of the run, NULL: no hand-over
+  explicit PlanRun(int wfmt_, int form_ = 0, float* skws_ = nullptr, size_t skws_floats_ = 0, void* st_ = nullptr)
+      : wfmt(wfmt_), form(form_), skws(skws_), skws_floats(skws_floats_), st(st_) {}
+  // an EMPTY registry over the arena's ring: once per generator pass, feature forward or loss backward
+  void amax_begin(float* ring, size_t set_floats, size_t set_stride) {
+    reg = AmaxReg();
     reg.ring = ring; reg.set_floats = set_floats; reg.set_stride = set_stride;
+    hand = set_floats && !(wfmt & P2L_WFMT_FLAG_NO_AMAX);     // (model descriptor flag)
 #ifdef P2L_NO_AMAX_HANDOVER                            // (A/B build: tools/ab_build.sh p2l_plan -DP2L_NO_AMAX_HANDOVER)
-    set_floats = 0;
+    hand = false;
 #endif
-    if (g_plan_wfmt & P2L_WFMT_FLAG_NO_AMAX) set_floats = 0;   // (model descriptor flag)
-    g_amax = set_floats ? &reg : nullptr;
   }
-  ~AmaxScope() { g_amax = nullptr; }
+  ConvCall mk_conv(int B, int H, int W, int Cin, int Cout, int taps) const {
+    ConvCall c;
+    c.d.wfmt = (taps == 9) ? (wfmt & 0xF) : ((wfmt & P2L_WFMT_FLAG_PW) ? P2L_WFMT_PW : P2L_WFMT_F32);
+    c.d.ext = 0;
+    c.d.form = form;
+    c.d.B = B; c.d.H = H; c.d.W = W; c.d.Cin = Cin; c.d.Cout = Cout; c.d.taps = taps;
+    c.d.ups = 0; c.d.x_ld = Cin; c.d.pro = P2L_PRO_NONE; c.d.pro_bstride = 0;
+    c.d.alpha = 1.f; c.d.act = P2L_ACT_NONE; c.d.pool = P2L_POOL_NONE;
+    c.d.y_ld = Cout; c.d.yp_ld = Cout; c.d.n_store = Cout; c.d.res_ld = 0;
+    c.d.res_ups = 0; c.d.mask_ld = 0; c.d.splitk = 1; c.d.algo_flops = 0.0;
+    return c;
+  }
+  int run_conv(ConvCall& c);
+  int run_dgrad_arb(ConvCall& c, const ArbArgs& a, float* dx, float* tmp, float* part);
+  // dense batched product C[M][N] = A x B through the shared workspace (the GEMM attention path): the shape
+  // and the two k-major flags fix every pitch
+  int dense_gemm(int batch, int M, int N, int K, int a_kmajor, int b_kmajor, const float* A, const float* B,
+                 float* C) {
+    P2LGemm g{};
+    g.batch = batch; g.M = M; g.N = N; g.K = K;
+    g.lda = a_kmajor ? M : K; g.ldb = b_kmajor ? N : K; g.ldc = N;
+    g.stride_a = (int64_t)M * K; g.stride_b = (int64_t)N * K; g.stride_c = (int64_t)M * N;
+    g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor; g.alpha = 1.f; g.accumulate = 0;
+    return p2l_gemm_ws(&g, A, B, C, skws, skws_floats * sizeof(float), st);
+  }
+  void amax_drop(const float* t) { if (amax()) reg.drop(t); }
+  // a NON-conv kernel writes t [B,H,W,C] and can leave ns maxima per image: t's entry dies; launch(slots) gets
+  // a set of the ring when the hand-over is on and ns * B fits (else NULL), and its maxima are entered
+  template <class Launch>
+  int amax_writer(const float* t, int B, int H, int W, int C, int ns, Launch&& launch) {
+    int set = -1;
+    amax_drop(t);
+    float* so = (amax() && ns > 0 && (size_t)ns * B <= reg.set_floats) ? reg.take(&set) : nullptr;
+    RET_IF(launch(so));
+    if (so) reg.put(t, B, H, W, C, so, ns, set);
+    return P2L_OK;
+  }
 };
-inline void amax_drop(const float* t) { if (g_amax) g_amax->drop(t); }
-// slots per image a plan has to provide for this conv's maxima (ring sizing)
-int conv_amax_slots(ConvCall& c) {
-  c.d.splitk = p2l_conv_suggest_splitk(&c.d);
-  return p2l_conv_amax_slots(&c.d);
-}
 
 }  // namespace
 // (library-internal, p2l_common.h: the StyleGAN2 plan folds the partials of its high-resolution producers too)
@@ -227,9 +255,9 @@ extern "C" int p2l_selftest_amaxreg(void) {
 }
 namespace {
 
-int run_conv(ConvCall& c, float* skws, size_t skws_floats, void* st) {
+int PlanRun::run_conv(ConvCall& c) {
   c.d.splitk = p2l_conv_suggest_splitk(&c.d);
-  AmaxReg* R = g_amax;
+  AmaxReg* R = amax();
   P2LConvExtra ex{};
   float *so = nullptr, *sop = nullptr;
   int ns = 0, set_o = -1, set_p = -1;
@@ -268,8 +296,7 @@ struct ArbArgs {
   const float* skip; int skip_ld, skip_C, skip_ups;
   float* ds; float* dt; int dsdt_bstride;
 };
-int run_dgrad_arb(ConvCall& c, const ArbArgs& a, float* dx, float* tmp, float* part,
-                  float* skws, size_t skws_floats, void* st) {
+int PlanRun::run_dgrad_arb(ConvCall& c, const ArbArgs& a, float* dx, float* tmp, float* part) {
   c.d.splitk = p2l_conv_suggest_splitk(&c.d);
   const bool pooled = c.d.pool == P2L_POOL_SUM;
   const bool half = pooled || c.d.ups == 3;          // result lives at half resolution
@@ -281,7 +308,7 @@ int run_dgrad_arb(ConvCall& c, const ArbArgs& a, float* dx, float* tmp, float* p
     arb.x = a.x; arb.x_ld = a.x_ld; arb.s = a.s; arb.t = a.t; arb.st_bstride = a.st_bstride;
     arb.skip = a.skip; arb.skip_ld = a.skip_ld; arb.skip_C = a.skip_C; arb.skip_ups = a.skip_ups;
     arb.ds = a.ds; arb.dt = a.dt; arb.dsdt_bstride = a.dsdt_bstride; arb.partial = part;
-    AmaxReg* R = g_amax;
+    AmaxReg* R = amax();
     float* so = nullptr;
     int ns = 0, set_o = -1;
     if (R) {
@@ -299,7 +326,7 @@ int run_dgrad_arb(ConvCall& c, const ArbArgs& a, float* dx, float* tmp, float* p
     return rc;
   }
   if (pooled) { c.yp = tmp; c.y = nullptr; } else { c.y = tmp; c.yp = nullptr; }
-  RET_IF(run_conv(c, skws, skws_floats, st));
+  RET_IF(run_conv(c));
   amax_drop(dx);
   return p2l_affine_relu_bwd(tmp, c.d.Cout, a.x, a.x_ld, a.s, a.t, a.st_bstride, a.skip,
                              a.skip_ld, a.skip_C, a.skip_ups, dx, c.d.Cout, a.ds, a.dt,
@@ -333,11 +360,11 @@ struct BGLayout {
   int out_res;
 };
 
-int bg_layout(const P2LBigGAN* m, int B, BGLayout& L) {
+int bg_layout(const P2LBigGAN* m, int B, BGLayout& L, int form = 0) {
   if (!m || m->n_blocks < 1 || m->n_blocks > P2L_MAX_BLOCKS || B < 1) return P2L_EINVAL;
   // kernel choice (hence split-K workspace and activation-backward partial rows) follows the
-  // weight format: the size query and the run must lay the arena out for the same one
-  g_plan_wfmt = m->wfmt;
+  // weight format: the size query and the run lay the arena out for the descriptor's
+  const PlanRun run(m->wfmt, form);
   Arena a;
   const int cond = m->z_dim + m->c_dim;
   L.cond = a.take((size_t)B * cond);
@@ -356,11 +383,7 @@ int bg_layout(const P2LBigGAN* m, int B, BGLayout& L) {
   size_t sum_partial = 0, max_sk = 0;
   int max_slots = 0;
   auto upd_sk = [&](int Hc, int Cin, int Cout, int taps) {
-    ConvCall c = mk_conv(B, Hc, Hc, Cin, Cout, taps);
-    const size_t f = conv_ws_floats(c);
-    if (f > max_sk) max_sk = f;
-    const int ns = conv_amax_slots(c);
-    if (ns > max_slots) max_slots = ns;
+    conv_sizes(run.mk_conv(B, Hc, Hc, Cin, Cout, taps), max_sk, max_slots);
   };
   for (int i = 0; i < m->n_blocks; ++i) {
     if (i == m->attn_before) {
@@ -429,7 +452,7 @@ int bg_layout(const P2LBigGAN* m, int B, BGLayout& L) {
       // this block: one per 128-pixel tile in the conv epilogue, one per 2x2 quad when the
       // input-gradient conv splits K (small batches) and its finish kernel does the work
       auto pf_of = [&](int Hc, int Cin, int Cout, int taps, int pool) {
-        ConvCall c = mk_conv(B, Hc, Hc, Cin, Cout, taps);
+        ConvCall c = run.mk_conv(B, Hc, Hc, Cin, Cout, taps);
         c.d.pool = pool;
         c.d.splitk = p2l_conv_suggest_splitk(&c.d);
         int nb = p2l_conv_arb_nblk_ws(&c.d);
@@ -568,14 +591,22 @@ extern "C" int p2l_biggan_ws_lookup(const P2LBigGAN* m, int Bn, int what, int Li
 
 extern "C" int p2l_biggan_fwd(const P2LBigGAN* m, const float* z, const float* c, int B,
                               void* ws, size_t ws_bytes, float* img16, void* st) {
-  g_plan_wfmt = m ? m->wfmt : P2L_WFMT_F32;
   BGLayout L;
   RET_IF(bg_layout(m, B, L));
   if (!ws || ws_bytes < L.total * sizeof(float) || !z || !c || !img16) return P2L_EWS;
   float* W = (float*)ws;
   const int cond = m->z_dim + m->c_dim, CT = m->cbn_total;
-  float* skws = W + L.skws;
-  AmaxScope amax_scope(W + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  PlanRun run(m->wfmt, 0, W + L.skws, L.skws_floats, st);
+  run.amax_begin(W + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  // conv k of GenBlock g reads relu(cbn_k(x)) and leaves the maxima of what it writes (its reader takes the
+  // fp16 x 2 form with them); where the plan knows that reader's CBN (block nb, index nk: the affine it fuses
+  // in front of its ReLU) the maxima are recorded with it applied
+  auto cbn = [&](ConvCall& cc, const P2LGenBlock& g, int k, const P2LGenBlock* nb, int nk) {
+    cc.d.pro = P2L_PRO_AFFINE_RELU; cc.d.pro_bstride = CT;
+    cc.ps = W + L.s + g.cbn_off[k]; cc.pt = W + L.t + g.cbn_off[k];
+    cc.want_amax = true;
+    if (nb) { cc.next_ps = W + L.s + nb->cbn_off[nk]; cc.next_pt = W + L.t + nb->cbn_off[nk]; cc.next_bstride = CT; }
+  };
 
   RET_IF(p2l_concat2(z, c, W + L.cond, B, m->z_dim, m->c_dim, st));
   RET_IF(p2l_linear_fwd(W + L.cond, m->cbn_w, nullptr, W + L.raw, B, cond, 2 * CT, st));
@@ -590,17 +621,17 @@ extern "C" int p2l_biggan_fwd(const P2LBigGAN* m, const float* z, const float* c
     if (i == m->attn_before) {
       const int C = m->attn_ch, H = L.att_H, P = H * H;
       if (C != Cx) return P2L_EINVAL;
-      ConvCall th = mk_conv(B, H, H, C, C / 8, 1);
+      ConvCall th = run.mk_conv(B, H, H, C, C / 8, 1);
       th.x = x; th.w = m->att_w[0]; th.y = W + L.att_theta;
-      RET_IF(run_conv(th, skws, L.skws_floats, st));
-      ConvCall ph = mk_conv(B, H, H, C, C / 8, 1);
+      RET_IF(run.run_conv(th));
+      ConvCall ph = run.mk_conv(B, H, H, C, C / 8, 1);
       ph.x = x; ph.w = m->att_w[1]; ph.y = W + L.att_phi; ph.yp = W + L.att_phi_p;
       ph.d.pool = P2L_POOL_MAX;
-      RET_IF(run_conv(ph, skws, L.skws_floats, st));
-      ConvCall gg = mk_conv(B, H, H, C, C / 2, 1);
+      RET_IF(run.run_conv(ph));
+      ConvCall gg = run.mk_conv(B, H, H, C, C / 2, 1);
       gg.x = x; gg.w = m->att_w[2]; gg.y = W + L.att_g; gg.yp = W + L.att_g_p;
       gg.d.pool = P2L_POOL_MAX;
-      RET_IF(run_conv(gg, skws, L.skws_floats, st));
+      RET_IF(run.run_conv(gg));
       if (L.att_fused) {
         // attn_g = softmax(theta phi_p^T) g_p, fused; lse = row statistic for the backward pass
         P2LAttn ad{B, P, P / 4, C / 8, C / 2};
@@ -608,29 +639,17 @@ extern "C" int p2l_biggan_fwd(const P2LBigGAN* m, const float* z, const float* c
                             W + L.att_lse, W + L.att_ws, L.att_ws_floats * sizeof(float), st));
       } else {
       // S = theta^T phi  -> [B, P, P/4]
-        P2LGemm g1{};
-        g1.batch = B; g1.M = P; g1.N = P / 4; g1.K = C / 8;
-        g1.lda = C / 8; g1.ldb = C / 8; g1.ldc = P / 4;
-        g1.stride_a = (int64_t)P * (C / 8); g1.stride_b = (int64_t)(P / 4) * (C / 8);
-        g1.stride_c = (int64_t)P * (P / 4);
-        g1.a_kmajor = 0; g1.b_kmajor = 0; g1.alpha = 1.f; g1.accumulate = 0;
-        RET_IF(p2l_gemm_ws(&g1, W + L.att_theta, W + L.att_phi_p, W + L.att_P, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P, P / 4, C / 8, 0, 0, W + L.att_theta, W + L.att_phi_p, W + L.att_P));
         RET_IF(p2l_softmax_fwd(W + L.att_P, W + L.att_P, (int64_t)B * P, P / 4, st));
         // attn_g[p, :] = sum_k P[p,k] g[k, :]
-        P2LGemm g2{};
-        g2.batch = B; g2.M = P; g2.N = C / 2; g2.K = P / 4;
-        g2.lda = P / 4; g2.ldb = C / 2; g2.ldc = C / 2;
-        g2.stride_a = (int64_t)P * (P / 4); g2.stride_b = (int64_t)(P / 4) * (C / 2);
-        g2.stride_c = (int64_t)P * (C / 2);
-        g2.a_kmajor = 0; g2.b_kmajor = 1; g2.alpha = 1.f; g2.accumulate = 0;
-        RET_IF(p2l_gemm_ws(&g2, W + L.att_P, W + L.att_g_p, W + L.att_ag, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P, C / 2, P / 4, 0, 1, W + L.att_P, W + L.att_g_p, W + L.att_ag));
       }
-      ConvCall oc = mk_conv(B, H, H, C / 2, C, 1);
+      ConvCall oc = run.mk_conv(B, H, H, C / 2, C, 1);
       oc.x = W + L.att_ag; oc.w = m->att_w[3]; oc.y = W + L.att_y;
       oc.d.alpha = m->gamma; oc.res = x; oc.d.res_ld = C;
       oc.want_amax = true;                             // (read by this block's conv_0 through cbn_0)
       oc.next_ps = W + L.s + m->blocks[i].cbn_off[0]; oc.next_pt = W + L.t + m->blocks[i].cbn_off[0]; oc.next_bstride = CT;
-      RET_IF(run_conv(oc, skws, L.skws_floats, st));
+      RET_IF(run.run_conv(oc));
       x = W + L.att_y;
     }
     const P2LGenBlock& g = m->blocks[i];
@@ -638,73 +657,64 @@ extern "C" int p2l_biggan_fwd(const P2LBigGAN* m, const float* z, const float* c
     if (g.cin != Cx) return P2L_EINVAL;
     const int mid = g.cin / 4;
     // conv_0 : relu(cbn_0(x)) 1x1 cin -> mid
-    ConvCall c0 = mk_conv(B, o.H, o.H, g.cin, mid, 1);
+    ConvCall c0 = run.mk_conv(B, o.H, o.H, g.cin, mid, 1);
     c0.x = x; c0.w = g.w[0]; c0.bias = g.b[0]; c0.y = W + o.h1;
-    c0.d.pro = P2L_PRO_AFFINE_RELU; c0.d.pro_bstride = CT;
-    c0.ps = W + L.s + g.cbn_off[0]; c0.pt = W + L.t + g.cbn_off[0];
-    c0.want_amax = true;                               // (conv_1: Winograd / sub-pixel / direct, all fp16 x 2)
-    c0.next_ps = W + L.s + g.cbn_off[1]; c0.next_pt = W + L.t + g.cbn_off[1]; c0.next_bstride = CT;
-    RET_IF(run_conv(c0, skws, L.skws_floats, st));
+    cbn(c0, g, 0, &g, 1);                              // (conv_1: Winograd / sub-pixel / direct, all fp16 x 2)
+    RET_IF(run.run_conv(c0));
     // conv_1 : relu(cbn_1) -> (nearest x2) -> 3x3
-    ConvCall c1 = mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
+    ConvCall c1 = run.mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
     c1.x = W + o.h1; c1.w = g.w[1]; c1.bias = g.b[1]; c1.y = W + o.h2; c1.d.ups = g.up;
     // sub-pixel form from 16^2 inputs up (8^2 / 4^2 inputs measured: no gain at 18 candidates, -1 ... 2 % at 2-3)
     if (g.up && g.w1_sp && o.H >= 16) { c1.d.ups = 2; c1.w = g.w1_sp; }
-    c1.d.pro = P2L_PRO_AFFINE_RELU; c1.d.pro_bstride = CT;
-    c1.ps = W + L.s + g.cbn_off[1]; c1.pt = W + L.t + g.cbn_off[1];
-    c1.want_amax = true;
-    c1.next_ps = W + L.s + g.cbn_off[2]; c1.next_pt = W + L.t + g.cbn_off[2]; c1.next_bstride = CT;
-    RET_IF(run_conv(c1, skws, L.skws_floats, st));
-    ConvCall c2 = mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
+    cbn(c1, g, 1, &g, 2);
+    RET_IF(run.run_conv(c1));
+    ConvCall c2 = run.mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
     c2.x = W + o.h2; c2.w = g.w[2]; c2.bias = g.b[2]; c2.y = W + o.h3;
-    c2.d.pro = P2L_PRO_AFFINE_RELU; c2.d.pro_bstride = CT;
-    c2.ps = W + L.s + g.cbn_off[2]; c2.pt = W + L.t + g.cbn_off[2];
-    c2.want_amax = true;                               // (conv_3 is a pointwise conv: fp16 x 2 with the maxima)
-    c2.next_ps = W + L.s + g.cbn_off[3]; c2.next_pt = W + L.t + g.cbn_off[3]; c2.next_bstride = CT;
-    RET_IF(run_conv(c2, skws, L.skws_floats, st));
+    cbn(c2, g, 2, &g, 3);                              // (conv_3 is a pointwise conv: fp16 x 2 with the maxima)
+    RET_IF(run.run_conv(c2));
     // conv_3 : 1x1 mid -> cout, + shortcut (channel-truncated, nearest x2)
-    ConvCall c3 = mk_conv(B, o.Ho, o.Ho, mid, g.cout, 1);
+    ConvCall c3 = run.mk_conv(B, o.Ho, o.Ho, mid, g.cout, 1);
     c3.x = W + o.h3; c3.w = g.w[3]; c3.bias = g.b[3]; c3.y = W + o.y;
-    c3.d.pro = P2L_PRO_AFFINE_RELU; c3.d.pro_bstride = CT;
-    c3.ps = W + L.s + g.cbn_off[3]; c3.pt = W + L.t + g.cbn_off[3];
     c3.res = x; c3.d.res_ld = g.cin; c3.d.res_ups = g.up;
-    c3.want_amax = true;                               // (the next block's conv_0; the attention convs read it raw)
-    if (i + 1 < m->n_blocks && i + 1 != m->attn_before) {
-      c3.next_ps = W + L.s + m->blocks[i + 1].cbn_off[0]; c3.next_pt = W + L.t + m->blocks[i + 1].cbn_off[0];
-      c3.next_bstride = CT;
-    }
-    RET_IF(run_conv(c3, skws, L.skws_floats, st));
+    // (the next block's conv_0; the attention convs read it raw)
+    cbn(c3, g, 3, (i + 1 < m->n_blocks && i + 1 != m->attn_before) ? &m->blocks[i + 1] : nullptr, 0);
+    RET_IF(run.run_conv(c3));
     x = W + o.y;
     Cx = g.cout;
   }
   if (Cx != m->ch) return P2L_EINVAL;
   // tail: relu(bn(x)) -> conv_to_rgb (3 of ch outputs) -> tanh, NHWC16
-  ConvCall rc = mk_conv(B, L.out_res, L.out_res, m->ch, 32, 9);
+  ConvCall rc = run.mk_conv(B, L.out_res, L.out_res, m->ch, 32, 9);
   rc.x = x; rc.w = m->rgb_w; rc.bias = m->rgb_b; rc.y = img16;
   rc.d.pro = P2L_PRO_AFFINE_RELU; rc.d.pro_bstride = 0; rc.ps = m->tail_s; rc.pt = m->tail_t;
   rc.d.act = P2L_ACT_TANH; rc.d.y_ld = 16; rc.d.n_store = 16;
   rc.d.algo_flops = 2.0 * B * L.out_res * L.out_res * (double)m->ch * 3 * 9;
-  if (g_plan_wfmt & P2L_WFMT_FLAG_THIN) rc.d.wfmt = P2L_WFMT_BF16X3T;
-  RET_IF(run_conv(rc, skws, L.skws_floats, st));
+  if (run.wfmt & P2L_WFMT_FLAG_THIN) rc.d.wfmt = P2L_WFMT_BF16X3T;
+  RET_IF(run.run_conv(rc));
   return P2L_OK;
 }
 
 extern "C" int p2l_biggan_bwd(const P2LBigGAN* m, int B, void* ws, size_t ws_bytes,
                               const float* img16, float* dimg16, float* dz, float* dc,
                               void* st) {
-  g_plan_wfmt = m ? m->wfmt : P2L_WFMT_F32;
+  int form = 0;
 #if defined(P2L_AB_BWD_BF3) || defined(P2L_AB_BWD_BF3_BG)
-  struct FormScope { FormScope() { g_plan_form = P2L_FORM_WINO_BF3; } ~FormScope() { g_plan_form = 0; } } form_scope;
+  form = P2L_FORM_WINO_BF3;
 #endif
   BGLayout L;
-  RET_IF(bg_layout(m, B, L));
+  RET_IF(bg_layout(m, B, L, form));
   if (!ws || ws_bytes < L.total * sizeof(float) || !img16 || !dimg16 || !dz || !dc)
     return P2L_EWS;
   float* W = (float*)ws;
   const int cond = m->z_dim + m->c_dim, CT = m->cbn_total;
-  float* skws = W + L.skws;
   float* part = W + L.arb_partial;
-  AmaxScope amax_scope(W + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  PlanRun run(m->wfmt, form, W + L.skws, L.skws_floats, st);
+  run.amax_begin(W + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  // backward of relu(cbn_k(x)) of GenBlock g, x [.., C]: ds / dt go to the CBN's columns
+  auto cbn_arb = [&](const P2LGenBlock& g, int k, const float* x, int C) {
+    return ArbArgs{x, C, W + L.s + g.cbn_off[k], W + L.t + g.cbn_off[k], CT, nullptr, 0, 0, 0,
+                   W + L.ds + g.cbn_off[k], W + L.dt + g.cbn_off[k], CT};
+  };
   // ds / dt of the ~50 activation-backwards are only needed by the conditioning gradient at
   // the very end: record their second reduction stage and run it as ONE launch
   struct ArbDefer {
@@ -720,16 +730,16 @@ extern "C" int p2l_biggan_bwd(const P2LBigGAN* m, int B, void* ws, size_t ws_byt
   RET_IF(p2l_tanh_bwd16(img16, dimg16, (int64_t)B * R * R, st));
   {
     // conv_to_rgb input-gradient fused with the unconditional BN+ReLU backward.
-    ConvCall c = mk_conv(B, R, R, 16, m->ch, 9);
+    ConvCall c = run.mk_conv(B, R, R, 16, m->ch, 9);
     c.x = dimg16; c.w = m->rgb_wt;
     c.d.algo_flops = 2.0 * B * R * R * (double)m->ch * 3 * 9;
-    if (g_plan_wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
+    if (run.wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
     const float* xlast = W + L.blk[m->n_blocks - 1].y;
     // ds/dt of the tail BN feed nothing (no conditioning): park them in `draw`.
     ArbArgs a{xlast, m->ch, m->tail_s, m->tail_t, 0, nullptr, 0, 0, 0, W + L.draw,
               W + L.draw + (size_t)B * m->ch, m->ch};
     c.want_amax = true;                                  // (conv_3's input gradient of the last block reads ga)
-    RET_IF(run_dgrad_arb(c, a, ga, gd, part, skws, L.skws_floats, st));
+    RET_IF(run.run_dgrad_arb(c, a, ga, gd, part));
     part += L.tail_pf;
   }
   for (int i = m->n_blocks - 1; i >= 0; --i) {
@@ -743,39 +753,32 @@ extern "C" int p2l_biggan_bwd(const P2LBigGAN* m, int B, void* ws, size_t ws_byt
 
     // ga = dy (kept for the shortcut), gb / gc alternate, gd = temp of the unfused path
     // conv_3 input-gradient: dy[cout] -> [mid], + relu(cbn_3) backward
-    ConvCall d3 = mk_conv(B, o.Ho, o.Ho, g.cout, mid, 1);
+    ConvCall d3 = run.mk_conv(B, o.Ho, o.Ho, g.cout, mid, 1);
     d3.x = ga; d3.w = g.wt[3];
-    ArbArgs a3{W + o.h3, mid, W + L.s + g.cbn_off[3], W + L.t + g.cbn_off[3], CT, nullptr, 0,
-               0, 0, W + L.ds + g.cbn_off[3], W + L.dt + g.cbn_off[3], CT};
     d3.want_amax = true;
-    RET_IF(run_dgrad_arb(d3, a3, gb, gd, part, skws, L.skws_floats, st));
+    RET_IF(run.run_dgrad_arb(d3, cbn_arb(g, 3, W + o.h3, mid), gb, gd, part));
     part += o.pf;
     // conv_2
-    ConvCall d2 = mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
+    ConvCall d2 = run.mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
     d2.x = gb; d2.w = g.wt[2];
-    ArbArgs a2{W + o.h2, mid, W + L.s + g.cbn_off[2], W + L.t + g.cbn_off[2], CT, nullptr, 0,
-               0, 0, W + L.ds + g.cbn_off[2], W + L.dt + g.cbn_off[2], CT};
     d2.want_amax = true;
-    RET_IF(run_dgrad_arb(d2, a2, gc, gd, part, skws, L.skws_floats, st));
+    RET_IF(run.run_dgrad_arb(d2, cbn_arb(g, 2, W + o.h2, mid), gc, gd, part));
     part += o.pf;
     // conv_1 (+ nearest-x2 backward = 2x2 sum pool fused in the epilogue)
-    ConvCall d1 = mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
+    ConvCall d1 = run.mk_conv(B, o.Ho, o.Ho, mid, mid, 9);
     d1.x = gc; d1.w = g.wt[1];
     if (g.up && g.wt1_sp && o.H >= 32) { d1.d.ups = 3; d1.w = g.wt1_sp; }   // sub-pixel form
     else if (g.up) d1.d.pool = P2L_POOL_SUM;
-    ArbArgs a1{W + o.h1, mid, W + L.s + g.cbn_off[1], W + L.t + g.cbn_off[1], CT, nullptr, 0,
-               0, 0, W + L.ds + g.cbn_off[1], W + L.dt + g.cbn_off[1], CT};
     d1.want_amax = true;
-    RET_IF(run_dgrad_arb(d1, a1, gb, gd, part, skws, L.skws_floats, st));
+    RET_IF(run.run_dgrad_arb(d1, cbn_arb(g, 1, W + o.h1, mid), gb, gd, part));
     part += o.pf;
     // conv_0, + relu(cbn_0) backward + shortcut gradient from dy (= ga)
-    ConvCall d0 = mk_conv(B, o.H, o.H, mid, g.cin, 1);
+    ConvCall d0 = run.mk_conv(B, o.H, o.H, mid, g.cin, 1);
     d0.x = gb; d0.w = g.wt[0];
-    const int skipC = (g.cin != g.cout) ? g.cin / 2 : g.cin;
-    ArbArgs a0{xin, g.cin, W + L.s + g.cbn_off[0], W + L.t + g.cbn_off[0], CT, ga, g.cout,
-               skipC, g.up, W + L.ds + g.cbn_off[0], W + L.dt + g.cbn_off[0], CT};
+    ArbArgs a0 = cbn_arb(g, 0, xin, g.cin);
+    a0.skip = ga; a0.skip_ld = g.cout; a0.skip_C = (g.cin != g.cout) ? g.cin / 2 : g.cin; a0.skip_ups = g.up;
     d0.want_amax = true;
-    RET_IF(run_dgrad_arb(d0, a0, gc, gd, part, skws, L.skws_floats, st));
+    RET_IF(run.run_dgrad_arb(d0, a0, gc, gd, part));
     part += o.pf;
     { float* tmp = ga; ga = gc; gc = tmp; }
 
@@ -783,14 +786,14 @@ extern "C" int p2l_biggan_bwd(const P2LBigGAN* m, int B, void* ws, size_t ws_byt
       // ---- SelfAttn backward; ga = d out [B,H,H,C] ------------------------
       // (gb becomes a scratch matrix of the attention kernels: ITS maxima die.  Until round 5 every entry was
       //  cleared here, the incoming gradient's too, and the o_conv gradient below ran in bf16 x 3 for want of them)
-      amax_drop(gb);
+      run.amax_drop(gb);
       const int C = m->attn_ch, H = L.att_H, P = H * H;
       const float* x = (i == 0) ? W + L.x0 : W + L.blk[i - 1].y;
       (void)x;
       // d attn_g = gamma * dgrad(o_conv)(dy)
-      ConvCall dob = mk_conv(B, H, H, C, C / 2, 1);
+      ConvCall dob = run.mk_conv(B, H, H, C, C / 2, 1);
       dob.x = ga; dob.w = m->att_wt[3]; dob.y = W + L.d_ag; dob.d.alpha = m->gamma;
-      RET_IF(run_conv(dob, skws, L.skws_floats, st));
+      RET_IF(run.run_conv(dob));
       if (L.att_fused) {
         // d g_p = P^T d_ag with P recomputed from lse; then d theta, d phi_p: P and dP are
         // recomputed tile by tile, dS^T goes once through the scratch buffer gb
@@ -802,66 +805,37 @@ extern "C" int p2l_biggan_bwd(const P2LBigGAN* m, int B, void* ws, size_t ws_byt
                                W + L.att_ws, L.att_ws_floats * sizeof(float), st));
       } else {
       // dP[p,k] = sum_c d_ag[p,c] g_p[k,c]
-        P2LGemm q1{};
-        q1.batch = B; q1.M = P; q1.N = P / 4; q1.K = C / 2;
-        q1.lda = C / 2; q1.ldb = C / 2; q1.ldc = P / 4;
-        q1.stride_a = (int64_t)P * (C / 2); q1.stride_b = (int64_t)(P / 4) * (C / 2);
-        q1.stride_c = (int64_t)P * (P / 4);
-        q1.alpha = 1.f;
-        RET_IF(p2l_gemm_ws(&q1, W + L.d_ag, W + L.att_g_p, gb, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P, P / 4, C / 2, 0, 0, W + L.d_ag, W + L.att_g_p, gb));
         // d g_p[k,c] = sum_p P[p,k] d_ag[p,c]
-        P2LGemm q2{};
-        q2.batch = B; q2.M = P / 4; q2.N = C / 2; q2.K = P;
-        q2.lda = P / 4; q2.ldb = C / 2; q2.ldc = C / 2;
-        q2.stride_a = (int64_t)P * (P / 4); q2.stride_b = (int64_t)P * (C / 2);
-        q2.stride_c = (int64_t)(P / 4) * (C / 2);
-        q2.a_kmajor = 1; q2.b_kmajor = 1; q2.alpha = 1.f;
-        RET_IF(p2l_gemm_ws(&q2, W + L.att_P, W + L.d_ag, W + L.d_g_p, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P / 4, C / 2, P, 1, 1, W + L.att_P, W + L.d_ag, W + L.d_g_p));
         // dS = softmax backward (in place in gb)
         RET_IF(p2l_softmax_bwd(W + L.att_P, gb, gb, (int64_t)B * P, P / 4, st));
         // d theta[p,d] = sum_k dS[p,k] phi_p[k,d]
-        P2LGemm q3{};
-        q3.batch = B; q3.M = P; q3.N = C / 8; q3.K = P / 4;
-        q3.lda = P / 4; q3.ldb = C / 8; q3.ldc = C / 8;
-        q3.stride_a = (int64_t)P * (P / 4); q3.stride_b = (int64_t)(P / 4) * (C / 8);
-        q3.stride_c = (int64_t)P * (C / 8);
-        q3.b_kmajor = 1; q3.alpha = 1.f;
-        RET_IF(p2l_gemm_ws(&q3, gb, W + L.att_phi_p, W + L.d_theta, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P, C / 8, P / 4, 0, 1, gb, W + L.att_phi_p, W + L.d_theta));
         // d phi_p[k,d] = sum_p dS[p,k] theta[p,d]
-        P2LGemm q4{};
-        q4.batch = B; q4.M = P / 4; q4.N = C / 8; q4.K = P;
-        q4.lda = P / 4; q4.ldb = C / 8; q4.ldc = C / 8;
-        q4.stride_a = (int64_t)P * (P / 4); q4.stride_b = (int64_t)P * (C / 8);
-        q4.stride_c = (int64_t)(P / 4) * (C / 8);
-        q4.a_kmajor = 1; q4.b_kmajor = 1; q4.alpha = 1.f;
-        RET_IF(p2l_gemm_ws(&q4, gb, W + L.att_theta, W + L.d_phi_p, skws, L.skws_floats * sizeof(float), st));
+        RET_IF(run.dense_gemm(B, P / 4, C / 8, P, 1, 1, gb, W + L.att_theta, W + L.d_phi_p));
       }
       // max-pool backward for phi and g
       // (the max-pool backward leaves the maxima of what it writes for the 1x1 convs t2 / t3 below,
       //  which take the fp16 x 2 form with them)
       auto pool_bwd = [&](const float* y, const float* dyp, float* dy, int Cc) -> int {
-        float* so = nullptr;
-        int set_o = -1;
-        const int ns = p2l_maxpool2_bwd_amax_slots(H, H, Cc);
-        amax_drop(dy);
-        if (g_amax && ns > 0 && (size_t)ns * B <= g_amax->set_floats) so = g_amax->take(&set_o);
-        RET_IF(p2l_maxpool2_bwd_amax(y, Cc, dyp, Cc, nullptr, 0, dy, Cc, B, H, H, Cc, 0, so, st));
-        if (so) g_amax->put(dy, B, H, H, Cc, so, ns, set_o);
-        return P2L_OK;
+        return run.amax_writer(dy, B, H, H, Cc, p2l_maxpool2_bwd_amax_slots(H, H, Cc), [&](float* so) {
+          return p2l_maxpool2_bwd_amax(y, Cc, dyp, Cc, nullptr, 0, dy, Cc, B, H, H, Cc, 0, so, st);
+        });
       };
       RET_IF(pool_bwd(W + L.att_phi, W + L.d_phi_p, W + L.d_phi, C / 8));
       RET_IF(pool_bwd(W + L.att_g, W + L.d_g_p, W + L.d_g, C / 2));
       // dx = dy + theta^T-grad + phi-grad + g-grad (chained residual, in place)
-      ConvCall t1 = mk_conv(B, H, H, C / 8, C, 1);
+      ConvCall t1 = run.mk_conv(B, H, H, C / 8, C, 1);
       t1.x = W + L.d_theta; t1.w = m->att_wt[0]; t1.y = ga; t1.res = ga; t1.d.res_ld = C;
-      RET_IF(run_conv(t1, skws, L.skws_floats, st));
-      ConvCall t2 = mk_conv(B, H, H, C / 8, C, 1);
+      RET_IF(run.run_conv(t1));
+      ConvCall t2 = run.mk_conv(B, H, H, C / 8, C, 1);
       t2.x = W + L.d_phi; t2.w = m->att_wt[1]; t2.y = ga; t2.res = ga; t2.d.res_ld = C;
-      RET_IF(run_conv(t2, skws, L.skws_floats, st));
-      ConvCall t3 = mk_conv(B, H, H, C / 2, C, 1);
+      RET_IF(run.run_conv(t2));
+      ConvCall t3 = run.mk_conv(B, H, H, C / 2, C, 1);
       t3.x = W + L.d_g; t3.w = m->att_wt[2]; t3.y = ga; t3.res = ga; t3.d.res_ld = C;
       t3.want_amax = true;                               // (ga feeds the next block's conv_3 input gradient)
-      RET_IF(run_conv(t3, skws, L.skws_floats, st));
+      RET_IF(run.run_conv(t3));
     }
   }
   // ga = d gen_z output [B, 16*16*ch]; conditioning gradients
@@ -906,8 +880,11 @@ void vgg_taps(int H, int W, LossTaps& T) {
   }
 }
 
-int pl_layout(int B, int H, int W, PLLayout& L) {
+// wfmt: the format to lay out for (a descriptor's, or the caller's choice where there is none); only the
+// split-K workspace and the maxima ring behind it, the last two regions, depend on it
+int pl_layout(int wfmt, int B, int H, int W, PLLayout& L, int form = 0) {
   if (B < 1 || H < 32 || W < 32 || !is_pow2(H) || !is_pow2(W)) return P2L_EINVAL;
+  const PlanRun run(wfmt, form);
   Arena a;
   size_t max_act = 0, max_sk = 0;
   int pi = 0, max_slots = 0;
@@ -917,15 +894,8 @@ int pl_layout(int B, int H, int W, PLLayout& L) {
     L.y[i] = a.take(n);
     if (n > max_act) max_act = n;
     if (vgg_pool_after(i)) L.yp[pi++] = a.take(n / 4);
-    ConvCall f = mk_conv(B, h, w, kVggCin[i], kVggCout[i], 9);
-    size_t s1 = conv_ws_floats(f);
-    ConvCall d = mk_conv(B, h, w, kVggCout[i], i == 0 ? 32 : kVggCin[i], 9);
-    size_t s2 = conv_ws_floats(d);
-    if (s1 > max_sk) max_sk = s1;
-    if (s2 > max_sk) max_sk = s2;
-    const int n1 = conv_amax_slots(f), n2 = conv_amax_slots(d);
-    if (n1 > max_slots) max_slots = n1;
-    if (n2 > max_slots) max_slots = n2;
+    conv_sizes(run.mk_conv(B, h, w, kVggCin[i], kVggCout[i], 9), max_sk, max_slots);               // forward
+    conv_sizes(run.mk_conv(B, h, w, kVggCout[i], i == 0 ? 32 : kVggCin[i], 9), max_sk, max_slots);  // input gradient
     if (vgg_pool_after(i) && i >= 1) {
       const int n3 = p2l_maxpool2_bwd_amax_slots(h, w, kVggCout[i]);
       if (n3 > max_slots) max_slots = n3;
@@ -948,24 +918,25 @@ int pl_layout(int B, int H, int W, PLLayout& L) {
 // VGG16 features forward on an NHWC16 image; y[i] = relu(conv_i), pooled copies.
 int vgg_forward(const P2LVggLpips* v, const float* img16, int B, int H, int W, float* Wk,
                 const PLLayout& L, void* st) {
-  AmaxScope amax_scope(Wk + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  PlanRun run(v->wfmt, 0, Wk + L.skws, L.skws_floats, st);
+  run.amax_begin(Wk + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
   const float* x = img16;
   int pi = 0;
   for (int i = 0; i < 13; ++i) {
     const int h = H / kVggDiv[i], w = W / kVggDiv[i];
-    ConvCall c = mk_conv(B, h, w, kVggCin[i], kVggCout[i], 9);
+    ConvCall c = run.mk_conv(B, h, w, kVggCin[i], kVggCout[i], 9);
     c.x = x; c.w = v->w[i]; c.bias = v->b[i]; c.y = Wk + L.y[i];
     c.d.act = P2L_ACT_RELU;
     if (i == 0) {
       c.d.pro = P2L_PRO_AFFINE; c.d.pro_bstride = 0; c.ps = v->in_s; c.pt = v->in_t;
       c.d.algo_flops = 2.0 * B * h * w * 3.0 * kVggCout[0] * 9;
-      if (g_plan_wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
+      if (run.wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
     }
     if (vgg_pool_after(i)) {
       c.d.pool = P2L_POOL_MAX; c.yp = Wk + L.yp[pi];
     }
     c.want_amax = i < 12;
-    RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
+    RET_IF(run.run_conv(c));
     if (vgg_pool_after(i)) { x = Wk + L.yp[pi]; ++pi; }
     else x = Wk + L.y[i];
   }
@@ -986,7 +957,7 @@ extern "C" int p2l_projloss_ws_lookup(int B, int H, int W, int idx, size_t* floa
                                       int32_t shape[4]) {
   if (idx < 0 || idx >= 13 || !float_off || !shape) return P2L_EINVAL;
   PLLayout L;
-  RET_IF(pl_layout(B, H, W, L));
+  RET_IF(pl_layout(P2L_WFMT_F32, B, H, W, L));         // (the conv outputs lie in front of what follows the format)
   *float_off = L.y[idx];
   shape[0] = B; shape[1] = H / kVggDiv[idx]; shape[2] = W / kVggDiv[idx]; shape[3] = kVggCout[idx];
   return P2L_OK;
@@ -998,12 +969,10 @@ extern "C" size_t p2l_projloss_ws_bytes(int B, int H, int W) {
   // K by the grid size, the Winograd format slices its small-grid layers by their shape
   size_t total = 0;
   for (int fmt : {(int)P2L_WFMT_F32, (int)P2L_WFMT_BF16X3W, (int)P2L_WFMT_BF16X3}) {
-    g_plan_wfmt = fmt;
     PLLayout L;
-    if (pl_layout(B, H, W, L)) return 0;
+    if (pl_layout(fmt, B, H, W, L)) return 0;
     if (L.total > total) total = L.total;
   }
-  g_plan_wfmt = P2L_WFMT_F32;
   return total * sizeof(float);
 }
 
@@ -1011,9 +980,8 @@ extern "C" int p2l_projloss_prepare(const P2LVggLpips* v, const float* target,
                                     const float* weight, const float* loss_mask, int B,
                                     int H, int W, const P2LLossCache* cache, void* ws,
                                     size_t ws_bytes, void* st) {
-  g_plan_wfmt = v ? v->wfmt : P2L_WFMT_F32;
   PLLayout L;
-  RET_IF(pl_layout(B, H, W, L));
+  RET_IF(pl_layout(v ? v->wfmt : P2L_WFMT_F32, B, H, W, L));
   L.taps.bind(v, cache);
   return loss_prepare(L, target, weight, loss_mask, B, H, W, ws, ws_bytes, st,
                       [&](const float* x) { return vgg_forward(v, x, B, H, W, (float*)ws, L, st); });
@@ -1025,9 +993,8 @@ extern "C" int p2l_projloss_fwd(const P2LVggLpips* v, const float* img16,
                                 float beta, int use_lpips, int B, int H, int W, void* ws,
                                 size_t ws_bytes, float* loss, float* loss_l1,
                                 float* loss_lpips, void* st) {
-  g_plan_wfmt = v ? v->wfmt : P2L_WFMT_F32;
   PLLayout L;
-  RET_IF(pl_layout(B, H, W, L));
+  RET_IF(pl_layout(v ? v->wfmt : P2L_WFMT_F32, B, H, W, L));
   L.taps.bind(v, cache);
   return loss_fwd(L, img16, target, weight, loss_mask, beta, use_lpips, B, H, W, ws, ws_bytes, loss, loss_l1,
                   loss_lpips, st, [&](const float* x) { return vgg_forward(v, x, B, H, W, (float*)ws, L, st); });
@@ -1038,12 +1005,13 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
                                 const float* loss_mask, const P2LLossCache* cache,
                                 float beta, int use_lpips, const float* gloss, int B, int H,
                                 int W, void* ws, size_t ws_bytes, float* dimg16, void* st) {
-  g_plan_wfmt = v ? v->wfmt : P2L_WFMT_F32;
+  const int wfmt = v ? v->wfmt : P2L_WFMT_F32;
+  int form = 0;
 #if defined(P2L_AB_BWD_BF3) || defined(P2L_AB_BWD_BF3_PL)
-  struct FormScope { FormScope() { g_plan_form = P2L_FORM_WINO_BF3; } ~FormScope() { g_plan_form = 0; } } form_scope;
+  form = P2L_FORM_WINO_BF3;
 #endif
   PLLayout L;
-  RET_IF(pl_layout(B, H, W, L));
+  RET_IF(pl_layout(wfmt, B, H, W, L, form));
   L.taps.bind(v, cache);
   LossBwd bw;
   RET_IF(loss_bwd_begin(L, img16, target, weight, loss_mask, beta, use_lpips, gloss, B, H, W, ws, ws_bytes, dimg16,
@@ -1051,7 +1019,8 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
   if (bw.done) return P2L_OK;
   float* Wk = (float*)ws;
   const LossTaps& T = L.taps;
-  AmaxScope amax_scope(Wk + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
+  PlanRun run(wfmt, form, Wk + L.skws, L.skws_floats, st);
+  run.amax_begin(Wk + L.amax_ring, L.amax_set_floats, L.amax_set_stride);
   float *ga = bw.ga, *gb = bw.gb;
   // top: relu5_3 is only consumed by the LPIPS tap
   RET_IF(bw.tap(4));
@@ -1060,36 +1029,33 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
   for (int i = 12; i >= 1; --i) {
     const int h = H / kVggDiv[i], w = W / kVggDiv[i];
     // input-gradient of conv i: ga [h,w,Cout_i] -> [h,w,Cin_i]
-    ConvCall c = mk_conv(B, h, w, kVggCout[i], kVggCin[i], 9);
+    ConvCall c = run.mk_conv(B, h, w, kVggCout[i], kVggCin[i], 9);
     c.x = ga; c.w = v->wt[i]; c.y = gb;
     const int prev = i - 1;
     if (!vgg_pool_after(prev)) {
       // input is relu(conv_{i-1}) directly: fuse its ReLU mask in the epilogue
       c.mask = Wk + L.y[prev]; c.d.mask_ld = kVggCout[prev];
       c.want_amax = i > 1;
-      RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
+      RET_IF(run.run_conv(c));
     } else {
       // input is maxpool(relu(conv_{i-1})); conv_{i-1} is also an LPIPS tap
-      RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
+      RET_IF(run.run_conv(c));
       const int k = vgg_tap_of(prev);
       const int hp = T.h[k], wp = T.w[k], P = T.P(k), C = T.C[k];
       // (written by a non-conv kernel, which leaves its own maxima for the dgrad that reads ga next)
-      amax_drop(ga);
-      float* so = nullptr;
-      int set_o = -1;
 #ifdef P2L_AB_TAP_POOL_2PASS      // A/B builds: the two-pass form of rounds 1-4
+      run.amax_drop(ga);            // (in front of the tap kernels, as it always was)
       RET_IF(bw.tap(k));
-      const int ns = p2l_maxpool2_bwd_amax_slots(hp, wp, C);
-      if (g_amax && prev >= 1 && ns > 0 && (size_t)ns * B <= g_amax->set_floats) so = g_amax->take(&set_o);
-      RET_IF(p2l_maxpool2_bwd_amax(Wk + L.y[prev], C, gb, C, bw.gtap, C, ga, C, B, hp, wp, C, 1, so, st));
+      RET_IF(run.amax_writer(ga, B, hp, wp, C, prev >= 1 ? p2l_maxpool2_bwd_amax_slots(hp, wp, C) : 0, [&](float* so) {
+        return p2l_maxpool2_bwd_amax(Wk + L.y[prev], C, gb, C, bw.gtap, C, ga, C, B, hp, wp, C, 1, so, st);
+      }));
 #else
       // tap gradient + pool backward of gb + ReLU mask in one pass over conv_{i-1}'s output
-      const int ns = p2l_lpips_tap_nblk(P, C);
-      if (g_amax && prev >= 1 && ns > 0 && (size_t)ns * B <= g_amax->set_floats) so = g_amax->take(&set_o);
-      RET_IF(p2l_lpips_tap_pool_bwd(Wk + T.y[k], T.nft[k], (int64_t)P * C, T.lin[k], T.wt[k], P, Wk + L.tail.gs, gb,
-                                    ga, so, B, hp, wp, C, st));
+      RET_IF(run.amax_writer(ga, B, hp, wp, C, prev >= 1 ? p2l_lpips_tap_nblk(P, C) : 0, [&](float* so) {
+        return p2l_lpips_tap_pool_bwd(Wk + T.y[k], T.nft[k], (int64_t)P * C, T.lin[k], T.wt[k], P, Wk + L.tail.gs, gb,
+                                      ga, so, B, hp, wp, C, st);
+      }));
 #endif
-      if (so) g_amax->put(ga, B, hp, wp, C, so, ns, set_o);
       --pi;
       continue;  // ga already holds the masked gradient of conv_{i-1}
     }
@@ -1098,11 +1064,11 @@ extern "C" int p2l_projloss_bwd(const P2LVggLpips* v, const float* img16,
   (void)pi;
   // conv 0 input-gradient -> d img16 (1/scale folded into the packed weights)
   {
-    ConvCall c = mk_conv(B, H, W, 64, 32, 9);
+    ConvCall c = run.mk_conv(B, H, W, 64, 32, 9);
     c.x = ga; c.w = v->wt[0]; c.y = dimg16; c.d.y_ld = 16; c.d.n_store = 16;
     c.d.algo_flops = 2.0 * B * H * W * 3.0 * 64 * 9;
-    if (g_plan_wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
-    RET_IF(run_conv(c, Wk + L.skws, L.skws_floats, st));
+    if (run.wfmt & P2L_WFMT_FLAG_THIN) c.d.wfmt = P2L_WFMT_BF16X3T;
+    RET_IF(run.run_conv(c));
   }
   return loss_bwd_end(bw);
 }

@@ -38,11 +38,10 @@ struct SgLayout {
 };
 constexpr int kAmaxCompactFrom = 4096;
 
-thread_local int g_sg_wfmt = P2L_WFMT_F32;   // the model's weight format: set by sg_layout
-
-P2LConv mk(int B, int H, int Cin, int Cout, int taps) {
+// wfmt: the model descriptor's (the format of its 3x3 convs | flags)
+P2LConv mk(int wfmt, int B, int H, int Cin, int Cout, int taps) {
   P2LConv d{};
-  d.wfmt = (taps == 9) ? (g_sg_wfmt & 0xF) : P2L_WFMT_F32;
+  d.wfmt = (taps == 9) ? (wfmt & 0xF) : P2L_WFMT_F32;
   d.B = B; d.H = H; d.W = H; d.Cin = Cin; d.Cout = Cout; d.taps = taps;
   d.x_ld = Cin; d.alpha = 1.f; d.y_ld = Cout; d.yp_ld = Cout; d.n_store = Cout; d.splitk = 1;
   return d;
@@ -62,7 +61,6 @@ void suggest_split(P2LConv& d, size_t ws_floats_have) {
 int sg_layout(const P2LStyleGAN2* m, int B, SgLayout& L) {
   if (!m || B < 1 || m->n_conv < 1 || m->n_conv > P2L_SG2_MAX_CONVS || m->n_rgb > P2L_SG2_MAX_RGBS)
     return P2L_EINVAL;
-  g_sg_wfmt = m->wfmt;
   Arena a;
   size_t max_act = 0, max_u = 0, max_c = 0, max_strips = 0;
   size_t max_cws = (size_t)B * 64;
@@ -85,19 +83,19 @@ int sg_layout(const P2LStyleGAN2* m, int B, SgLayout& L) {
     if (!c.up) {
       // K-sliced forms of the stride-1 layers: slices behind the 256 B of maxima per image, one partial of the
       // fused modulation backward per 2x2 quad
-      P2LConv f = mk(B, c.res, c.cin, c.cout, 9);
+      P2LConv f = mk(m->wfmt, B, c.res, c.cin, c.cout, 9);
       f.pro = P2L_PRO_AFFINE; f.pro_bstride = c.cin;
       suggest_split(f, 0);
       size_t w = p2l_conv_workspace_bytes(&f) / sizeof(float);
       if (w > max_cws) max_cws = w;
-      P2LConv g = mk(B, c.res, c.cout, c.cin, 9);
+      P2LConv g = mk(m->wfmt, B, c.res, c.cout, c.cin, 9);
       suggest_split(g, 0);
       w = p2l_conv_workspace_bytes(&g) / sizeof(float);
       if (w > max_cws) max_cws = w;
       const size_t pq = 2 * (size_t)B * p2l_conv_arb_nblk_ws(&g) * cm;
       if (pq > p1) p1 = pq;
     } else {
-      P2LConv g = mk(B, c.res, c.cout, c.cin, 9);
+      P2LConv g = mk(m->wfmt, B, c.res, c.cout, c.cin, 9);
       g.ups = 3; g.ext = 1;
       suggest_split(g, 0);
       const size_t w = p2l_conv_workspace_bytes(&g) / sizeof(float);
@@ -272,7 +270,7 @@ extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
   for (int l = 0; l < m->n_conv; ++l) {
     const P2LSg2Conv& c = m->conv[l];
     const float* nz = noise + (size_t)B * c.noise_off;
-    P2LConv d = mk(B, c.res, c.cin, c.cout, 9);
+    P2LConv d = mk(m->wfmt, B, c.res, c.cin, c.cout, 9);
     d.pro = P2L_PRO_AFFINE; d.pro_bstride = c.cin;
     P2LConvExtra ex{};
     ex.amax.in = am_in; ex.amax.in_n = am_n; ex.amax.in_applied = am_in ? 1 : 0;
@@ -318,7 +316,7 @@ extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
         RET_IF(p2l_sg2_rgb_up_fwd(W + L.skip[rj - 1], W + L.upbuf, B, r.res / 2, r.res / 2, st));
         res = W + L.upbuf;
       }
-      P2LConv t = mk(B, r.res, r.cin, 32, 1);
+      P2LConv t = mk(m->wfmt, B, r.res, r.cin, 32, 1);
       t.pro = P2L_PRO_AFFINE; t.pro_bstride = r.cin; t.n_store = 16; t.y_ld = 16; t.res_ld = 16;
       t.algo_flops = 2.0 * B * r.res * r.res * (double)r.cin * 3;
       RET_IF(p2l_conv_fwd(&t, x, r.w, r.bias, W + L.rs[rj], W + L.zeros, res, nullptr,
@@ -370,7 +368,7 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
     bool gy_ready = false;
     while (rj >= 0 && m->rgb[rj].after_conv == l) {
       const P2LSg2Rgb& r = m->rgb[rj];
-      P2LConv t = mk(B, r.res, 16, r.cin, 1);
+      P2LConv t = mk(m->wfmt, B, r.res, 16, r.cin, 1);
       t.algo_flops = 2.0 * B * r.res * r.res * (double)r.cin * 3;
       RET_IF(dgrad_scale(t, gs_cur, r.wt, W + L.y[l], W + L.rs[rj], r.cin,
                          have_next ? gx : nullptr, gy, W + L.rds[rj], tmp, W + L.part_r[rj], scratch, B, r.res,
@@ -398,13 +396,13 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
     float* gout = (dy == gx) ? gy : gx;
     if (c.up) {
       RET_IF(p2l_sg2_blur_bwd_amax(gd, tmp, B, c.res, c.res, c.cout, am_du, st));
-      P2LConv d = mk(B, c.res, c.cout, c.cin, 9);
+      P2LConv d = mk(m->wfmt, B, c.res, c.cout, c.cin, 9);
       d.ups = 3; d.ext = 1;
       // unfused temp must not alias the conv input (tmp): use gd
       RET_IF(dgrad_scale(d, tmp, c.wt, x_in, W + L.s[l], c.cin, nullptr, gout, W + L.ds[l], gd, W + L.part_l[l],
                          scratch, B, res_in, W + L.cws, L.cws_floats, am_du, st));
     } else {
-      P2LConv d = mk(B, c.res, c.cout, c.cin, 9);
+      P2LConv d = mk(m->wfmt, B, c.res, c.cout, c.cin, 9);
       RET_IF(dgrad_scale(d, gd, c.wt, x_in, W + L.s[l], c.cin, nullptr, gout, W + L.ds[l], tmp, W + L.part_l[l],
                          scratch, B, res_in, W + L.cws, L.cws_floats, am_gd, st));
     }
