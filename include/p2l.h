@@ -46,7 +46,8 @@ extern "C" {
  *   p2l_reduce_rows, p2l_adam_step, p2l_adam_step_dev, p2l_clamp, p2l_vec_scale_div, p2l_concat2, p2l_split2,
  *   p2l_sg2_pixelnorm_fwd/_bwd, p2l_sg2_bias_lrelu_fwd, p2l_sg2_lrelu_bwd, p2l_sg2_demod_fwd/_bwd,
  *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
- *   p2l_add_inplace, p2l_sg2_noise_relayout.
+ *   p2l_add_inplace, p2l_sg2_noise_relayout, p2l_area_pool3_to_nhwc16, p2l_area_pool_nchw,
+ *   p2l_area_unpool16_add_nchw3.
  * Every OTHER entry point checks only what its own comment states (a shape or alignment constraint, an unsupported
  * size): it does not test its pointers or its batch size, and a caller must not rely on it to. */
 
@@ -541,6 +542,23 @@ int p2l_nchw3_to_nhwc16(const float* src, float* dst, int Bn, int H, int W,
                         void* stream);
 int p2l_nhwc16_to_nchw3(const float* src, float* dst, int Bn, int H, int W,
                         void* stream);
+/* Area pooling in front of the LPIPS term (`lpips_size`; csrc/p2l_pool.hip).  pool_f, f in
+ * {2, 4, 8, 16}, is log2 f nested 2x2 means in fp32, each level
+ *   x'[y,x] = ((x[2y,2x] + x[2y,2x+1]) + (x[2y+1,2x] + x[2y+1,2x+1])) * 0.25f
+ * with every operation rounded on its own (no contraction): the bits of that expression evaluated by torch.
+ *   p2l_area_pool3_to_nhwc16     src [Bn,3,H,W] -> dst [Bn,H/f,W/f,16] = pool_f(src), channels 3..15 WRITTEN as +0.0
+ *   p2l_area_pool_nchw           dst [Bn,C,H/f,W/f] = pool_f(src * mul), src and mul [Bn,C,H,W]; mul NULL = pool_f(src)
+ *   p2l_area_unpool16_add_nchw3  dout [Bn,3,H,W] = d_full16[...,0:3] + expand_f(d_small16[...,0:3]) * (1 / f^2),
+ *                                d_small16 [Bn,H/f,W/f,16], d_full16 [Bn,H,W,16] or NULL (= the second term alone);
+ *                                expand_f = nearest-neighbour repetition; dout is written, never accumulated into
+ * One launch each, no workspace, no atomics; a value does not depend on Bn or on the image's place in the batch.
+ * P2L_EINVAL before the launch: a NULL or not 16-byte aligned pointer (mul and d_full16 may be NULL), Bn, C, H or W
+ * < 1, f outside {2, 4, 8, 16}, H or W no multiple of f. */
+int p2l_area_pool3_to_nhwc16(const float* src, float* dst, int Bn, int H, int W, int f, void* stream);
+int p2l_area_pool_nchw(const float* src, const float* mul, float* dst, int Bn, int C, int H, int W, int f,
+                       void* stream);
+int p2l_area_unpool16_add_nchw3(const float* d_small16, const float* d_full16, float* dout, int Bn, int H, int W,
+                                int f, void* stream);
 /* d(pre-tanh) = d(img) * (1 - img^2), in place on the 16-channel gradient    */
 int p2l_tanh_bwd16(const float* img, float* dimg, int64_t P, void* stream);
 

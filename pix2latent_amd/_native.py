@@ -312,6 +312,7 @@ EXPORTS = [
     'p2l_gram_f64_ws_bytes', 'p2l_gram_f64', 'p2l_gram_f64_wide_ws_bytes', 'p2l_gram_f64_wide',
     'p2l_poisson_blend_ws_bytes', 'p2l_poisson_blend',
     'p2l_sg2_noise_reg_ws_bytes', 'p2l_sg2_noise_reg_fwd', 'p2l_sg2_noise_reg_bwd', 'p2l_sg2_noise_normalize',
+    'p2l_area_pool3_to_nhwc16', 'p2l_area_pool_nchw', 'p2l_area_unpool16_add_nchw3',
 ]
 
 _lib = None
@@ -381,6 +382,9 @@ def lib():
         _lib.p2l_sg2_noise_reg_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_size_t, vp]
         _lib.p2l_sg2_noise_reg_bwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.c_size_t, vp]
         _lib.p2l_sg2_noise_normalize.argtypes = [vp, vp, i32, i32, vp, C.c_size_t, vp]
+        _lib.p2l_area_pool3_to_nhwc16.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        _lib.p2l_area_pool_nchw.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        _lib.p2l_area_unpool16_add_nchw3.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     return _lib
 
 

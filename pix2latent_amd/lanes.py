@@ -50,6 +50,9 @@ class LaneScratch(object):
         self.ws, self.ws_bytes, self.cap = None, 0, -1
         self.img16 = self.dimg16 = None
         self.ticket, self.last_B = 0, 0
+        # a loss with `lpips_size`: its arena and staging above are at the pooled size, the L1 term's are here
+        self.full16 = self.dfull16 = self.l1_part = None
+        self.full_cap, self.full_res = -1, None
 
 
 class Scratch(object):
@@ -80,6 +83,19 @@ class Scratch(object):
             img16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
             dimg16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
             s.ws, s.ws_bytes, s.cap, s.img16, s.dimg16 = ws, nbytes, B, img16, dimg16
+            self.generation += 1
+        return s
+
+    def grow_full(self, B, H, W, n_part, device):
+        """the current lane's record with the full-resolution staging of a pooled loss for B images of H x W (the
+        two 16-channel tensors and B * n_part floats of L1 partial sums), kept in the SAME record as the pooled-size
+        scratch: `drop_side` and `clear` free both, and a re-allocation bumps the one `generation`"""
+        s = self.here()
+        if B > s.full_cap or s.full_res != (H, W):
+            full16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
+            dfull16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
+            part = torch.empty(B * n_part, device=device, dtype=torch.float32)
+            s.full16, s.dfull16, s.l1_part, s.full_cap, s.full_res = full16, dfull16, part, B, (H, W)
             self.generation += 1
         return s
 

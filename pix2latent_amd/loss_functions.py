@@ -179,6 +179,56 @@ class NoiseRegularizer(object):
 
 
 # ---------------------------------------------------------------------------
+# `lpips_size`: the LPIPS term on an area-pooled image (the StyleGAN2 projector's 256^2)
+# ---------------------------------------------------------------------------
+POOL_FACTORS = (1, 2, 4, 8, 16)
+
+
+def area_pool_torch(x, f):
+    """pool_f(x) of x [..., H, W]: log2 f nested 2x2 means in fp32, each level ((a + b) + (c + d)) * 0.25 -- the
+    cell order of `noise_regularize_torch`.  The definition in torch ops, on any device and for any channel count:
+    the CPU path, and what the HIP kernels (csrc/p2l_pool.hip) are held to bit for bit."""
+    f = int(f)
+    H, W = x.shape[-2:]
+    if f not in POOL_FACTORS or H % f or W % f:
+        raise ValueError('area_pool_torch: factor %d on %s (a factor of %s that divides H and W)'
+                         % (f, tuple(x.shape), POOL_FACTORS))
+    x = x.float()
+    while f > 1:
+        x = ((x[..., 0::2, 0::2] + x[..., 0::2, 1::2]) + (x[..., 1::2, 0::2] + x[..., 1::2, 1::2])) * 0.25
+        f //= 2
+    return x
+
+
+def lpips_pool_factor(shape, lpips_size):
+    """f = H // lpips_size for an output of `shape` [B,3,H,W] (1 for lpips_size=None), or a ValueError that names
+    the shapes: from shape arithmetic alone, before anything is launched"""
+    if lpips_size is None:
+        return 1
+    s = int(lpips_size)
+    H, W = int(shape[-2]), int(shape[-1])
+    if s < 1 or H % s:
+        raise ValueError('lpips_size=%d does not divide the height of the output %s' % (s, tuple(shape)))
+    f = H // s
+    if f not in POOL_FACTORS:
+        raise ValueError('lpips_size=%d on an output %s is a pooling factor of %d: supported are %s'
+                         % (s, tuple(shape), f, POOL_FACTORS))
+    if W % f:
+        raise ValueError('lpips_size=%d on an output %s: the pooling factor %d does not divide the width %d'
+                         % (s, tuple(shape), f, W))
+    return f
+
+
+class _Pooled(object):
+    """what a pooled loss keeps per (target, weight, loss_mask) chunk: pool_f(target), pool_f(weight * loss_mask),
+    the full-resolution weight sum of the L1 term"""
+
+    def __init__(self, target, weight, wsum, held):
+        self.target, self.weight, self.wsum, self.held = target, weight, wsum, held
+        self.guard = _StreamGuard().filled()
+
+
+# ---------------------------------------------------------------------------
 # native engine shared by Reconstruction / Perceptual / Projection losses
 # ---------------------------------------------------------------------------
 class _LpipsParams(object):
@@ -381,6 +431,7 @@ class _LossEngine(object):
         self.keep = {}           # key -> the tensors it identifies (kept alive)
         self.cache = None        # P2LLossCache of the slot bound by the last prepare()
         self._memo = {}
+        self._pooled = {}        # (idents of target / weight / loss_mask, f, want_l1) -> _Pooled, LRU order
 
     # per-lane scratch (the cached target features are shared: read-only while steps run)
     lanes_ok = True
@@ -454,6 +505,30 @@ class _LossEngine(object):
                                 _StreamGuard().filled(), t)
         self._memo[name][2].reader()
         return self._memo[name][1]
+
+    def pooled(self, target, weight, loss_mask, f, want_l1):
+        """-> _Pooled of conformed full-resolution tensors, memoised on their identity and version as `bind` does:
+        pooling runs once per chunk and generation, a step makes no new device tensors, and the cache slot of the
+        pooled-size LPIPS term (keyed on the identity of the POOLED tensors) stays the same."""
+        from . import ops
+        key = (self._ident(target), self._ident(weight), self._ident(loss_mask), f, want_l1)
+        ent = self._pooled.pop(key, None)
+        if ent is None:
+            if len(self._pooled) >= 2 * self.MAX_SLOTS:
+                self._pooled.pop(next(iter(self._pooled)))
+            wsum = None
+            if want_l1:
+                B, HW3 = target.size(0), target[0].numel()
+                wsum = torch.empty(B, device=target.device, dtype=torch.float32)
+                N.check(self.lib.p2l_weight_sum(N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum), B, HW3, N.stream()),
+                        'p2l_weight_sum')
+            # (the sources are kept alive: their data_ptr identifies them)
+            ent = _Pooled(ops.area_pool_nchw(target, f), ops.area_pool_nchw(weight, f, mul=loss_mask), wsum,
+                          (target, weight, loss_mask))
+        else:
+            ent.guard.reader()                 # (pooled on another lane's stream, perhaps in this very step)
+        self._pooled[key] = ent
+        return ent
 
     def _same_content(self, target, weight, loss_mask, use_lpips, B):
         """A generation of a CMA run starts from FRESH variables (reference base_cma_optimizer.py:79):
@@ -628,6 +703,103 @@ class _ProjLossFn(torch.autograd.Function):
         return dout, None, None, None, None, None, None
 
 
+def _apply_pooled(eng, output, target, weight, loss_mask, beta, mode, f):
+    """`_apply` with the LPIPS term at [H/f, W/f]: L1w(out, ...) + beta * LPIPSw(pool_f(out), pool_f(target),
+    pool_f(weight * loss_mask)); mode 2 = the second term alone.  The one-channel-weight factor 3 of the reference
+    (see `_apply`) belongs to the L1 term."""
+    B = output.size(0)
+    wc, mc = _channels(weight), _channels(loss_mask)
+    l1_factor = 3.0 if (mode == 0 and wc == 1 and mc in (None, 1)) else 1.0
+    return _PooledLossFn.apply(output, eng.bind('target', target, B, like=output),
+                               eng.bind('weight', weight, B, like=output),
+                               eng.bind('loss_mask', loss_mask, B, like=output), eng, float(beta), l1_factor,
+                               mode, f)
+
+
+class _PooledLossFn(torch.autograd.Function):
+    """The engine's plan is allocated and prepared at the pooled size and driven as the LPIPS term alone; the L1
+    term runs at full resolution through p2l_l1_loss_fwd / _bwd.  Forward: pool + pack (one launch), the plan,
+    [pack, L1].  Backward: the plan, [L1], then ONE launch that writes d out = dL1 + expand_f(dLPIPS) / f^2."""
+
+    @staticmethod
+    def forward(ctx, output, target, weight, loss_mask, eng, beta, l1_factor, mode, f):
+        lib = eng.lib
+        B, _, H, W = output.shape
+        h, w = H // f, W // f
+        out_c = output.contiguous().float()
+        want_l1 = mode != 2
+        ent = eng.pooled(target, weight, loss_mask, f, want_l1)
+        slot = eng.prepare(ent.target, ent.target, ent.weight, None, 1)      # (first argument: shape and device)
+        s = eng._scratch.here()
+        N.check(lib.p2l_area_pool3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, f, N.stream()),
+                'p2l_area_pool3_to_nhwc16')
+        loss = torch.empty(B, device=output.device, dtype=torch.float32)
+        l1 = torch.empty_like(loss)
+        lp = torch.empty_like(loss)
+        # (the plan's own L1 term, of the pooled images, lands in `l1`: a by-product unless this is mode 2)
+        N.check(eng.f_fwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(ent.target), N.ptr(ent.weight), None,
+                          C.byref(slot.desc), N.f32(1.0), 1, B, h, w, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                          N.ptr(loss), N.ptr(l1), N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
+        if want_l1:
+            eng._scratch.grow_full(B, H, W, lib.p2l_l1_loss_nblk(H, W), output.device)
+            l1 = torch.empty_like(loss)
+            N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()),
+                    'p2l_nchw3_to_nhwc16')
+            N.check(lib.p2l_l1_loss_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                                        N.ptr(ent.wsum), N.ptr(l1), N.ptr(s.l1_part), B, H, W, N.stream()),
+                    'p2l_l1_loss_fwd')
+            # loss = l1_factor * l1 + beta * lp
+            N.check(lib.p2l_vec_scale_div(N.ptr(l1), None, N.ptr(loss), B, N.f32(l1_factor), N.stream()),
+                    'p2l_vec_scale_div')
+            N.check(lib.p2l_reduce_rows(N.ptr(lp), N.ptr(loss), B, 1, N.f32(beta), None, 1, N.stream()),
+                    'p2l_reduce_rows')
+        if len(eng._lanes) > 1:
+            slot.used()
+        ctx.eng, ctx.slot, ctx.ent = eng, slot, ent
+        ctx.beta, ctx.l1_factor, ctx.want_l1, ctx.f = beta, l1_factor, want_l1, f
+        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
+        ctx.has_mask = loss_mask is not None
+        ctx.stamp = eng._scratch.stamp()
+        eng.last_l1, eng.last_lpips = l1, lp
+        return loss if want_l1 else lp
+
+    @staticmethod
+    def backward(ctx, gloss):
+        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
+            return _PooledLossFn._backward(ctx, gloss)
+
+    @staticmethod
+    def _backward(ctx, gloss):
+        eng, ent, f = ctx.eng, ctx.ent, ctx.f
+        lib = eng.lib
+        out_c, target, weight, loss_mask = ctx.saved_tensors
+        if not ctx.has_mask:
+            loss_mask = None
+        B, _, H, W = out_c.shape
+        if eng._scratch.stale(ctx.stamp):
+            raise N.NativeError('loss workspace was reused by a later forward before '
+                                'backward(); use one loss object per in-flight graph')
+        s = eng._scratch.here()
+        g = gloss.contiguous().float()
+        # d (beta * LPIPS) / d pool_f(out), the LPIPS term alone (use_lpips = 2)
+        N.check(eng.f_bwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(ent.target), N.ptr(ent.weight), None,
+                          C.byref(ctx.slot.desc), N.f32(ctx.beta), 2, N.ptr(g), B, H // f, W // f, N.ptr(s.ws),
+                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()), 'p2l_%sloss_bwd' % eng.prefix)
+        if len(eng._lanes) > 1:
+            ctx.slot.used()
+        dfull = None
+        if ctx.want_l1:
+            gl = g if ctx.l1_factor == 1.0 else g * ctx.l1_factor
+            dfull = s.dfull16
+            N.check(lib.p2l_l1_loss_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                                        N.ptr(ent.wsum), N.ptr(gl), N.ptr(dfull), B, H, W, 0, N.stream()),
+                    'p2l_l1_loss_bwd')
+        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
+        N.check(lib.p2l_area_unpool16_add_nchw3(N.ptr(s.dimg16), N.ptr(dfull), N.ptr(dout), B, H, W, f,
+                                                N.stream()), 'p2l_area_unpool16_add_nchw3')
+        return dout, None, None, None, None, None, None, None, None
+
+
 _VGG_PARAMS = {}
 # net -> (packed-parameter class, synthetic weights, loader of the upstream checkpoint pair)
 _LPIPS_NETS = {'vgg': (_VggLpipsParams, 'lpips_vgg_weights', 'load_lpips_vgg'),
@@ -679,18 +851,26 @@ class ProjectionLoss(nn.Module):
     """ The default loss that is used in the paper (reference loss_functions.py:86-100).
 
     lpips_net: 'alex' (reference default), 'vgg' or 'squeeze'; all three are native HIP plans.
+    lpips_size: None (the reference: LPIPS over the output as it is) or the height the output, the target and
+        `weight * loss_mask` are area-pooled to in front of the LPIPS term, as the StyleGAN2 projector does with
+        256 (`area_pool_torch`; the factor H // lpips_size is 1, 2, 4, 8 or 16).  The L1 term stays at full
+        resolution.
     """
 
-    def __init__(self, lpips_net='alex', beta=10, weights=None, device='cuda'):
+    def __init__(self, lpips_net='alex', beta=10, weights=None, device='cuda', lpips_size=None):
         super().__init__()
         self.beta = beta
+        self.lpips_size = None if lpips_size is None else int(lpips_size)
         self._engine = _LossEngine(_vgg_params(lpips_net, weights, device))
         self.rloss_fn = ReconstructionLoss()
-        self.ploss_fn = PerceptualLoss(net=lpips_net, weights=weights, device=device)
+        self.ploss_fn = PerceptualLoss(net=lpips_net, weights=weights, device=device, lpips_size=lpips_size)
         return
 
     def __call__(self, output, target, weight=None, loss_mask=None):
-        return _apply(self._engine, output, target, weight, loss_mask, self.beta, 0)
+        f = lpips_pool_factor(output.shape, self.lpips_size)
+        if f == 1:
+            return _apply(self._engine, output, target, weight, loss_mask, self.beta, 0)
+        return _apply_pooled(self._engine, output, target, weight, loss_mask, self.beta, 0, f)
 
 
 class ReconstructionLoss(nn.Module):
@@ -724,12 +904,17 @@ class ReconstructionLoss(nn.Module):
 
 
 class PerceptualLoss(nn.Module):
-    """ LPIPS loss with spatial weighting (reference loss_functions.py:127-148) """
+    """ LPIPS loss with spatial weighting (reference loss_functions.py:127-148); `lpips_size` as in
+    ProjectionLoss: the LPIPS term of the area-pooled tensors """
 
-    def __init__(self, net='vgg', use_gpu=True, weights=None, device='cuda'):
+    def __init__(self, net='vgg', use_gpu=True, weights=None, device='cuda', lpips_size=None):
         super(PerceptualLoss, self).__init__()
+        self.lpips_size = None if lpips_size is None else int(lpips_size)
         self._engine = _LossEngine(_vgg_params(net, weights, device))
         return
 
     def __call__(self, output, target, weight=None, loss_mask=None):
-        return _apply(self._engine, output, target, weight, loss_mask, 1.0, 2)
+        f = lpips_pool_factor(output.shape, self.lpips_size)
+        if f == 1:
+            return _apply(self._engine, output, target, weight, loss_mask, 1.0, 2)
+        return _apply_pooled(self._engine, output, target, weight, loss_mask, 1.0, 2, f)

@@ -375,6 +375,41 @@ def conv1_dgrad(g, w_t3, H, W, K, S, pad):
     return d
 
 
+# ---- area pooling in front of the LPIPS term (csrc/p2l_pool.hip; NCHW tensors) ----------
+def area_pool3_to_nhwc16(x, f, out=None):
+    """x [B,3,H,W] -> [B,H/f,W/f,16]: pool_f(x) in channels 0..2, +0.0 in 3..15 (p2l_area_pool3_to_nhwc16)"""
+    B, _, H, W = x.shape
+    assert x.size(1) == 3, 'an image of 3 channels'
+    if out is None:
+        out = torch.empty(B, H // f, W // f, 16, device=x.device)
+    N.check(_lib().p2l_area_pool3_to_nhwc16(N.ptr(x), N.ptr(out), B, H, W, int(f), N.stream()),
+            'p2l_area_pool3_to_nhwc16')
+    return out
+
+
+def area_pool_nchw(x, f, mul=None):
+    """pool_f(x * mul) of x [B,C,H,W] (mul of the same shape, or None) -> [B,C,H/f,W/f] (p2l_area_pool_nchw)"""
+    B, Cc, H, W = x.shape
+    assert mul is None or mul.shape == x.shape
+    out = torch.empty(B, Cc, H // f, W // f, device=x.device)
+    N.check(_lib().p2l_area_pool_nchw(N.ptr(x), N.ptr(mul), N.ptr(out), B, Cc, H, W, int(f), N.stream()),
+            'p2l_area_pool_nchw')
+    return out
+
+
+def area_unpool16_add_nchw3(d_small16, d_full16, f, out=None):
+    """[B,3,H,W] = d_full16[...,0:3] + expand_f(d_small16[...,0:3]) / f^2 with d_small16 [B,H/f,W/f,16] and d_full16
+    [B,H,W,16] or None (p2l_area_unpool16_add_nchw3); `out` is overwritten"""
+    B, h, w, _ = d_small16.shape
+    H, W = h * f, w * f
+    assert d_full16 is None or tuple(d_full16.shape) == (B, H, W, 16)
+    if out is None:
+        out = torch.empty(B, 3, H, W, device=d_small16.device)
+    N.check(_lib().p2l_area_unpool16_add_nchw3(N.ptr(d_small16), N.ptr(d_full16), N.ptr(out), B, H, W, int(f),
+                                               N.stream()), 'p2l_area_unpool16_add_nchw3')
+    return out
+
+
 # ---- StyleGAN2 noise regulariser / per-layer normalisation (csrc/p2l_noise_reg.hip) ----
 _NOISE_RES = {}
 

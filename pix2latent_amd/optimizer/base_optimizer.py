@@ -336,7 +336,9 @@ class _BaseOptimizer(SearchLoopMixin):
         a lane's workspace (lanes.Scratch.generation) leaves the old pointers baked into the
         captured launches
         ... and the regularisers of the input variables: their launches and constants (layer list, weight)
-        are part of the capture"""
+        are part of the capture
+        ... and the loss object with its `lpips_size`: which launches a step makes of it (the pooled LPIPS term or
+        the full-resolution one) is baked in too"""
         owners = (self.model, getattr(self.loss_fn, '_engine', None))
         return (variables.num_samples, lo, hi, self.max_batch_size, self.exec_batch_size,
                 variables.opt.state_key()) + tuple(
@@ -346,7 +348,8 @@ class _BaseOptimizer(SearchLoopMixin):
             (name, _regularizer_key(v.get('regularizer', None))) for name, v in sorted(variables.input.items())
             if v.get('regularizer', None) is not None) + tuple(
             (name, v.buf.data_ptr(), v.buf._version) for name, v in sorted(variables.output.items())
-            if v.get('buf', None) is not None)
+            if v.get('buf', None) is not None) + (
+            ('loss_fn', id(self.loss_fn), getattr(self.loss_fn, 'lpips_size', None)),)
 
     def _graphed_step(self, variables, optimize, transform, lo, hi):
         """optimize steps without a transform, on variables whose device buffers were seen
