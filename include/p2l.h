@@ -40,7 +40,10 @@ extern "C" {
 /* Host-side argument checks.  The entry points listed here refuse, with
  * P2L_EINVAL and BEFORE anything is launched, a NULL where a pointer is required, Bn < 1, any other size < 1
  * (p2l_reduce_rows: n < 0), a row pitch below the row length, and Bn > 65535 where the batch is a y/z grid
- * dimension (p2l_scale_bwd, p2l_sg2_styled_act_bwd(_amax), p2l_weight_map, p2l_l1_loss_fwd/_bwd):
+ * dimension (p2l_scale_bwd, p2l_affine_relu_bwd, p2l_arb_finish, p2l_gemm(_ws), p2l_affine_grid_sample_bwd with
+ * dtheta, p2l_sg2_styled_act_bwd(_amax), p2l_weight_map, p2l_l1_loss_fwd/_bwd):
+ *   p2l_gemm(_ws), p2l_softmax_fwd/_bwd, p2l_affine_relu_bwd, p2l_arb_finish, p2l_affine_grid_sample(_bwd),
+ *   p2l_sg2_blur_fwd(_amax), p2l_sg2_blur_bwd(_amax),
  *   p2l_linear_fwd(_ld), p2l_linear_bwd(_ld), p2l_cbn_fold_fwd/_bwd, p2l_scale_bwd, p2l_relu_mask,
  *   p2l_nchw3_to_nhwc16, p2l_nhwc16_to_nchw3, p2l_tanh_bwd16, p2l_weight_sum, p2l_weight_map, p2l_l1_loss_fwd/_bwd,
  *   p2l_reduce_rows, p2l_adam_step, p2l_adam_step_dev, p2l_clamp, p2l_vec_scale_div, p2l_concat2, p2l_split2,
@@ -407,7 +410,14 @@ int p2l_pack_conv_weight_subpix_h2(const float* w_oihw, int O, int I, int N_pad,
 /*   C[b] = alpha * op(A[b]) * op(B[b])  (+ C[b] if accumulate)              */
 /*   a_kmajor=0: A is [M][lda] with K contiguous; 1: A is [K][lda], M contig */
 /*   b_kmajor=0: B is [N][ldb] with K contiguous; 1: B is [K][ldb], N contig */
-/*   M % 128 == 0, N % 32 == 0, K % 16 == 0.                                 */
+/*   M % 128 == 0, N % 32 == 0, K % 16 == 0, all three at least one tile     */
+/*   (M >= 128, N >= 32, K >= 16); lda, ldb % 4 == 0 and not below the row   */
+/*   they pitch (K, or M / N for a K-major operand); ldc >= N; the batch     */
+/*   strides >= 0 (stride_b = 0: one B for the batch); 1 <= batch <= 65535.  */
+/*   Anything else: P2L_EINVAL before the launch.                            */
+/*   Order of the sum: one fp32 accumulator per output walks k upwards, two  */
+/*   products per step (k, k + 4 within each group of 8), then * alpha, then */
+/*   + C.                                                                    */
 /* ------------------------------------------------------------------------- */
 typedef struct P2LGemm {
   int32_t batch, M, N, K;
@@ -419,10 +429,14 @@ typedef struct P2LGemm {
 } P2LGemm;
 int p2l_gemm(const P2LGemm* d, const float* A, const float* B, float* C,
              void* stream);
-/* same, splitting K over extra blocks when the product is deep (K >= 1024) and has fewer
- * than 192 output tiles; the K slices are summed in a fixed order (no atomics).  `ws` needs
- * p2l_gemm_ws_bytes(d) bytes (0 = this product is never split); without it the call is
- * p2l_gemm. */
+/* same, splitting K over extra blocks when the product is deep (K >= 1024) and four images of it have
+ * fewer than 192 output tiles; the K slices are summed in a fixed order (no atomics).  `ws` needs
+ * p2l_gemm_ws_bytes(d) bytes (0 = this product is never split); without it, with a short one or with
+ * ldc % 4 != 0 the call is p2l_gemm.  p2l_gemm_ws_bytes = s * batch * M * N * 4 with s = min(8, K / 256,
+ * ceil(512 / (4 * tiles))) slices asked for (tiles = (M / 128) * (N / 64 or 32); s <= 1: 0 bytes); the slices
+ * are ceil(ceil(K / s) / 16) * 16 deep, the last one shorter, and their number is recounted from that depth.  It
+ * does not depend on `batch`: image b of a batch has the bits of the same image multiplied alone.  Per slice the
+ * order above; the slices are added in index order, then * alpha, then + C. */
 size_t p2l_gemm_ws_bytes(const P2LGemm* d);
 int p2l_gemm_ws(const P2LGemm* d, const float* A, const float* B, float* C, void* ws,
                 size_t ws_bytes, void* stream);
@@ -488,9 +502,16 @@ int p2l_cbn_fold_bwd(const float* ds, const float* dt, const float* mean,
 /*   dt[b,c] = sum_p g   (written at ds[b*dsdt_bstride + c]).                 */
 /* skip (optional) is the GenBlock shortcut gradient: the block-output        */
 /* gradient dY restricted to channels c < skip_C; with skip_ups=1 dY lives at */
-/* [B,2H,2W,*] and its 2x2 children are summed (nearest-x2 backward).         */
+/* [B,2H,2W,*] and its 2x2 children are summed (nearest-x2 backward), row-major */
+/* as (c0 + c1) + (c2 + c3).                                                    */
 /* Deterministic two-stage reduction; `partial` needs 2*B*nblk*C floats with  */
-/* nblk = p2l_affine_relu_bwd_nblk(H*W).  C % 64 == 0.                        */
+/* nblk = p2l_affine_relu_bwd_nblk(H*W).  C % 32 == 0, C >= 32 (strips of 64   */
+/* channels; the upper half of the last strip idles where C % 64 == 32);       */
+/* 1 <= Bn <= 65535, H, W >= 1, every pitch % 4 == 0 and >= C, skip_C % 4 == 0 */
+/* in 0..C.  The mask takes the FORWARD's decision: the conv prologues compute  */
+/* a = max(fmaf(x, s, t), 0) (one rounding), and so does this kernel -- where   */
+/* x*s and t cancel, the element is live exactly when the forward's a > 0       */
+/* (tests/test_glue_kernels_gpu.py holds the two against each other).           */
 int p2l_affine_relu_bwd_nblk(int P);
 int p2l_affine_relu_bwd(const float* da, int da_ld, const float* x, int x_ld,
                         const float* s, const float* t, int st_bstride,
@@ -508,6 +529,9 @@ int p2l_scale_bwd(const float* da, int da_ld, const float* x, int x_ld, const fl
 
 /* ------------------------------------------------------------------------- */
 /* Row softmax for the attention matrix and its backward.                    */
+/*   P = exp(S - max_row S) / sum ; dS = P * (dP - sum_row P dP)             */
+/* cols in {256, 512, 1024, 2048} (one wave per row; other widths:           */
+/* P2L_EUNSUP, nothing written), rows >= 1, dense rows, 16-byte aligned.     */
 /* ------------------------------------------------------------------------- */
 int p2l_softmax_fwd(const float* S, float* P, int64_t rows, int cols,
                     void* stream);
@@ -851,7 +875,8 @@ int p2l_affine_grid_sample(const float* src, const float* theta, float* dst, int
  * pix2latent/loss_functions.py:30-38 invertibility_loss; autograd through
  * spatial_transform.py:69-104): d src (gather form of the adjoint, may be NULL) and d theta [B][6]
  * (may be NULL; needs src and p2l_affine_grid_sample_bwd_ws_bytes of workspace).  Fixed summation
- * order, no atomics. */
+ * order, no atomics.  Bn, C, H, W >= 1 (with dtheta: Bn <= 65535); P2L_EINVAL and, for a missing or short
+ * workspace, P2L_EWS are returned before anything is launched. */
 size_t p2l_affine_grid_sample_bwd_ws_bytes(int Bn, int H, int W);
 int p2l_affine_grid_sample_bwd(const float* src, const float* theta, const float* dout,
                                float* dsrc, float* dtheta, int Bn, int C, int H, int W,
@@ -949,7 +974,13 @@ int p2l_sg2_demod_fwd(const float* s, const float* Wsq, float* d, int Bn, int Ci
                       void* stream);
 int p2l_sg2_demod_bwd(const float* s, const float* Wsq, const float* d, const float* dd, float* ds,
                       int Bn, int Cin, int Cout, int accumulate, void* stream);
-/* y[B,H,W,C] = lrelu(blur4x4(u[B,H+2,W+2,C]) * d[b,c] + nw*noise[b,p] + bias[c]) * sqrt2 */
+/* y[B,H,W,C] = lrelu(blur4x4(u[B,H+2,W+2,C]) * d[b,c] + nw*noise[b,p] + bias[c]) * sqrt2
+ * The frame u holds the H+1 x W+1 result of the stride-2 transposed conv in rows 0..H, columns 0..W; its last row
+ * (H+1) and column (W+1) are zero on input.  blur4x4(u)[Y,X] = sum_{j,i} a_j a_i u[Y+j-1, X+i-1], a = [1 3 3 1] / 4,
+ * taps above row 0 / left of column 0 are zero.  H % 4 == 0, W % 4 == 0, C % 4 == 0 (H != W is fine); noise
+ * [B, H*W] may be NULL; a pre-activation of 0 or -0 takes the negative slope.  p2l_sg2_blur_bwd is the transpose:
+ * du[B,H+2,W+2,C] from g[B,H,W,C], the WHOLE frame written (row H+1 and column W+1 too: the forward reads them),
+ * C % 4 == 0, any H, W >= 1. */
 int p2l_sg2_blur_fwd(const float* u, const float* d, const float* noise, float nw,
                      const float* bias, float* y, int Bn, int H, int W, int C, void* stream);
 /* activation backward of a styled conv: gd = dy*lrelu'(y)*d ; dd[b,c] = sum_p dy*lrelu'(y)*c

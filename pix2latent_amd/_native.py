@@ -368,6 +368,12 @@ def lib():
         _lib.p2l_add_inplace.argtypes = [vp, vp, i64_, vp]
         _lib.p2l_sg2_styled_act_bwd.argtypes = [vp, vp, vp, vp, f32_, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
         _lib.p2l_sg2_styled_act_bwd_amax.argtypes = [vp, vp, vp, vp, f32_, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+        _lib.p2l_softmax_fwd.argtypes = [vp, vp, i64_, i32, vp]
+        _lib.p2l_softmax_bwd.argtypes = [vp, vp, vp, i64_, i32, vp]
+        _lib.p2l_sg2_blur_fwd.argtypes = [vp, vp, vp, f32_, vp, vp, i32, i32, i32, i32, vp]
+        _lib.p2l_sg2_blur_fwd_amax.argtypes = [vp, vp, vp, f32_, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+        _lib.p2l_sg2_blur_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        _lib.p2l_sg2_blur_bwd_amax.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
         _lib.p2l_gram_f64_ws_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
         _lib.p2l_gram_f64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -243,8 +243,12 @@ extern "C" int p2l_gemm_ws(const P2LGemm* d, const float* A, const float* B, flo
 static int gemm_impl(const P2LGemm* d, const float* A, const float* B, float* C, void* ws,
                      size_t ws_bytes, void* stream) {
   if (!d || !A || !B || !C) return P2L_EINVAL;
-  if (d->M % 128 || d->N % 32 || d->K % 16 || d->batch < 1) return P2L_EINVAL;
+  if (d->M < 128 || d->N < 32 || d->K < 16 || d->batch < 1 || d->batch > 65535) return P2L_EINVAL;  // (batch: grid y)
+  if (d->M % 128 || d->N % 32 || d->K % 16) return P2L_EINVAL;
   if (d->lda % 4 || d->ldb % 4) return P2L_EINVAL;
+  if (d->lda < (d->a_kmajor ? d->M : d->K) || d->ldb < (d->b_kmajor ? d->N : d->K) || d->ldc < d->N)
+    return P2L_EINVAL;
+  if (d->stride_a < 0 || d->stride_b < 0 || d->stride_c < 0) return P2L_EINVAL;
   GemmK g{};
   g.A = A; g.B = B; g.C = C;
   g.M = d->M; g.N = d->N; g.K = d->K;

@@ -168,11 +168,13 @@ __global__ __launch_bounds__(256) void affine_relu_bwd_kernel(const ArbK k) {
     const size_t pix = (size_t)b * k.P + p;
     const f32x4 xv = *reinterpret_cast<const f32x4*>(k.x + pix * k.x_ld + c);
     const f32x4 dv = *reinterpret_cast<const f32x4*>(k.da + pix * k.da_ld + c);
+    // the mask is the FORWARD's decision: the conv prologues round x*s+t once (a fused multiply-add), and where
+    // the product and t cancel a twice-rounded sum has another sign (p2l.h)
     f32x4 g;
-    g.x = (k.nomask || xv.x * s4.x + t4.x > 0.f) ? dv.x : 0.f;
-    g.y = (k.nomask || xv.y * s4.y + t4.y > 0.f) ? dv.y : 0.f;
-    g.z = (k.nomask || xv.z * s4.z + t4.z > 0.f) ? dv.z : 0.f;
-    g.w = (k.nomask || xv.w * s4.w + t4.w > 0.f) ? dv.w : 0.f;
+    g.x = (k.nomask || fmaf(xv.x, s4.x, t4.x) > 0.f) ? dv.x : 0.f;
+    g.y = (k.nomask || fmaf(xv.y, s4.y, t4.y) > 0.f) ? dv.y : 0.f;
+    g.z = (k.nomask || fmaf(xv.z, s4.z, t4.z) > 0.f) ? dv.z : 0.f;
+    g.w = (k.nomask || fmaf(xv.w, s4.w, t4.w) > 0.f) ? dv.w : 0.f;
     as += g * xv;
     at += g;
     f32x4 o = g * s4;
@@ -1062,15 +1064,18 @@ extern "C" int p2l_affine_relu_bwd(const float* da, int da_ld, const float* x,
                                    float* partial, int Bn, int H, int W, int C,
                                    void* stream) {
   if (!da || !x || !s || !t || !dx || !ds || !dt || !partial) return P2L_EINVAL;
-  if (C % 32 || da_ld % 4 || x_ld % 4 || dx_ld % 4 || st_bstride % 4) return P2L_EINVAL;
-  if (skip && (skip_ld % 4 || skip_C % 4)) return P2L_EINVAL;
+  if (C % 32 || da_ld % 4 || x_ld % 4 || dx_ld % 4 || st_bstride % 4 || dsdt_bstride % 4) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || H < 1 || W < 1 || C < 32) return P2L_EINVAL;      // (Bn is the grid's z)
+  if (da_ld < C || x_ld < C || dx_ld < C || st_bstride < C || dsdt_bstride < C) return P2L_EINVAL;
+  if (skip && (skip_ld % 4 || skip_C % 4 || skip_C < 0 || skip_C > C || skip_ld < skip_C)) return P2L_EINVAL;
   ArbK k{};
   k.da = da; k.x = x; k.s = s; k.t = t; k.skip = skip; k.dx = dx; k.partial = partial;
   k.da_ld = da_ld; k.x_ld = x_ld; k.dx_ld = dx_ld; k.skip_ld = skip_ld;
   k.skip_C = skip_C; k.skip_ups = skip_ups; k.st_bstride = st_bstride;
   k.Bn = Bn; k.P = H * W; k.C = C; k.H = H; k.W = W;
   k.nblk = cdiv(k.P, ARB_SLAB);
-  hipLaunchKernelGGL(affine_relu_bwd_kernel, dim3(k.nblk, C / 64, Bn), dim3(256), 0,
+  // (cdiv(C, 64) strips: the upper half of the last one idles where C % 64 == 32, as for p2l_scale_bwd)
+  hipLaunchKernelGGL(affine_relu_bwd_kernel, dim3(k.nblk, cdiv(C, 64), Bn), dim3(256), 0,
                      ST(stream), k);
   const int rc = p2l_check_launch();
   if (rc) return rc;
@@ -1102,7 +1107,9 @@ extern "C" int p2l_arb_defer_flush(void* stream) {
 
 extern "C" int p2l_arb_finish(const float* partial, float* ds, float* dt, int Bn, int nblk,
                               int C, int out_bstride, void* stream) {
+  if (!partial || !ds || !dt) return P2L_EINVAL;
   if (C % 32 || out_bstride % 4) return P2L_EINVAL;
+  if (Bn < 1 || Bn > 65535 || nblk < 1 || C < 32 || out_bstride < C) return P2L_EINVAL;   // (Bn is the grid's y)
   if (g_arb_defer) {
     ArbFinGroup& g = g_arb_group;
     if (g.n == ARB_GROUP_MAX || (g.n > 0 && g.Bn != Bn)) {
@@ -1142,7 +1149,9 @@ extern "C" int p2l_scale_bwd(const float* da, int da_ld, const float* x, int x_l
 
 extern "C" int p2l_softmax_fwd(const float* S, float* P, int64_t rows, int cols,
                                void* stream) {
-  const dim3 grid(cdiv(rows, 4)), block(256);
+  if (cols != 256 && cols != 512 && cols != 1024 && cols != 2048) return P2L_EUNSUP;
+  if (!S || !P || rows < 1 || (rows + 3) / 4 > (int64_t)INT32_MAX) return P2L_EINVAL;   // (the grid's x)
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   if (cols == 1024) hipLaunchKernelGGL(softmax_fwd_kernel<4>, grid, block, 0, ST(stream), S, P, (long long)rows, cols);
   else if (cols == 256) hipLaunchKernelGGL(softmax_fwd_kernel<1>, grid, block, 0, ST(stream), S, P, (long long)rows, cols);
   else if (cols == 512) hipLaunchKernelGGL(softmax_fwd_kernel<2>, grid, block, 0, ST(stream), S, P, (long long)rows, cols);
@@ -1152,7 +1161,9 @@ extern "C" int p2l_softmax_fwd(const float* S, float* P, int64_t rows, int cols,
 }
 extern "C" int p2l_softmax_bwd(const float* P, const float* dP, float* dS,
                                int64_t rows, int cols, void* stream) {
-  const dim3 grid(cdiv(rows, 4)), block(256);
+  if (cols != 256 && cols != 512 && cols != 1024 && cols != 2048) return P2L_EUNSUP;
+  if (!P || !dP || !dS || rows < 1 || (rows + 3) / 4 > (int64_t)INT32_MAX) return P2L_EINVAL;   // (the grid's x)
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   if (cols == 1024) hipLaunchKernelGGL(softmax_bwd_kernel<4>, grid, block, 0, ST(stream), P, dP, dS, (long long)rows, cols);
   else if (cols == 256) hipLaunchKernelGGL(softmax_bwd_kernel<1>, grid, block, 0, ST(stream), P, dP, dS, (long long)rows, cols);
   else if (cols == 512) hipLaunchKernelGGL(softmax_bwd_kernel<2>, grid, block, 0, ST(stream), P, dP, dS, (long long)rows, cols);
@@ -1353,7 +1364,8 @@ extern "C" int p2l_reduce_rows(const float* partial, float* out, int Bn, int n,
 
 extern "C" int p2l_affine_grid_sample(const float* src, const float* theta, float* dst, int Bn,
                                       int C, int H, int W, void* stream) {
-  if (!src || !theta || !dst || Bn < 1) return P2L_EINVAL;
+  if (!src || !theta || !dst || Bn < 1 || C < 1 || H < 1 || W < 1) return P2L_EINVAL;
+  if ((int64_t)H * W > INT32_MAX || (int64_t)Bn * H * W > (int64_t)INT32_MAX * 256) return P2L_EINVAL;
   hipLaunchKernelGGL(affine_grid_sample_kernel, dim3(cdiv((size_t)Bn * H * W, 256)), dim3(256),
                      0, ST(stream), src, theta, dst, Bn, C, H, W);
   return p2l_check_launch();
@@ -1365,14 +1377,16 @@ extern "C" size_t p2l_affine_grid_sample_bwd_ws_bytes(int Bn, int H, int W) {
 extern "C" int p2l_affine_grid_sample_bwd(const float* src, const float* theta, const float* dout,
                                           float* dsrc, float* dtheta, int Bn, int C, int H, int W,
                                           void* workspace, size_t ws_bytes, void* stream) {
-  if (!theta || !dout || Bn < 1 || (!dsrc && !dtheta)) return P2L_EINVAL;
+  if (!theta || !dout || (!dsrc && !dtheta) || (dtheta && !src)) return P2L_EINVAL;
+  if (Bn < 1 || C < 1 || H < 1 || W < 1) return P2L_EINVAL;
+  if ((int64_t)H * W > INT32_MAX || (int64_t)Bn * H * W > (int64_t)INT32_MAX * 256) return P2L_EINVAL;
+  if (dtheta && Bn > 65535) return P2L_EINVAL;                                   // (Bn is the grid's y)
+  if (dtheta && (!workspace || ws_bytes < p2l_affine_grid_sample_bwd_ws_bytes(Bn, H, W))) return P2L_EWS;
   if (dsrc)
     hipLaunchKernelGGL(affine_grid_sample_bwd_src_kernel, dim3(cdiv((size_t)Bn * H * W, 256)), dim3(256),
                        0, ST(stream), dout, theta, dsrc, Bn, C, H, W);
   if (dtheta) {
-    if (!src) return P2L_EINVAL;
     const int nblk = cdiv(H * W, 256);
-    if (!workspace || ws_bytes < p2l_affine_grid_sample_bwd_ws_bytes(Bn, H, W)) return P2L_EWS;
     hipLaunchKernelGGL(affine_grid_sample_bwd_theta_kernel, dim3(nblk, Bn), dim3(256), 0, ST(stream),
                        src, theta, dout, (float*)workspace, C, H, W);
     hipLaunchKernelGGL(affine_grid_sample_bwd_theta_finish, dim3(cdiv(Bn * 6, 64)), dim3(64), 0,

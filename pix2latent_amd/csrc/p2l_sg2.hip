@@ -542,8 +542,11 @@ extern "C" int p2l_sg2_demod_bwd(const float* s, const float* Wsq, const float* 
 extern "C" int p2l_sg2_blur_fwd_amax(const float* u, const float* d, const float* noise, float nw,
                                      const float* bias, float* y, int Bn, int H, int W, int C,
                                      const float* next_s, float* amax_out, void* stream) {
+  if (!u || !d || !bias || !y) return P2L_EINVAL;                           // (noise, next_s, amax_out may be NULL)
+  if (Bn < 1 || H < 1 || W < 1 || C < 1) return P2L_EINVAL;
   if (C % 4) return P2L_EINVAL;
   if (H % 4 || W % 4) return P2L_EINVAL;
+  if ((int64_t)Bn * (H / 4) * (W / 4) * (C / 4) > (int64_t)INT32_MAX * 256) return P2L_EINVAL;   // (the grid's x)
   const dim3 grid(cdiv((size_t)Bn * (H / 4) * (W / 4) * (C / 4), 256));
   hipLaunchKernelGGL(blur_fwd_kernel, grid, dim3(256), 0, ST(stream), u, d, noise, nw, bias, y, Bn, H, W, C,
                      amax_out ? next_s : nullptr, amax_out);
@@ -605,7 +608,10 @@ extern "C" int p2l_sg2_rows_defer_flush(void* stream) {
 }
 extern "C" int p2l_sg2_blur_bwd_amax(const float* g, float* du, int Bn, int H, int W, int C, float* amax_out,
                                      void* stream) {
+  if (!g || !du) return P2L_EINVAL;                                         // (amax_out may be NULL)
+  if (Bn < 1 || H < 1 || W < 1 || C < 1) return P2L_EINVAL;
   if (C % 4) return P2L_EINVAL;
+  if ((int64_t)Bn * ((H + 5) / 4) * ((W + 5) / 4) * (C / 4) > (int64_t)INT32_MAX * 256) return P2L_EINVAL;
   const dim3 grid(cdiv((size_t)Bn * ((H + 5) / 4) * ((W + 5) / 4) * (C / 4), 256));
   hipLaunchKernelGGL(blur_bwd_kernel, grid, dim3(256), 0, ST(stream), g, du, Bn, H, W, C, amax_out);
   return p2l_check_launch();

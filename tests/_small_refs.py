@@ -2,8 +2,8 @@
 losses and the optimiser), written from the formulas in the header comments and the reference arithmetic they cite
 -- not from the kernels.  Forwards are direct restatements; every backward is autograd through its forward in
 float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks these functions against
-independent formulations, tests/test_small_kernels_gpu.py and tests/test_loss_kernels_gpu.py hold the kernels to
-them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py and
+tests/test_glue_kernels_gpu.py hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
@@ -288,6 +288,127 @@ def conv1_dgrad(g, w_t3, H, W, K, S, pad):
     out = g.new_zeros(B, H, W, 16)
     out[..., :3] = d.permute(0, 2, 3, 1)
     return out
+
+
+# ---- glue kernels (tests/test_glue_kernels_gpu.py) -----------------------------------------------------------------
+def gemm(A, B, M, N, K, a_kmajor=False, b_kmajor=False, alpha=1.0, C0=None):
+    """C[b] = alpha * op(A[b]) op(B[b]) (+ C0[b]).  A: [batch, M, lda] (K contiguous) or, K-major, [batch, K, lda]
+    (M contiguous); B: [batch or 1, N, ldb] or [batch or 1, K, ldb]; C0: [batch, M, ldc].  Pitches may exceed the
+    row: the gap columns are not read.  -> [batch, M, N]"""
+    a = A[..., :K, :M].transpose(-1, -2) if a_kmajor else A[..., :M, :K]
+    b = B[..., :K, :N] if b_kmajor else B[..., :N, :K].transpose(-1, -2)
+    out = alpha * torch.matmul(a, b.to(a.dtype))
+    return out if C0 is None else out + C0[..., :N].to(a.dtype)
+
+
+def softmax_rows(S):                                # P = exp(S - max) / sum exp(S - max), over the last dimension
+    e = torch.exp(S - S.max(dim=-1, keepdim=True)[0].detach())
+    return e / e.sum(dim=-1, keepdim=True)
+
+
+def softmax_rows_bwd(P, dP):
+    """dS = P (dP - sum_row P dP) from the SAVED probabilities, as the kernel gets them (fp32-rounded: they need not
+    add up to 1, and hold exact zeros, so there are no logits to differentiate at).  The exception to "autograd
+    through the forward"; tests/test_small_refs.py holds it against vjp(softmax_rows) where P is the softmax itself."""
+    return P * (dP.to(P.dtype) - (P * dP.to(P.dtype)).sum(dim=-1, keepdim=True))
+
+
+def affine_relu_fwd(x, s, t):                       # a[b,p,c] = max(x[b,p,c] * s[b,c] + t[b,c], 0)
+    return torch.relu(x * s.to(x.dtype)[:, None, :] + t.to(x.dtype)[:, None, :])
+
+
+def skip_term(skip, skip_C, skip_ups, Bn, H, W, C):
+    """[B, H*W, C]: skip on channels < skip_C, zero above; skip_ups: skip is [B, 2H, 2W, *] and its 2x2 children
+    are summed (the backward of nearest x 2)"""
+    out = skip.new_zeros(Bn, H * W, C)
+    if skip_ups:
+        sk = skip.reshape(Bn, H, 2, W, 2, skip.shape[-1]).sum(dim=(2, 4))
+    else:
+        sk = skip
+    out[:, :, :skip_C] = sk.reshape(Bn, H * W, -1)[:, :, :skip_C]
+    return out
+
+
+def affine_relu_bwd(da, x, s, t, skip=None, skip_C=0, skip_ups=False, H=None, W=None):
+    """-> dx [B,P,C] (+ the skip term), ds, dt [B,C]: autograd through affine_relu_fwd (no gradient at a == 0)"""
+    dx, ds, dt = vjp(affine_relu_fwd, [x, s.to(x.dtype), t.to(x.dtype)], da)
+    if skip is not None:
+        Bn, P, C = x.shape
+        if not skip_ups:
+            H, W = P, 1
+        dx = dx + skip_term(skip.to(x.dtype), skip_C, skip_ups, Bn, H, W, C)
+    return dx, ds, dt
+
+
+def warp_coords(theta, H, W):
+    """sampling positions (ix, iy) [B, H, W] in source pixels of F.affine_grid + F.grid_sample(align_corners=False)
+    for theta [B, 6]: g0 = (2 x + 1) / W - 1, g = theta (g0x, g0y, 1), i = ((g + 1) size - 1) / 2"""
+    dt = theta.dtype
+    gx0 = ((2 * torch.arange(W, dtype=dt) + 1) / W - 1)[None, None, :]
+    gy0 = ((2 * torch.arange(H, dtype=dt) + 1) / H - 1)[None, :, None]
+    th = theta.reshape(-1, 6)[:, :, None, None]
+    gx = th[:, 0] * gx0 + th[:, 1] * gy0 + th[:, 2]
+    gy = th[:, 3] * gx0 + th[:, 4] * gy0 + th[:, 5]
+    return ((gx + 1) * W - 1) / 2, ((gy + 1) * H - 1) / 2
+
+
+def warp_corners(src, theta):
+    """the four corners of every sample: [(value [B,C,H,W] (0 outside the image), weight [B,1,H,W])] in the order
+    (y0,x0), (y0,x1), (y1,x0), (y1,x1)"""
+    B, C, H, W = src.shape
+    ix, iy = warp_coords(theta.to(src.dtype), H, W)
+    fx, fy = torch.floor(ix).detach(), torch.floor(iy).detach()
+    wx1, wy1 = ix - fx, iy - fy
+    x0, y0 = fx.long(), fy.long()
+    flat = src.reshape(B, C, H * W)
+    out = []
+    for dy, wy in ((0, 1 - wy1), (1, wy1)):
+        for dx, wx in ((0, 1 - wx1), (1, wx1)):
+            xx, yy = x0 + dx, y0 + dy
+            ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+            idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).reshape(B, 1, H * W).expand(B, C, H * W)
+            v = torch.gather(flat, 2, idx).reshape(B, C, H, W) * ok[:, None].to(src.dtype)
+            out.append((v, (wy * wx)[:, None]))
+    return out
+
+
+def affine_warp(src, theta):
+    """bilinear warp with zero padding: dst[b,c,y,x] = sum over the 4 corners of src * weight.  src [B,C,H,W],
+    theta [B,6]"""
+    return sum(v * w for v, w in warp_corners(src, theta))
+
+
+def affine_warp_bwd(src, theta, dout):              # -> dsrc [B,C,H,W], dtheta [B,6]
+    return vjp(affine_warp, [src, theta.to(src.dtype)], dout)
+
+
+FIR = (0.25, 0.75, 0.75, 0.25)
+
+
+def blur4(u):
+    """[B, H+2, W+2, C] -> [B, H, W, C]: sum_{j,i} a_j a_i u[Y+j-1, X+i-1], a = [1 3 3 1] / 4; row / column -1 are
+    zero (rows 0..H and columns 0..W of the frame hold the transposed conv's result, the last ones are zero)"""
+    B, UH, UW, C = u.shape
+    H, W = UH - 2, UW - 2
+    p = torch.cat([u.new_zeros(B, 1, UW, C), u], dim=1)
+    p = torch.cat([p.new_zeros(B, UH + 1, 1, C), p], dim=2)          # p[y + 1, x + 1] = u[y, x]
+    out = u.new_zeros(B, H, W, C)
+    for j in range(4):
+        for i in range(4):
+            out = out + (FIR[j] * FIR[i]) * p[:, j:j + H, i:i + W]
+    return out
+
+
+def sg2_blur_fwd(u, d, noise, nw, bias):
+    """y = lrelu(blur4(u) * d[b,c] + nw * noise[b,p] + bias[c]) * sqrt2; noise [B, H*W] or None"""
+    return styled_act(blur4(u).flatten(1, 2), d.to(u.dtype), None if noise is None else noise.to(u.dtype), nw,
+                      bias.to(u.dtype)).view(u.shape[0], u.shape[1] - 2, u.shape[2] - 2, u.shape[3])
+
+
+def sg2_blur_bwd(g, H, W):
+    """du [B, H+2, W+2, C] of sum(blur4(u) * g): the transpose of the FIR, the whole frame"""
+    B, C = g.shape[0], g.shape[-1]
+    return vjp(blur4, [g.new_zeros(B, H + 2, W + 2, C)], g)
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

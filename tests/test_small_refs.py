@@ -302,3 +302,170 @@ def test_pool_references_on_hand_written_ties():
     tap = R.lpips_tap_bwd(f.view(2, 24, 8), nft, lin, wt, gs).view(2, 4, 6, 8)
     pooled = R.vjp(lambda f_: F.max_pool2d(f_.permute(0, 3, 1, 2), 2), [f], dyp.permute(0, 3, 1, 2))
     assert torch.equal(R.lpips_tap_pool_bwd(f, nft, lin, wt, gs, dyp), (pooled + tap) * (f > 0))
+
+
+# ---- the glue kernels' references (tests/test_glue_kernels_gpu.py) -------------------------------------------------
+@pytest.mark.parametrize('akm,bkm', [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_gemm_layouts_and_pitches(akm, bkm):
+    """both operand layouts at pitches above the row, junk in the gap: == a triple loop written as einsum on the
+    dense operands, one B shared by the batch (leading dimension 1), alpha and the added C"""
+    g = _g(60 + 2 * akm + bkm)
+    bt, M, Nn, K = 3, 8, 6, 10
+    a = torch.randn(bt, M, K, generator=g, dtype=D)
+    b = torch.randn(bt, Nn, K, generator=g, dtype=D)
+    c0 = torch.randn(bt, M, Nn, generator=g, dtype=D)
+
+    def pitched(t, ld):
+        o = torch.full(t.shape[:-1] + (ld,), 1e30, dtype=D)
+        o[..., :t.shape[-1]] = t
+        return o
+    A = pitched(a.transpose(1, 2).contiguous(), M + 4) if akm else pitched(a, K + 8)
+    B = pitched(b.transpose(1, 2).contiguous(), Nn + 12) if bkm else pitched(b, K + 4)
+    want = torch.einsum('bmk,bnk->bmn', a, b)
+    assert (R.gemm(A, B, M, Nn, K, akm, bkm) - want).abs().max().item() < 1e-13
+    got = R.gemm(A, B, M, Nn, K, akm, bkm, -0.37, pitched(c0, Nn + 4))
+    assert (got - (-0.37 * want + c0)).abs().max().item() < 1e-13
+    shared = R.gemm(A, B[1:2], M, Nn, K, akm, bkm)
+    assert (shared - torch.einsum('bmk,nk->bmn', a, b[1])).abs().max().item() < 1e-13
+
+
+def test_softmax_rows_and_its_backward():
+    g = _g(61)
+    S = torch.randn(5, 32, generator=g, dtype=D) * 4
+    S[1] = 2.5                                                   # all equal
+    S[2] += 1e4                                                  # only the max subtraction keeps it finite
+    S[3, 7] += 800.0                                             # the others underflow to exactly 0
+    P = R.softmax_rows(S)
+    assert (P - torch.softmax(S, dim=-1)).abs().max().item() < 1e-15
+    assert (P.sum(-1) - 1).abs().max().item() < 1e-14
+    assert torch.equal(P[1], torch.full((32,), 1.0 / 32, dtype=D))
+    assert float(P[3, 7]) == 1.0 and float(P[3].sum()) == 1.0
+    dP = torch.randn(5, 32, generator=g, dtype=D)
+    want = R.vjp(R.softmax_rows, [S], dP)
+    assert (R.softmax_rows_bwd(P, dP) - want).abs().max().item() < 1e-14
+    # ... and the closed form is linear in P: on probabilities that do not sum to 1 (the fp32-rounded ones the kernel
+    # is handed) it is the expression of the header, not the gradient at some other logits
+    P2 = P * 1.25
+    assert (R.softmax_rows_bwd(P2, dP) - P2 * (dP - (P2 * dP).sum(-1, keepdim=True))).abs().max().item() == 0.0
+
+
+@pytest.mark.parametrize('skip_kind', ['none', 'same', 'half', 'zero', 'ups'])
+def test_affine_relu_bwd_is_the_written_out_formula(skip_kind):
+    g = _g(62)
+    Bn, H, W, C = 2, 3, 5, 8
+    P = H * W
+    x = torch.randn(Bn, P, C, generator=g, dtype=D)
+    s = torch.randn(Bn, C, generator=g, dtype=D)
+    t = torch.randn(Bn, C, generator=g, dtype=D)
+    da = torch.randn(Bn, P, C, generator=g, dtype=D)
+    x[0, 0, 0], s[0, 0], t[0, 0] = 2.0, 0.5, -1.0                # x s + t == +0: masked off
+    x[0, 1, 0] = -2.0
+    t[1, 3] = -100.0                                             # a whole channel masked off
+    a = R.affine_relu_fwd(x, s, t)
+    assert float(a[0, 0, 0]) == 0 and bool((a[1, :, 3] == 0).all())
+    m = ((x * s[:, None] + t[:, None]) > 0).to(D)
+    skip, skip_C, ups = None, 0, False
+    if skip_kind in ('same', 'half', 'zero'):
+        skip, skip_C = torch.randn(Bn, P, C + 4, generator=g, dtype=D), {'same': C, 'half': C // 2, 'zero': 0}[skip_kind]
+    elif skip_kind == 'ups':
+        skip, skip_C, ups = torch.randn(Bn, 2 * H, 2 * W, C, generator=g, dtype=D), C // 2, True
+    dx, ds, dt = R.affine_relu_bwd(da, x, s, t, skip, skip_C, ups, H, W)
+    want = m * da * s[:, None]
+    if skip_kind in ('same', 'half', 'zero'):
+        want[:, :, :skip_C] += skip[:, :, :skip_C]
+    elif ups:
+        for yy in range(H):
+            for xx in range(W):
+                kids = skip[:, 2 * yy:2 * yy + 2, 2 * xx:2 * xx + 2, :skip_C].sum(dim=(1, 2))
+                want[:, yy * W + xx, :skip_C] += kids
+    assert (dx - want).abs().max().item() < 1e-13
+    assert (ds - (m * da * x).sum(1)).abs().max().item() < 1e-13
+    assert (dt - (m * da).sum(1)).abs().max().item() < 1e-13
+    assert float(ds[1, 3]) == 0 and float(dt[1, 3]) == 0
+    if skip_kind == 'none':
+        assert float(dx[0, 0, 0]) == 0
+
+
+def _random_thetas(g, Bn, scale=0.35):
+    return (torch.eye(2, 3, dtype=D).view(1, 6) + scale * torch.randn(Bn, 6, generator=g, dtype=D))
+
+
+@pytest.mark.parametrize('C,H,W', [(1, 8, 8), (3, 16, 32), (3, 24, 40), (1, 37, 53)])
+def test_affine_warp_is_affine_grid_plus_grid_sample(C, H, W):
+    g = _g(63)
+    Bn = 4
+    src = torch.randn(Bn, C, H, W, generator=g, dtype=D)
+    theta = _random_thetas(g, Bn)
+    theta[0] = torch.tensor([1.0, 0, 0, 0, 1.0, 0], dtype=D)                  # identity: the image itself
+    theta[1] = torch.tensor([0.0, 0, 5.0, 0, 0.0, 0], dtype=D)                # every sample outside: exactly 0
+    dout = torch.randn(Bn, C, H, W, generator=g, dtype=D)
+
+    def torch_warp(s_, th_):
+        grid = F.affine_grid(th_.view(-1, 2, 3), list(s_.shape), align_corners=False)
+        return F.grid_sample(s_, grid, mode='bilinear', padding_mode='zeros', align_corners=False)
+    got, want = R.affine_warp(src, theta), torch_warp(src, theta)
+    assert (got - want).abs().max().item() < 1e-12
+    assert (got[0] - src[0]).abs().max().item() < 1e-13 and bool((got[1] == 0).all())
+    dsrc, dth = R.affine_warp_bwd(src, theta, dout)
+    wsrc, wth = R.vjp(torch_warp, [src, theta], dout)
+    assert (dsrc - wsrc).abs().max().item() < 1e-12
+    # (not image 0: with every sample ON a pixel centre the warp has a kink in theta at each of them, and which side
+    #  a formulation differentiates depends on the last bit of its coordinate; d src has no such kink)
+    assert ((dth - wth).abs() / (1 + wth.abs()))[1:].max().item() < 1e-11
+    # the corner weights of a sample add up to 1, corner values outside the image are zero
+    cs = R.warp_corners(torch.ones_like(src), theta)
+    assert (sum(w for _, w in cs) - 1).abs().max().item() < 1e-13
+    assert bool((cs[0][0][1] == 0).all())
+
+
+@pytest.mark.parametrize('H,W', [(4, 4), (4, 8), (8, 4), (8, 12), (16, 4)])
+def test_sg2_blur_is_conv2d_and_the_oracles_upfirdn(H, W):
+    g = _g(64)
+    Bn, C = 2, 4
+    u = torch.randn(Bn, H + 2, W + 2, C, generator=g, dtype=D)
+    u[:, H + 1] = 0
+    u[:, :, W + 1] = 0
+    k1 = torch.tensor([1.0, 3.0, 3.0, 1.0], dtype=D)
+    k = torch.outer(k1, k1) / 16.0                                           # [1 3 3 1]^2 / 64 * 4
+    real = u[:, :H + 1, :W + 1].permute(0, 3, 1, 2)                          # the transposed conv's result
+    want = F.conv2d(F.pad(real, [1, 1, 1, 1]).reshape(Bn * C, 1, H + 3, W + 3), k.view(1, 1, 4, 4))
+    want = want.view(Bn, C, H, W).permute(0, 2, 3, 1)
+    got = R.blur4(u)
+    assert got.shape == (Bn, H, W, C) and (got - want).abs().max().item() < 1e-13
+    ora = stylegan2_ref.upfirdn2d(real, stylegan2_ref.make_kernel([1, 3, 3, 1]).double() * 4, pad=(1, 1))
+    assert (got - ora.permute(0, 2, 3, 1)).abs().max().item() < 1e-13
+    # the activation around it: the oracle's noise injection and fused leaky ReLU
+    d = torch.rand(Bn, C, generator=g, dtype=D) + 0.5
+    noise = torch.randn(Bn, H * W, generator=g, dtype=D)
+    bias = torch.randn(C, generator=g, dtype=D)
+    for nz, nw in ((noise, 0.3), (noise, 0.0), (None, 0.3)):
+        y = R.sg2_blur_fwd(u, d, nz, nw, bias)
+        pre = want.permute(0, 3, 1, 2) * d[:, :, None, None]
+        if nz is not None:
+            pre = pre + nw * nz.view(Bn, 1, H, W)
+        assert (y.permute(0, 3, 1, 2) - stylegan2_ref.fused_leaky_relu(pre, bias)).abs().max().item() < 1e-13
+    # the transpose: <blur(u), g> == <u, blur^T g> for a FULL frame u; row H+1 and column W+1 of du are reached from
+    # the last real row and column and are not zero
+    gr = torch.randn(Bn, H, W, C, generator=g, dtype=D)
+    du = R.sg2_blur_bwd(gr, H, W)
+    full = torch.randn(Bn, H + 2, W + 2, C, generator=g, dtype=D)
+    assert abs((R.blur4(full) * gr).sum().item() - (full * du).sum().item()) < 1e-10
+    assert bool((du[:, H + 1, 1:] != 0).all()) and bool((du[:, 1:, W + 1] != 0).all())
+    assert (du[:, H + 1, W + 1] - gr[:, H - 1, W - 1] / 16).abs().max().item() < 1e-15
+
+
+def test_warp_general_seeds_stay_under_the_exclusion_cap():
+    """the thetas tests/test_glue_kernels_gpu.py draws for its general warp cases leave fewer than 1 % of the samples
+    within the coordinate bound of an integer -- on the reference alone, before any kernel is asked"""
+    import _pin
+    import test_glue_kernels_gpu as T
+    try:
+        for Cc, H, W in T.WARP_GENERAL:
+            for sd in range(_pin.SEEDS + 3):
+                _pin._DRAW['seed'] = sd
+                theta = T._general_thetas(T._gen(208, Cc, H, W)).to(D)
+                near, bx, by = T._near_integer(theta, H, W)
+                assert float(near.float().mean(dim=(1, 2)).max()) < T.WARP_CAP, (Cc, H, W, sd)
+                assert float(bx.max()) < 4096 and float(by.max()) < 4096           # the bound itself: < 2^-12 pixels
+    finally:
+        _pin._DRAW['seed'] = 0
