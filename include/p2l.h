@@ -50,7 +50,7 @@ extern "C" {
  *   p2l_sg2_pixelnorm_fwd/_bwd, p2l_sg2_bias_lrelu_fwd, p2l_sg2_lrelu_bwd, p2l_sg2_demod_fwd/_bwd,
  *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
  *   p2l_add_inplace, p2l_sg2_noise_relayout, p2l_area_pool3_to_nhwc16, p2l_area_pool_nchw,
- *   p2l_area_unpool16_add_nchw3.
+ *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd.
  * Every OTHER entry point checks only what its own comment states (a shape or alignment constraint, an unsupported
  * size): it does not test its pointers or its batch size, and a caller must not rely on it to. */
 
@@ -1104,6 +1104,25 @@ int p2l_sg2_noise_reg_bwd(const float* noises, const int32_t* res, int n_layers,
                           float* dnoises, const void* ws, size_t ws_bytes, void* stream);
 int p2l_sg2_noise_normalize(float* noises, const int32_t* res, int n_layers, int Bn, void* ws, size_t ws_bytes,
                             void* stream);
+
+/* Whitened-PCA prior on a latent (csrc/p2l_latent_prior.hip).  w [B][L][D] fp32 (W+ rows; L = 1
+ * for a plain vector), basis A [K][D] fp64, mean [D] fp64, layer_w [L] fp64, all on the device.  With
+ * x = (p_space && w < 0) ? 5 w : w (exact in fp64; -0.0 and 0 take slope 1), d = x - mean and
+ * v[b,l,k] = sum_j A[k,j] d[b,l,j]:   loss[b] = sum_l layer_w[l] (1 / K) sum_k v[b,l,k]^2, fp64, rounded once to fp32.
+ * _fwd takes the basis TRANSPOSED (basis_t [D][K], element A[k,j] at basis_t[j * K + k]) and leaves v (fp64 [B * L][K])
+ * in the workspace; _bwd takes the basis as it is (basis [K][D]), reads w and the workspace AS THE FORWARD LEFT IT, and
+ * writes dw[b,l,j] = gloss[b] (NULL = 1) * slope(w[b,l,j]) * (2 layer_w[l] / K) * sum_k A[k,j] v[b,l,k], fp64, rounded
+ * once; gloss is applied last, so gloss = 2 or -1 scale the result bit for bit.  Every sum runs in an order that
+ * follows from (D, K, L) alone: a candidate's loss and dw do not depend on B, on its row, on the stream or on the
+ * call.  Launches: forward 2, backward 1, whatever B is; no atomics, no memset.
+ * P2L_EINVAL (a NULL w / basis / mean / layer_w / loss / dw; B, L or K < 1; K > D; D not a multiple of 64 or above 512;
+ * B > 65535; L > 1048576; w of _fwd not 16-byte aligned) and P2L_EWS (NULL, not 8-byte aligned or short workspace) are returned before any launch;
+ * p2l_latent_prior_ws_bytes is host-only (B * L * K * 8) and 0 for sizes the launches refuse. */
+size_t p2l_latent_prior_ws_bytes(int B, int L, int K);
+int p2l_latent_prior_fwd(const float* w, const double* basis_t, const double* mean, const double* layer_w, int B, int L,
+                         int D, int K, int p_space, float* loss, void* ws, size_t ws_bytes, void* stream);
+int p2l_latent_prior_bwd(const float* w, const double* basis, const double* layer_w, const float* gloss, int B, int L,
+                         int D, int K, int p_space, const void* ws, size_t ws_bytes, float* dw, void* stream);
 
 
 #ifdef __cplusplus

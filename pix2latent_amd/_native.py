@@ -313,6 +313,7 @@ EXPORTS = [
     'p2l_poisson_blend_ws_bytes', 'p2l_poisson_blend',
     'p2l_sg2_noise_reg_ws_bytes', 'p2l_sg2_noise_reg_fwd', 'p2l_sg2_noise_reg_bwd', 'p2l_sg2_noise_normalize',
     'p2l_area_pool3_to_nhwc16', 'p2l_area_pool_nchw', 'p2l_area_unpool16_add_nchw3',
+    'p2l_latent_prior_ws_bytes', 'p2l_latent_prior_fwd', 'p2l_latent_prior_bwd',
 ]
 
 _lib = None
@@ -349,7 +350,7 @@ def lib():
                      'p2l_packed_weight_floats', 'p2l_packed_subpix_weight_floats', 'p2l_attn_fwd_ws_bytes', 'p2l_affine_grid_sample_bwd_ws_bytes',
                      'p2l_attn_bwd_dv_ws_bytes', 'p2l_attn_bwd_qk_ws_bytes', 'p2l_color_adjust_ws_bytes',
                      'p2l_gram_f64_ws_bytes', 'p2l_gram_f64_wide_ws_bytes', 'p2l_poisson_blend_ws_bytes',
-                     'p2l_sg2_noise_reg_ws_bytes'):
+                     'p2l_sg2_noise_reg_ws_bytes', 'p2l_latent_prior_ws_bytes'):
             getattr(_lib, name).restype = C.c_size_t
         # (64-bit sizes: without argtypes ctypes would pass them as C int)
         # the small entry points that take an int64_t count or a float: a bare Python number would travel as C int
@@ -391,6 +392,9 @@ def lib():
         _lib.p2l_area_pool3_to_nhwc16.argtypes = [vp, vp, i32, i32, i32, i32, vp]
         _lib.p2l_area_pool_nchw.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
         _lib.p2l_area_unpool16_add_nchw3.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+        _lib.p2l_latent_prior_ws_bytes.argtypes = [i32, i32, i32]
+        _lib.p2l_latent_prior_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
+        _lib.p2l_latent_prior_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp]
     return _lib
 
 

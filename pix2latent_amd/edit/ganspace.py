@@ -179,13 +179,8 @@ def gram_f64_wide(x, rows, cols, ld):
     return gram, colsum
 
 
-def w_covariance(model, num_samples, chunk_rows=65536):
-    """(C [512, 512], mean [512]) of w = model.mapping(z), z ~ N(0, I), float64 on the CPU.
-
-    z is drawn with torch.randn on the CPU generator in chunks of `chunk_rows` rows, so under one
-    torch.manual_seed the draws depend on (num_samples, chunk_rows) only.  Each chunk is mapped on the device
-    and goes through p2l_gram_f64_wide once; the Grams and column sums are added in float64 on the device in
-    chunk order, C = (G - s s^T / N) / (N - 1).  Only one chunk of w exists at a time."""
+def _mapped_covariance(model, num_samples, chunk_rows, p_space):
+    from ..loss_functions import to_p_space
     if num_samples < 2:
         raise ValueError('num_samples must be at least 2')
     if chunk_rows < 1:
@@ -197,6 +192,8 @@ def w_covariance(model, num_samples, chunk_rows=65536):
         for start in range(0, num_samples, chunk_rows):
             n = min(chunk_rows, num_samples - start)
             w = model.mapping(torch.randn(n, W_DIM)).contiguous()
+            if p_space:
+                w = to_p_space(w)                    # fp32: the samples are these rounded values
             g, cs = gram_f64_wide(w, n, W_DIM, W_DIM)
             G += g
             s += cs
@@ -204,6 +201,23 @@ def w_covariance(model, num_samples, chunk_rows=65536):
     G, s = G.cpu(), s.cpu()
     C = (G - torch.outer(s, s) / num_samples) / (num_samples - 1)
     return C, s / num_samples
+
+
+def w_covariance(model, num_samples, chunk_rows=65536):
+    """(C [512, 512], mean [512]) of w = model.mapping(z), z ~ N(0, I), float64 on the CPU.
+
+    z is drawn with torch.randn on the CPU generator in chunks of `chunk_rows` rows, so under one
+    torch.manual_seed the draws depend on (num_samples, chunk_rows) only.  Each chunk is mapped on the device
+    and goes through p2l_gram_f64_wide once; the Grams and column sums are added in float64 on the device in
+    chunk order, C = (G - s s^T / N) / (N - 1).  Only one chunk of w exists at a time."""
+    return _mapped_covariance(model, num_samples, chunk_rows, False)
+
+
+def p_covariance(model, num_samples, chunk_rows=65536):
+    """(C [512, 512], mean [512]) of x = to_p_space(model.mapping(z)), float64 on the CPU: the statistics of the
+    P_N prior (`LF.LatentPrior.stylegan2`, DESIGN.md section 13).  The chunk loop and the draws of `w_covariance`;
+    the slope-5 map is one fp32 torch op on the chunk (the samples ARE its rounded values), each chunk goes through p2l_gram_f64_wide."""
+    return _mapped_covariance(model, num_samples, chunk_rows, True)
 
 
 def components_from_covariance(C, num_components):

@@ -179,6 +179,214 @@ class NoiseRegularizer(object):
 
 
 # ---------------------------------------------------------------------------
+# Whitened-PCA prior on a latent: W+ / z / the class vector
+# ---------------------------------------------------------------------------
+EIG_FLOOR = 2.0 ** -40      # of the largest eigenvalue: below it an fp64 eigh cannot tell an eigenvalue from zero
+
+
+def to_p_space(w):
+    """x = 5 w where w < 0, else w: the inverse of the StyleGAN2 mapping network's last leaky ReLU (slope 0.2), in
+    the dtype of w (5 w rounds in fp32; the prior's kernels form it in fp64, where it is exact).  -0.0 and 0 take
+    slope 1"""
+    return torch.where(w < 0, w * 5.0, w)
+
+
+def _rows3(w):
+    """[B, D] -> [B, 1, D]"""
+    if w.dim() == 2:
+        return w.unsqueeze(1)
+    if w.dim() != 3:
+        raise ValueError('the latent is [B, D] or [B, L, D], got %s' % (tuple(w.shape),))
+    return w
+
+
+def latent_prior_torch(w, basis, mean, layer_weights=None, p_space=True):
+    """The definition in torch ops, on any device.  w [B, L, D] (or [B, D]: L = 1), basis A [K, D], mean [D],
+    layer_weights [L] (None: 1 / L each):
+        x = 5 w where p_space and w < 0, else w;  d = x - mean;  v = d A^T;  P[b] = sum_l a_l (1 / K) sum_k v[b,l,k]^2
+    in fp64, rounded once to fp32.  The CPU path of `latent_prior` and the comparison point of
+    tools/bench_latent_prior.py."""
+    w = _rows3(w)
+    B, L, D = w.shape
+    A = torch.as_tensor(basis, dtype=torch.float64).to(w.device)
+    m = torch.as_tensor(mean, dtype=torch.float64).to(w.device)
+    if layer_weights is None:
+        a = torch.full((L,), 1.0 / L, dtype=torch.float64, device=w.device)
+    else:
+        a = torch.as_tensor(layer_weights, dtype=torch.float64).to(w.device)
+    if A.dim() != 2 or A.size(1) != D or m.shape != (D,) or a.shape != (L,):
+        raise ValueError('latent_prior_torch: w %s, basis %s, mean %s, layer weights %s'
+                         % (tuple(w.shape), tuple(A.shape), tuple(m.shape), tuple(a.shape)))
+    x = w.double()
+    if p_space:
+        x = torch.where(w < 0, x * 5.0, x)
+    v = (x - m) @ A.t()
+    return (((v * v).sum(2) / A.size(0)) * a).sum(1).float()
+
+
+class _LatentPriorFn(torch.autograd.Function):
+    """P [B] of w [B, L, D] through p2l_latent_prior_fwd / _bwd.  The workspace (v, fp64) is a tensor of this call,
+    saved for the backward: nothing is shared between lanes or with a captured graph, nothing waits for the host."""
+
+    @staticmethod
+    def forward(ctx, w, prior):
+        from . import ops
+        x = w.detach()
+        basis, basis_t, mean, layer_w = prior._device_tensors(x.device, x.size(1))
+        loss, ws = ops.latent_prior_fwd(x, basis_t, mean, layer_w, prior.p_space)
+        ctx.save_for_backward(x, ws, basis, layer_w)
+        ctx.p_space = prior.p_space
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        from . import ops
+        x, ws, basis, layer_w = ctx.saved_tensors
+        return ops.latent_prior_bwd(x, basis, layer_w, ctx.p_space, ws, gloss.float().contiguous()), None
+
+
+def latent_prior(w, prior):
+    """P [B] fp32 of the latent w ([B, L, D] or [B, D]) under `prior` (a `LatentPrior`; its `weight` is NOT applied),
+    differentiable in w.  Device tensors run the HIP kernels, CPU tensors `latent_prior_torch`."""
+    if not w.is_cuda:
+        return latent_prior_torch(w, prior.basis, prior.mean, prior.layer_weights, prior.p_space)
+    shape = w.shape
+    w = _rows3(w)
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    if w.size(2) != prior.dim or (prior.layer_weights is not None and w.size(1) != prior.layer_weights.numel()):
+        raise ValueError('latent_prior: a latent %s under a prior of dimension %d%s'
+                         % (tuple(shape), prior.dim, '' if prior.layer_weights is None
+                            else ' with %d layer weights' % prior.layer_weights.numel()))
+    return _LatentPriorFn.apply(w, prior)
+
+
+class LatentPrior(object):
+    """`weight * P(x)` per candidate, P the mean squared whitened coordinate of the latent:
+        P[b] = sum_l a_l (1 / K) sum_k (A (x[b,l] - mean))_k^2,   A = Lambda_K^-1/2 V_K^T
+    from the top K eigenpairs of a covariance, so that E[P] = 1 for latents of that distribution.  The
+    `regularizer=` of a latent variable (`var_manager.register('z', ..., regularizer=LF.LatentPrior.stylegan2(model))`);
+    with `p_space` the latent first goes back through the mapping network's last leaky ReLU (`to_p_space`): the
+    P_N / P_N+ prior of Zhu et al., "Improved StyleGAN Embedding" (2020).  Built by one of the constructors below.
+
+    basis [K, D], mean [D], layer_weights [L] or None (1 / L each, for whatever L the latent has) are fp64 on the
+    CPU; the device copies (the basis in both orientations) are made once per device."""
+
+    def __init__(self, basis, mean, weight=1.0, layer_weights=None, p_space=False, device='cuda'):
+        import hashlib
+        self.basis = torch.as_tensor(basis, dtype=torch.float64).cpu().contiguous()
+        self.mean = torch.as_tensor(mean, dtype=torch.float64).cpu().contiguous()
+        if self.basis.dim() != 2 or self.mean.shape != (self.basis.size(1),):
+            raise ValueError('basis is [K, D] and mean [D], got %s and %s'
+                             % (tuple(self.basis.shape), tuple(self.mean.shape)))
+        self.num_components, self.dim = self.basis.shape
+        if layer_weights is not None:
+            layer_weights = torch.as_tensor(layer_weights, dtype=torch.float64).cpu().reshape(-1).contiguous()
+        self.layer_weights = layer_weights
+        self.weight = float(weight)
+        self.p_space = bool(p_space)
+        self.device = torch.device(device)
+        h = hashlib.sha1(self.basis.numpy().tobytes())
+        h.update(self.mean.numpy().tobytes())
+        self._digest = h.hexdigest()
+        self._on_device = {}
+        if self.device.type == 'cuda' and torch.cuda.is_available():
+            self._device_tensors(self.device, None)
+
+    # ---- constructors
+    @classmethod
+    def from_covariance(cls, C, mean, num_components=None, weight=1.0, layer_weights=None, p_space=False,
+                        device='cuda'):
+        """C [D, D] and mean [D] of x (of `to_p_space(w)` when p_space).  The top `num_components` (None: all)
+        eigenpairs of an fp64 `torch.linalg.eigh`; components with lambda_k < 2^-40 lambda_1 are dropped with a
+        warning, and `num_components` above the kept rank is reduced to it."""
+        C = torch.as_tensor(C, dtype=torch.float64).cpu()
+        D = C.shape[0]
+        if C.dim() != 2 or C.shape[1] != D:
+            raise ValueError('C must be square, got %s' % (tuple(C.shape),))
+        if num_components is not None and num_components < 1:
+            raise ValueError('num_components must be at least 1, got %d' % num_components)
+        lam, V = torch.linalg.eigh(C)
+        lam, V = lam.flip(0), V.flip(1)
+        if not lam[0] > 0:
+            raise ValueError('the covariance has no positive eigenvalue')
+        kept = int((lam >= EIG_FLOOR * lam[0]).sum())
+        if kept < D:
+            warnings.warn('LatentPrior: %d of %d components have an eigenvalue below 2^-40 of the largest and are '
+                          'dropped' % (D - kept, D))
+        K = kept if num_components is None else min(int(num_components), kept)
+        basis = (V[:, :K] / lam[:K].sqrt()).t().contiguous()
+        return cls(basis, mean, weight, layer_weights, p_space, device)
+
+    @classmethod
+    def from_samples(cls, x, num_components=None, weight=1.0, layer_weights=None, p_space=False, device='cuda'):
+        """from samples x [N, D] (already in P space when p_space): mean and unbiased covariance in fp64"""
+        x = torch.as_tensor(x).detach().double().cpu()
+        if x.dim() != 2 or x.size(0) < 2:
+            raise ValueError('samples are [N >= 2, D], got %s' % (tuple(x.shape),))
+        N_, D = x.shape
+        if N_ <= D:
+            warnings.warn('LatentPrior.from_samples: %d samples of dimension %d: the covariance has rank %d at most'
+                          % (N_, D, N_ - 1))
+        mean = x.mean(0)
+        xc = x - mean
+        C = xc.t() @ xc / (N_ - 1)
+        return cls.from_covariance(C, mean, num_components, weight, layer_weights, p_space, device)
+
+    @classmethod
+    def standard_normal(cls, dim, weight=1.0, device='cuda'):
+        """identity basis, zero mean: P = |z|^2 / dim (BigGAN z, StyleGAN2 z)"""
+        return cls(torch.eye(dim, dtype=torch.float64), torch.zeros(dim, dtype=torch.float64), weight, None, False,
+                   device)
+
+    @classmethod
+    def stylegan2(cls, model, num_components=512, num_samples=100000, weight=1.0, layer_weights=None):
+        """the P_N+ prior of a StyleGAN2: statistics of to_p_space(mapping(z)) from `num_samples` draws
+        (`edit.ganspace.p_covariance`, z on the CPU generator), cached on the model per
+        (num_components, num_samples)"""
+        from .edit import ganspace
+        cache = getattr(model, '_latent_prior_stats', None)
+        if cache is None:
+            cache = model._latent_prior_stats = {}
+        key = (num_components, num_samples)
+        if key not in cache:
+            C, mean = ganspace.p_covariance(model, num_samples)
+            base = cls.from_covariance(C, mean, num_components, 1.0, None, True, model._dev)
+            cache[key] = (base.basis, base.mean)
+        basis, mean = cache[key]
+        return cls(basis, mean, weight, layer_weights, True, model._dev)
+
+    # ----
+    def _device_tensors(self, device, L):
+        """(basis [K, D], basis_t [D, K], mean [D], layer weights [L] or None for L = None) fp64 on `device`"""
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        for key in ((device, None), (device, L)):
+            if key in self._on_device:
+                continue
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('LatentPrior: first use on %s inside a graph capture; call it once eagerly' % device)
+            if key[1] is None:
+                b = self.basis.to(device)
+                self._on_device[key] = (b, b.t().contiguous(), self.mean.to(device))
+            elif self.layer_weights is None:
+                self._on_device[key] = torch.full((L,), 1.0 / L, dtype=torch.float64).to(device)
+            else:
+                self._on_device[key] = self.layer_weights.to(device)
+        return self._on_device[(device, None)] + (self._on_device.get((device, L)) if L is not None else None,)
+
+    def graph_key(self):
+        """what a captured step bakes in of this term (optimizer/base_optimizer.py `_graph_key`)"""
+        lw = None if self.layer_weights is None else tuple(self.layer_weights.tolist())
+        return ('LatentPrior', self.dim, self.num_components, lw, self.weight, self.p_space, self._digest)
+
+    def __call__(self, x):
+        return self.weight * latent_prior(x, self)
+
+
+# ---------------------------------------------------------------------------
 # `lpips_size`: the LPIPS term on an area-pooled image (the StyleGAN2 projector's 256^2; DESIGN.md section 12)
 # ---------------------------------------------------------------------------
 POOL_FACTORS = (1, 2, 4, 8, 16)

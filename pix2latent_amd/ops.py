@@ -498,3 +498,40 @@ def noise_reg_ws_pooled(ws, sizes, B):
             s, k = s // 2, k + 1
     first = B * (levels + items) * 4            # fp64 pairs, counted in floats
     return ws[first:first + B * P].view(B, P)
+
+
+# ---- whitened-PCA latent prior (csrc/p2l_latent_prior.hip) ----
+def _f64_ptr(t, what, numel):
+    assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == numel, \
+        '%s: expect %d contiguous fp64 values' % (what, numel)
+    return C.c_void_p(t.data_ptr())
+
+
+def latent_prior_ws_bytes(B, L, K):
+    return _lib().p2l_latent_prior_ws_bytes(int(B), int(L), int(K))
+
+
+def latent_prior_fwd(w, basis_t, mean, layer_w, p_space):
+    """w [B, L, D] fp32 device, basis_t [D, K] / mean [D] / layer_w [L] fp64 device ->
+    (P [B] fp32, workspace for latent_prior_bwd: v [B * L, K] fp64)"""
+    B, L, D = w.shape
+    K = basis_t.size(1)
+    # (sizes the library refuses get a one-value workspace: the refusal is the library's, before any launch)
+    ws = torch.empty(max(latent_prior_ws_bytes(B, L, K) // 8, 1), dtype=torch.float64, device=w.device)
+    loss = torch.empty(B, dtype=torch.float32, device=w.device)
+    N.check(_lib().p2l_latent_prior_fwd(N.ptr(w), _f64_ptr(basis_t, 'basis_t', D * K), _f64_ptr(mean, 'mean', D),
+                                        _f64_ptr(layer_w, 'layer_w', L), B, L, D, K, int(bool(p_space)),
+                                        N.ptr(loss), C.c_void_p(ws.data_ptr()), ws.numel() * 8, N.stream()),
+            'p2l_latent_prior_fwd')
+    return loss, ws
+
+
+def latent_prior_bwd(w, basis, layer_w, p_space, ws, gloss=None):
+    """gloss [B] (None = ones) times dP/dw [B, L, D], from w, basis [K, D] and the workspace latent_prior_fwd left"""
+    B, L, D = w.shape
+    K = basis.size(0)
+    dw = torch.empty_like(w)
+    N.check(_lib().p2l_latent_prior_bwd(N.ptr(w), _f64_ptr(basis, 'basis', K * D), _f64_ptr(layer_w, 'layer_w', L),
+                                        N.ptr(gloss), B, L, D, K, int(bool(p_space)), C.c_void_p(ws.data_ptr()),
+                                        ws.numel() * 8, N.ptr(dw), N.stream()), 'p2l_latent_prior_bwd')
+    return dw
