@@ -41,7 +41,7 @@ extern "C" {
  * P2L_EINVAL and BEFORE anything is launched, a NULL where a pointer is required, Bn < 1, any other size < 1
  * (p2l_reduce_rows: n < 0), a row pitch below the row length, and Bn > 65535 where the batch is a y/z grid
  * dimension (p2l_scale_bwd, p2l_affine_relu_bwd, p2l_arb_finish, p2l_gemm(_ws), p2l_affine_grid_sample_bwd with
- * dtheta, p2l_sg2_styled_act_bwd(_amax), p2l_weight_map, p2l_l1_loss_fwd/_bwd):
+ * dtheta, p2l_sg2_styled_act_bwd(_amax), p2l_weight_map, p2l_l1_loss_fwd/_bwd, p2l_l2_loss_fwd/_bwd):
  *   p2l_gemm(_ws), p2l_softmax_fwd/_bwd, p2l_affine_relu_bwd, p2l_arb_finish, p2l_affine_grid_sample(_bwd),
  *   p2l_sg2_blur_fwd(_amax), p2l_sg2_blur_bwd(_amax),
  *   p2l_linear_fwd(_ld), p2l_linear_bwd(_ld), p2l_cbn_fold_fwd/_bwd, p2l_scale_bwd, p2l_relu_mask,
@@ -50,7 +50,7 @@ extern "C" {
  *   p2l_sg2_pixelnorm_fwd/_bwd, p2l_sg2_bias_lrelu_fwd, p2l_sg2_lrelu_bwd, p2l_sg2_demod_fwd/_bwd,
  *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
  *   p2l_add_inplace, p2l_sg2_noise_relayout, p2l_area_pool3_to_nhwc16, p2l_area_pool_nchw,
- *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd.
+ *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd, p2l_l2_loss_fwd/_bwd, p2l_adam_step_sched.
  * Every OTHER entry point checks only what its own comment states (a shape or alignment constraint, an unsupported
  * size): it does not test its pointers or its batch size, and a caller must not rely on it to. */
 
@@ -606,6 +606,20 @@ int p2l_l1_loss_bwd(const float* img16, const float* target, const float* weight
                     const float* loss_mask, const float* wsum,
                     const float* gscale, float* dimg16, int Bn, int H, int W,
                     int accumulate, void* stream);
+/* Weighted L2 (csrc/p2l_pixel.hip), same layouts and contract:                        */
+/*   loss[b] = sum_{c,p} w*(t-o)^2 / wsum[b]   (w = weight*mask, wsum[b] from p2l_weight_sum)               */
+/*   dimg (+)= (gscale[b] / wsum[b]) * 2 * w * (o-t)                                                      */
+/* accumulate = 0 writes floats 0..2 and zeroes floats 3..15 of every pixel; accumulate = 1 adds into      */
+/* floats 0..3 (+0 into float 3) and leaves 4..15 alone.  The sum runs over block partials in an order     */
+/* that depends on (H, W) only.                                                                            */
+int p2l_l2_loss_nblk(int H, int W); /* floats per sample needed in `partial` */
+int p2l_l2_loss_fwd(const float* img16, const float* target, const float* weight,
+                    const float* loss_mask, const float* wsum, float* loss,
+                    float* partial, int Bn, int H, int W, void* stream);
+int p2l_l2_loss_bwd(const float* img16, const float* target, const float* weight,
+                    const float* loss_mask, const float* wsum,
+                    const float* gscale, float* dimg16, int Bn, int H, int W,
+                    int accumulate, void* stream);
 
 /* LPIPS tap (lpips.LPIPS(spatial=True) restated in oracle/lpips_ref.py):     */
 /*   nf = f / (||f||_2 + 1e-10) ; d[p] = sum_c lin[c]*(nf_o - nf_t)^2         */
@@ -669,6 +683,13 @@ int p2l_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
 int p2l_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
                       float lr, float beta1, float beta2, float eps,
                       int32_t* step_counters, int n_counters, void* stream);
+/* p2l_adam_step_dev with the learning rate read on the device: lr = lr_table[min(step_counters[0], n_lr - 1)],
+ * step_counters[0] being the 0-based count of completed steps (read before the counters advance).  lr_table is
+ * device memory, n_lr >= 1.  Otherwise the same arithmetic, expression by expression: a constant table gives the
+ * bits of p2l_adam_step_dev. */
+int p2l_adam_step_sched(float* p, const float* g, float* m, float* v, int64_t n,
+                        const float* lr_table, int n_lr, float beta1, float beta2, float eps,
+                        int32_t* step_counters, int n_counters, void* stream);
 int p2l_clamp(float* p, int64_t n, float lo, float hi, void* stream);
 
 /* out[b] = a[b] * scale / (div ? div[b] : 1) */

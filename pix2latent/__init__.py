@@ -9,12 +9,12 @@ import sys
 
 import pix2latent_amd as _impl
 from pix2latent_amd import *  # noqa: F401,F403
-from pix2latent_amd import distribution, VariableManager, save_variables  # noqa: F401
+from pix2latent_amd import distribution, VariableManager, save_variables, LRSchedule  # noqa: F401
 from pix2latent_amd import edit  # noqa: F401  (the README's `pix2latent.edit.BigGANLatentEditor`)
 
 __version__ = _impl.__version__
 
-for _name in ('distribution', 'variable_manager', 'loss_functions', 'optimizer', 'model',
+for _name in ('distribution', 'variable_manager', 'lr_schedule', 'loss_functions', 'optimizer', 'model',
               'utils', 'utils.image', 'utils.misc', 'utils.function_hooks', 'utils.video', 'parallel',
               'optimizer.closure', 'optimizer.base_optimizer',
               'optimizer.gradient_optimizer', 'optimizer.basincma_optimizer',

@@ -314,6 +314,7 @@ EXPORTS = [
     'p2l_sg2_noise_reg_ws_bytes', 'p2l_sg2_noise_reg_fwd', 'p2l_sg2_noise_reg_bwd', 'p2l_sg2_noise_normalize',
     'p2l_area_pool3_to_nhwc16', 'p2l_area_pool_nchw', 'p2l_area_unpool16_add_nchw3',
     'p2l_latent_prior_ws_bytes', 'p2l_latent_prior_fwd', 'p2l_latent_prior_bwd',
+    'p2l_l2_loss_nblk', 'p2l_l2_loss_fwd', 'p2l_l2_loss_bwd', 'p2l_adam_step_sched',
 ]
 
 _lib = None
@@ -360,6 +361,10 @@ def lib():
         _lib.p2l_clamp.argtypes = [vp, i64_, f32_, f32_, vp]
         _lib.p2l_adam_step.argtypes = [vp, vp, vp, vp, i64_, f32_, f32_, f32_, f32_, i32, vp]
         _lib.p2l_adam_step_dev.argtypes = [vp, vp, vp, vp, i64_, f32_, f32_, f32_, f32_, vp, i32, vp]
+        _lib.p2l_adam_step_sched.argtypes = [vp, vp, vp, vp, i64_, vp, i32, f32_, f32_, f32_, vp, i32, vp]
+        _lib.p2l_l2_loss_nblk.argtypes = [i32, i32]
+        _lib.p2l_l2_loss_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+        _lib.p2l_l2_loss_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
         _lib.p2l_reduce_rows.argtypes = [vp, vp, i32, i32, f32_, vp, i32, vp]
         _lib.p2l_vec_scale_div.argtypes = [vp, vp, vp, i32, f32_, vp]
         _lib.p2l_sg2_bias_lrelu_fwd.argtypes = [vp, vp, f32_, i32, i32, vp]

@@ -928,14 +928,14 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long l
 // step, so a captured HIP graph of the inner step can be replayed (optimizer/base_optimizer.py).
 // Same arithmetic as adam_kernel; the bias corrections are formed in double like torch does
 // on the host.  The counters are advanced by a second, one-block kernel behind it.
-__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long long n,
-                                float lr, float beta1, float beta2, float eps,
-                                const int* __restrict__ steps) {
+// (one body for the two kernels below: `lr` and `done`, the count of completed steps, are thread 0's)
+__device__ __forceinline__ void adam_dev_body(float* p, const float* g, float* m, float* v, long long n, float lr,
+                                              int done, float beta1, float beta2, float eps) {
   // the bias corrections once per block (two double-precision pow per ELEMENT were most of the 110 us this kernel
   // took on StyleGAN2's 8.4 M noise values); same values, same arithmetic per element
   __shared__ float bc[2];
   if (threadIdx.x == 0) {
-    const double step = (double)(steps[0] + 1);
+    const double step = (double)(done + 1);
     const double bc1 = 1.0 - pow((double)beta1, step);
     const double bc2 = 1.0 - pow((double)beta2, step);
     bc[0] = (float)((double)lr / bc1);
@@ -953,6 +953,25 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, lo
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
   p[i] = p[i] - step_size * (mi / denom);
+}
+__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long long n,
+                                float lr, float beta1, float beta2, float eps,
+                                const int* __restrict__ steps) {
+  adam_dev_body(p, g, m, v, n, lr, threadIdx.x == 0 ? steps[0] : 0, beta1, beta2, eps);
+}
+// adam_dev_kernel with the learning rate of a schedule: lr_table[min(completed steps, n_lr - 1)], read once per
+// block.  Everything else is the one body, so a constant table gives adam_dev_kernel's bits; the table is made on
+// the host (optimizer schedules need cos: no device trigonometry).
+__global__ void adam_sched_kernel(float* p, const float* g, float* m, float* v, long long n,
+                                  const float* __restrict__ lr_table, int n_lr, float beta1, float beta2,
+                                  float eps, const int* __restrict__ steps) {
+  int done = 0;
+  float lr = 0.f;
+  if (threadIdx.x == 0) {
+    done = steps[0];
+    lr = lr_table[done < 0 ? 0 : (done < n_lr ? done : n_lr - 1)];
+  }
+  adam_dev_body(p, g, m, v, n, lr, done, beta1, beta2, eps);
 }
 __global__ void counters_advance_kernel(int* c, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1414,6 +1433,17 @@ extern "C" int p2l_adam_step_dev(float* p, const float* g, float* m, float* v, i
   if (!p || !g || !m || !v || !step_counters || n_counters < 1 || n < 1) return P2L_EINVAL;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), p, g, m,
                      v, (long long)n, lr, beta1, beta2, eps, (const int*)step_counters);
+  hipLaunchKernelGGL(counters_advance_kernel, dim3(cdiv(n_counters, 256)), dim3(256), 0,
+                     ST(stream), (int*)step_counters, n_counters);
+  return p2l_check_launch();
+}
+extern "C" int p2l_adam_step_sched(float* p, const float* g, float* m, float* v, int64_t n,
+                                   const float* lr_table, int n_lr, float beta1, float beta2, float eps,
+                                   int32_t* step_counters, int n_counters, void* stream) {
+  if (!p || !g || !m || !v || !lr_table || !step_counters || n_lr < 1 || n_counters < 1 || n < 1)
+    return P2L_EINVAL;
+  hipLaunchKernelGGL(adam_sched_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), p, g, m,
+                     v, (long long)n, lr_table, n_lr, beta1, beta2, eps, (const int*)step_counters);
   hipLaunchKernelGGL(counters_advance_kernel, dim3(cdiv(n_counters, 256)), dim3(256), 0,
                      ST(stream), (int*)step_counters, n_counters);
   return p2l_check_launch();

@@ -53,6 +53,8 @@ class LaneScratch(object):
         # a loss with `lpips_size`: its arena and staging above are at the pooled size, the L1 term's are here
         self.full16 = self.dfull16 = self.l1_part = None
         self.full_cap, self.full_res = -1, None
+        # the block partial sums of an L2 pixel term beside a full-resolution LPIPS term
+        self.pix_part = None
 
 
 class Scratch(object):
@@ -96,6 +98,15 @@ class Scratch(object):
             dfull16 = torch.empty(B, H, W, 16, device=device, dtype=torch.float32)
             part = torch.empty(B * n_part, device=device, dtype=torch.float32)
             s.full16, s.dfull16, s.l1_part, s.full_cap, s.full_res = full16, dfull16, part, B, (H, W)
+            self.generation += 1
+        return s
+
+    def grow_part(self, n_floats, device):
+        """the current lane's record with `pix_part` of at least n_floats (the block partial sums of the L2 pixel
+        term); a re-allocation bumps `generation`"""
+        s = self.here()
+        if s.pix_part is None or s.pix_part.numel() < n_floats:
+            s.pix_part = torch.empty(n_floats, device=device, dtype=torch.float32)
             self.generation += 1
         return s
 

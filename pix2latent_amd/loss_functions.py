@@ -13,8 +13,10 @@ example (`ProjectionLoss`, reference loss_functions.py:86-100) runs as
     sum is evaluated as a sum at tap resolution against the adjoint-resized
     weight map (exact identity; only summation order differs).
 
-The un-weighted / L2 variants are not on the hot path and use plain torch ops on
-the tensor's own device.
+The weighted L2 pixel term (the StyleGAN2 projector's MSE; `ReconstructionLoss('l2')`,
+`ProjectionLoss(pixel_loss='l2', pixel_weight=...)`) runs as `p2l_l2_loss_fwd/_bwd`
+(csrc/p2l_pixel.hip).  The un-weighted variants, and CPU tensors, use
+plain torch ops on the tensor's own device.
 """
 import ctypes as C
 import os
@@ -738,6 +740,24 @@ class _LossEngine(object):
         self._pooled[key] = ent
         return ent
 
+    def weight_sum(self, target, weight, loss_mask):
+        """-> wsum [B] of conformed tensors (p2l_weight_sum), memoised on their identity and version as `pooled`
+        does: once per chunk and generation.  For a pixel term that runs without a cache slot."""
+        key = (self._ident(target), self._ident(weight), self._ident(loss_mask), 'wsum')
+        ent = self._pooled.pop(key, None)
+        if ent is None:
+            if len(self._pooled) >= 2 * self.MAX_SLOTS:
+                self._pooled.pop(next(iter(self._pooled)))
+            B, HW3 = target.size(0), target[0].numel()
+            wsum = torch.empty(B, device=target.device, dtype=torch.float32)
+            N.check(self.lib.p2l_weight_sum(N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum), B, HW3, N.stream()),
+                    'p2l_weight_sum')
+            ent = _Pooled(None, None, wsum, (target, weight, loss_mask))
+        else:
+            ent.guard.reader()
+        self._pooled[key] = ent
+        return ent.wsum
+
     def _same_content(self, target, weight, loss_mask, use_lpips, B):
         """A generation of a CMA run starts from FRESH variables (reference base_cma_optimizer.py:79):
         new target / weight tensors with the old CONTENT; and the chunks of one population carry copies
@@ -911,17 +931,170 @@ class _ProjLossFn(torch.autograd.Function):
         return dout, None, None, None, None, None, None
 
 
-def _apply_pooled(eng, output, target, weight, loss_mask, beta, mode, f):
+def _pixel_factor(weight, loss_mask):
+    """the reference's one-channel-weight quirk (see `_apply`): 3 for a one-channel `weight * loss_mask`"""
+    wc, mc = _channels(weight), _channels(loss_mask)
+    return 3.0 if (wc == 1 and mc in (None, 1)) else 1.0
+
+
+def _stale_error():
+    return N.NativeError('loss workspace was reused by a later forward before '
+                         'backward(); use one loss object per in-flight graph')
+
+
+def _apply_l2(eng, output, target, weight, loss_mask):
+    """the weighted L2 term alone (`ReconstructionLoss('l2')`), factor 3 of a one-channel weight included"""
+    B = output.size(0)
+    factor = _pixel_factor(weight, loss_mask)
+    loss = _L2LossFn.apply(output, eng.bind('target', target, B, like=output),
+                           eng.bind('weight', weight, B, like=output),
+                           eng.bind('loss_mask', loss_mask, B, like=output), eng)
+    return loss if factor == 1.0 else factor * loss
+
+
+class _L2LossFn(torch.autograd.Function):
+    """L2w(out, target, weight * loss_mask) [B] through p2l_l2_loss_fwd / _bwd: stage the image (one launch), the
+    weight sum once per (target, weight, loss_mask) identity, the kernels, unpack.  The staging and the block
+    partials are the lane's full-resolution scratch (`lanes.Scratch.grow_full`); no LPIPS arena is allocated."""
+
+    @staticmethod
+    def forward(ctx, output, target, weight, loss_mask, eng):
+        lib = eng.lib
+        B, _, H, W = output.shape
+        out_c = output.contiguous().float()
+        wsum = eng.weight_sum(target, weight, loss_mask)
+        s = eng._scratch.grow_full(B, H, W, lib.p2l_l2_loss_nblk(H, W), output.device)
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()), 'p2l_nchw3_to_nhwc16')
+        loss = torch.empty(B, device=output.device, dtype=torch.float32)
+        N.check(lib.p2l_l2_loss_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum),
+                                    N.ptr(loss), N.ptr(s.l1_part), B, H, W, N.stream()), 'p2l_l2_loss_fwd')
+        ctx.eng, ctx.wsum = eng, wsum
+        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
+        ctx.has_mask = loss_mask is not None
+        ctx.stamp = eng._scratch.stamp()
+        eng.last_l1 = loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
+            return _L2LossFn._backward(ctx, gloss)
+
+    @staticmethod
+    def _backward(ctx, gloss):
+        eng = ctx.eng
+        lib = eng.lib
+        out_c, target, weight, loss_mask = ctx.saved_tensors
+        if not ctx.has_mask:
+            loss_mask = None
+        B, _, H, W = out_c.shape
+        if eng._scratch.stale(ctx.stamp):
+            raise _stale_error()
+        s = eng._scratch.here()
+        g = gloss.contiguous().float()
+        N.check(lib.p2l_l2_loss_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                                    N.ptr(ctx.wsum), N.ptr(g), N.ptr(s.dfull16), B, H, W, 0, N.stream()),
+                'p2l_l2_loss_bwd')
+        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dfull16), N.ptr(dout), B, H, W, N.stream()), 'p2l_nhwc16_to_nchw3')
+        return dout, None, None, None, None
+
+
+def _apply_proj_l2(eng, output, target, weight, loss_mask, beta, pixel_weight):
+    """pixel_weight * L2w + beta * LPIPSw at the output's own resolution"""
+    B = output.size(0)
+    return _ProjL2LossFn.apply(output, eng.bind('target', target, B, like=output),
+                               eng.bind('weight', weight, B, like=output),
+                               eng.bind('loss_mask', loss_mask, B, like=output), eng, float(beta),
+                               float(pixel_weight) * _pixel_factor(weight, loss_mask))
+
+
+class _ProjL2LossFn(torch.autograd.Function):
+    """The L2 term beside the plan, on the image the plan staged.  Forward: pack, the plan (use_lpips = 1: its
+    forward has no LPIPS-only form, so its full-resolution L1 pass runs too and is discarded),
+    L2, then loss = scale * l2 + beta * lp.  Backward: the plan with use_lpips = 2 writes
+    d (beta * LPIPS) into dimg16, p2l_l2_loss_bwd adds the pixel term with gscale = scale * g (accumulate = 1).
+    The weight sum is the one in the slot's cache."""
+
+    @staticmethod
+    def forward(ctx, output, target, weight, loss_mask, eng, beta, scale):
+        lib = eng.lib
+        B, _, H, W = output.shape
+        out_c = output.contiguous().float()
+        slot = eng.prepare(out_c, target, weight, loss_mask, 1)
+        nblk = lib.p2l_l2_loss_nblk(H, W)
+        s = eng._scratch.grow_part(eng._scratch.here().cap * nblk, output.device)
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, N.stream()), 'p2l_nchw3_to_nhwc16')
+        loss = torch.empty(B, device=output.device, dtype=torch.float32)
+        l1 = torch.empty_like(loss)
+        l2 = torch.empty_like(loss)
+        lp = torch.empty_like(loss)
+        # (the plan's own L1 term lands in `l1`: a by-product)
+        N.check(eng.f_fwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                          C.byref(slot.desc), N.f32(1.0), 1, B, H, W, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                          N.ptr(loss), N.ptr(l1), N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
+        wsum = C.c_void_p(slot.desc.wsum)
+        N.check(lib.p2l_l2_loss_fwd(N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), wsum,
+                                    N.ptr(l2), N.ptr(s.pix_part), B, H, W, N.stream()), 'p2l_l2_loss_fwd')
+        # loss = scale * l2 + beta * lp
+        N.check(lib.p2l_vec_scale_div(N.ptr(l2), None, N.ptr(loss), B, N.f32(scale), N.stream()),
+                'p2l_vec_scale_div')
+        N.check(lib.p2l_reduce_rows(N.ptr(lp), N.ptr(loss), B, 1, N.f32(beta), None, 1, N.stream()),
+                'p2l_reduce_rows')
+        if len(eng._lanes) > 1:
+            slot.used()
+        ctx.eng, ctx.slot, ctx.beta, ctx.scale = eng, slot, beta, scale
+        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
+        ctx.has_mask = loss_mask is not None
+        ctx.stamp = eng._scratch.stamp()
+        eng.last_l1, eng.last_lpips = l2, lp
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
+            return _ProjL2LossFn._backward(ctx, gloss)
+
+    @staticmethod
+    def _backward(ctx, gloss):
+        eng = ctx.eng
+        lib = eng.lib
+        out_c, target, weight, loss_mask = ctx.saved_tensors
+        if not ctx.has_mask:
+            loss_mask = None
+        B, _, H, W = out_c.shape
+        if eng._scratch.stale(ctx.stamp):
+            raise _stale_error()
+        s = eng._scratch.here()
+        g = gloss.contiguous().float()
+        N.check(eng.f_bwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                          C.byref(ctx.slot.desc), N.f32(ctx.beta), 2, N.ptr(g), B, H, W, N.ptr(s.ws),
+                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()), 'p2l_%sloss_bwd' % eng.prefix)
+        gl = g if ctx.scale == 1.0 else g * ctx.scale
+        N.check(lib.p2l_l2_loss_bwd(N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                                    C.c_void_p(ctx.slot.desc.wsum), N.ptr(gl), N.ptr(s.dimg16), B, H, W, 1,
+                                    N.stream()), 'p2l_l2_loss_bwd')
+        if len(eng._lanes) > 1:
+            ctx.slot.used()
+        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dimg16), N.ptr(dout), B, H, W, N.stream()), 'p2l_nhwc16_to_nchw3')
+        return dout, None, None, None, None, None, None
+
+
+def _apply_pooled(eng, output, target, weight, loss_mask, beta, mode, f, pixel='l1', pixel_weight=1.0):
     """`_apply` with the LPIPS term at [H/f, W/f]: L1w(out, ...) + beta * LPIPSw(pool_f(out), pool_f(target),
     pool_f(weight * loss_mask)); mode 2 = the second term alone.  The one-channel-weight factor 3 of the reference
-    (see `_apply`) belongs to the L1 term."""
+    (see `_apply`) belongs to the L1 term.  pixel = 'l2': pixel_weight * L2w(out, ...) in the place of the L1 term
+    (its weight travels with the factor 3)."""
     B = output.size(0)
     wc, mc = _channels(weight), _channels(loss_mask)
     l1_factor = 3.0 if (mode == 0 and wc == 1 and mc in (None, 1)) else 1.0
+    if pixel == 'l2':
+        l1_factor = l1_factor * float(pixel_weight)
     return _PooledLossFn.apply(output, eng.bind('target', target, B, like=output),
                                eng.bind('weight', weight, B, like=output),
                                eng.bind('loss_mask', loss_mask, B, like=output), eng, float(beta), l1_factor,
-                               mode, f)
+                               mode, f, pixel)
 
 
 class _PooledLossFn(torch.autograd.Function):
@@ -930,8 +1103,12 @@ class _PooledLossFn(torch.autograd.Function):
     [pack, L1].  Backward: the plan, [L1], then ONE launch that writes d out = dL1 + expand_f(dLPIPS) / f^2."""
 
     @staticmethod
-    def forward(ctx, output, target, weight, loss_mask, eng, beta, l1_factor, mode, f):
+    def forward(ctx, output, target, weight, loss_mask, eng, beta, l1_factor, mode, f, pixel='l1'):
         lib = eng.lib
+        # the pixel term's entry points: L1, or L2 (same layouts and contract)
+        pix_nblk, pix_fwd, pix_name = (
+            (lib.p2l_l2_loss_nblk, lib.p2l_l2_loss_fwd, 'p2l_l2_loss_fwd') if pixel == 'l2' else
+            (lib.p2l_l1_loss_nblk, lib.p2l_l1_loss_fwd, 'p2l_l1_loss_fwd'))
         B, _, H, W = output.shape
         h, w = H // f, W // f
         out_c = output.contiguous().float()
@@ -949,13 +1126,13 @@ class _PooledLossFn(torch.autograd.Function):
                           C.byref(slot.desc), N.f32(1.0), 1, B, h, w, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
                           N.ptr(loss), N.ptr(l1), N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
         if want_l1:
-            eng._scratch.grow_full(B, H, W, lib.p2l_l1_loss_nblk(H, W), output.device)
+            eng._scratch.grow_full(B, H, W, pix_nblk(H, W), output.device)
             l1 = torch.empty_like(loss)
             N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()),
                     'p2l_nchw3_to_nhwc16')
-            N.check(lib.p2l_l1_loss_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                                        N.ptr(ent.wsum), N.ptr(l1), N.ptr(s.l1_part), B, H, W, N.stream()),
-                    'p2l_l1_loss_fwd')
+            N.check(pix_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                            N.ptr(ent.wsum), N.ptr(l1), N.ptr(s.l1_part), B, H, W, N.stream()),
+                    pix_name)
             # loss = l1_factor * l1 + beta * lp
             N.check(lib.p2l_vec_scale_div(N.ptr(l1), None, N.ptr(loss), B, N.f32(l1_factor), N.stream()),
                     'p2l_vec_scale_div')
@@ -964,7 +1141,7 @@ class _PooledLossFn(torch.autograd.Function):
         if len(eng._lanes) > 1:
             slot.used()
         ctx.eng, ctx.slot, ctx.ent = eng, slot, ent
-        ctx.beta, ctx.l1_factor, ctx.want_l1, ctx.f = beta, l1_factor, want_l1, f
+        ctx.beta, ctx.l1_factor, ctx.want_l1, ctx.f, ctx.pixel = beta, l1_factor, want_l1, f, pixel
         ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
         ctx.has_mask = loss_mask is not None
         ctx.stamp = eng._scratch.stamp()
@@ -999,13 +1176,14 @@ class _PooledLossFn(torch.autograd.Function):
         if ctx.want_l1:
             gl = g if ctx.l1_factor == 1.0 else g * ctx.l1_factor
             dfull = s.dfull16
-            N.check(lib.p2l_l1_loss_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                                        N.ptr(ent.wsum), N.ptr(gl), N.ptr(dfull), B, H, W, 0, N.stream()),
-                    'p2l_l1_loss_bwd')
+            pix_bwd = lib.p2l_l2_loss_bwd if ctx.pixel == 'l2' else lib.p2l_l1_loss_bwd
+            N.check(pix_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
+                            N.ptr(ent.wsum), N.ptr(gl), N.ptr(dfull), B, H, W, 0, N.stream()),
+                    'p2l_%s_loss_bwd' % ctx.pixel)
         dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
         N.check(lib.p2l_area_unpool16_add_nchw3(N.ptr(s.dimg16), N.ptr(dfull), N.ptr(dout), B, H, W, f,
                                                 N.stream()), 'p2l_area_unpool16_add_nchw3')
-        return dout, None, None, None, None, None, None, None, None
+        return dout, None, None, None, None, None, None, None, None, None
 
 
 _VGG_PARAMS = {}
@@ -1063,10 +1241,21 @@ class ProjectionLoss(nn.Module):
         `weight * loss_mask` are area-pooled to in front of the LPIPS term, as the StyleGAN2 projector does with
         256 (`area_pool_torch`; the factor H // lpips_size is 1, 2, 4, 8 or 16).  The L1 term stays at full
         resolution.
+    pixel_loss, pixel_weight: the loss is `pixel_weight * pixel term + beta * LPIPS term` with the weighted 'l1'
+        (the reference) or 'l2' (the StyleGAN2 projector's MSE term) pixel term; both fixed at construction.
+        `ProjectionLoss(lpips_net='vgg', beta=1, pixel_loss='l2', pixel_weight=mse, lpips_size=256)` is the
+        projector's image loss.
     """
 
-    def __init__(self, lpips_net='alex', beta=10, weights=None, device='cuda', lpips_size=None):
+    def __init__(self, lpips_net='alex', beta=10, weights=None, device='cuda', lpips_size=None,
+                 pixel_loss='l1', pixel_weight=1.0):
         super().__init__()
+        if pixel_loss not in ('l1', 'l2'):
+            raise ValueError("pixel_loss is 'l1' or 'l2', got %r" % (pixel_loss,))
+        pixel_weight = float(pixel_weight)
+        if not (0.0 <= pixel_weight < float('inf')):
+            raise ValueError('pixel_weight must be finite and not negative, got %r' % (pixel_weight,))
+        self.pixel_loss, self.pixel_weight = pixel_loss, pixel_weight
         self.beta = beta
         self.lpips_size = None if lpips_size is None else int(lpips_size)
         self._engine = _LossEngine(_vgg_params(lpips_net, weights, device))
@@ -1076,9 +1265,23 @@ class ProjectionLoss(nn.Module):
 
     def __call__(self, output, target, weight=None, loss_mask=None):
         f = lpips_pool_factor(output.shape, self.lpips_size)
+        eng, a = self._engine, self.pixel_weight
+        if self.pixel_loss == 'l2':
+            if f == 1:
+                return _apply_proj_l2(eng, output, target, weight, loss_mask, self.beta, a)
+            return _apply_pooled(eng, output, target, weight, loss_mask, self.beta, 0, f, 'l2', a)
+        if a == 1.0:
+            if f == 1:
+                return _apply(eng, output, target, weight, loss_mask, self.beta, 0)
+            return _apply_pooled(eng, output, target, weight, loss_mask, self.beta, 0, f)
+        if a == 0.0:                            # the LPIPS term alone
+            lp = _apply(eng, output, target, weight, loss_mask, 1.0, 2) if f == 1 else \
+                _apply_pooled(eng, output, target, weight, loss_mask, 1.0, 2, f)
+            return self.beta * lp
+        # a * L1 + beta * LPIPS = a * (L1 + (beta / a) * LPIPS): the rescaling route of the factor 3
         if f == 1:
-            return _apply(self._engine, output, target, weight, loss_mask, self.beta, 0)
-        return _apply_pooled(self._engine, output, target, weight, loss_mask, self.beta, 0, f)
+            return a * _apply(eng, output, target, weight, loss_mask, self.beta / a, 0)
+        return a * _apply_pooled(eng, output, target, weight, loss_mask, self.beta / a, 0, f)
 
 
 class ReconstructionLoss(nn.Module):
@@ -1091,7 +1294,7 @@ class ReconstructionLoss(nn.Module):
             self._native = True
         elif loss_type in ['l2', 2]:
             self.loss_fn = l2_loss
-            self._native = False
+            self._native = True
         else:
             raise ValueError('Unknown loss_type {}'.format(loss_type))
         self._engine = None
@@ -1101,6 +1304,8 @@ class ReconstructionLoss(nn.Module):
         if self._native and weight is not None and _native_ok(output, target, weight):
             if self._engine is None:
                 self._engine = _LossEngine(None)
+            if self.loss_fn is l2_loss:
+                return _apply_l2(self._engine, output, target, weight, loss_mask)
             return _apply(self._engine, output, target, weight, loss_mask, 0.0, 1)
         loss = self.loss_fn(output, target)
         if weight is not None:

@@ -335,6 +335,9 @@ class _BaseOptimizer(SearchLoopMixin):
         and a new Adam state at the old addresses), and a model or loss that frees or re-allocates
         a lane's workspace (lanes.Scratch.generation) leaves the old pointers baked into the
         captured launches
+        ... and the learning rate of every optimised variable (`FusedAdam.state_key`): a constant is a launch
+        argument, a schedule a device table; `edit_variable(name, {'learning_rate': ...})` + `initialize()` with
+        `reuse_buffers` keeps every address and must still re-capture
         ... and the regularisers of the input variables: their launches and constants (layer list, weight)
         are part of the capture
         ... and the loss object with its `lpips_size`: which launches a step makes of it (the pooled LPIPS term or

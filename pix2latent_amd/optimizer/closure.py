@@ -232,6 +232,25 @@ def _step_fused(model, vars, loss_fn, optimize, max_batch_size, grad_scale, popu
     return torch.cat(outs), LazyLosses(torch.cat(losses)), {}
 
 
+def _apply_schedules(opt):
+    """a parameter group registered with an `LRSchedule` gets the rate of its parameter's next step: the
+    schedule's value at the number of steps that parameter has completed (what p2l_adam_step_sched reads on
+    the device).  The count is the closure's own, kept in the group as 'lr_step' (`_count_steps`): an optimizer
+    class need not keep one (torch.optim.SGD does not).  Groups without a schedule are left alone."""
+    for group in getattr(opt, 'param_groups', ()):
+        sched = group.get('lr_schedule', None)
+        if sched is not None:
+            group['lr'] = sched.value(group.get('lr_step', 0))
+
+
+def _count_steps(opt):
+    """behind `opt.step`, before the gradients are cleared: a scheduled group whose parameter took part in the
+    step (it has a gradient: the parameters of the other chunks have none) has completed one more"""
+    for group in getattr(opt, 'param_groups', ()):
+        if group.get('lr_schedule', None) is not None and any(p.grad is not None for p in group['params']):
+            group['lr_step'] = group.get('lr_step', 0) + 1
+
+
 def _step_generic(model, vars, loss_fn, optimize, max_batch_size, grad_scale, population):
     outs, indiv_losses = [], []
     for ci, _vars in enumerate(split_vars(vars, size=max_batch_size)):
@@ -261,7 +280,9 @@ def _step_generic(model, vars, loss_fn, optimize, max_batch_size, grad_scale, po
 
         # (4) optimize
         if optimize:
+            _apply_schedules(_vars.opt)
             _vars.opt.step(closure)
+            _count_steps(_vars.opt)
             _vars.opt.zero_grad()
         else:
             with torch.no_grad():

@@ -23,6 +23,7 @@ import torch
 import torch.optim as optim
 
 from . import distribution as dist
+from .lr_schedule import LRSchedule
 from .utils.attrdict import AttrDict as edict
 
 
@@ -59,17 +60,36 @@ class FusedAdam(object):
             else:
                 m, v = torch.zeros_like(buf), torch.zeros_like(buf)
                 steps = torch.zeros(buf.size(0), dtype=torch.int32, device=buf.device)
-            self.entries[e['name']] = dict(buf=buf, lr=e['lr'], m=m, v=v, steps=steps)
+            sched = e['lr'] if isinstance(e['lr'], LRSchedule) else None
+            ent = dict(buf=buf, lr=e['lr'], m=m, v=v, steps=steps)
+            if sched is not None:
+                # (the device table is made here, eagerly: a captured step only reads it)
+                ent.update(lr=sched.value(0), sched=sched, lr_table=sched.device_table(buf.device))
+            self.entries[e['name']] = ent
             for leaf in e['leaves']:
-                self.param_groups.append({'params': [leaf], 'lr': e['lr']})
+                group = {'params': [leaf], 'lr': ent['lr']}
+                if sched is not None:
+                    group['lr_schedule'] = sched
+                self.param_groups.append(group)
 
     def state_key(self):
         """device addresses of everything a captured step writes through this optimizer
         (moments and step counters): part of the HIP-graph key of the inner step.  With
         `reuse_buffers` a re-initialised optimizer keeps them; without, a new optimizer that
-        happens to sit on recycled variable addresses is told apart by these."""
-        return tuple((n, e['m'].data_ptr(), e['v'].data_ptr(), e['steps'].data_ptr())
+        happens to sit on recycled variable addresses is told apart by these.
+        ... and the learning rate of every variable, which a captured launch bakes in: the constant itself, or the
+        schedule's `graph_key()` (its table's address and length are launch arguments)."""
+        return tuple((n, e['m'].data_ptr(), e['v'].data_ptr(), e['steps'].data_ptr(),
+                      e['sched'].graph_key() if 'sched' in e else float(e['lr']))
                      for n, e in sorted(self.entries.items()))
+
+    def current_lr(self, name):
+        """per-sample learning rate of the NEXT step of variable `name`, for inspection: reads the step counters
+        (a host sync)"""
+        e = self.entries[name]
+        if 'sched' not in e:
+            return [float(e['lr'])] * e['steps'].numel()
+        return [e['sched'].value(s) for s in self.state_steps(name)]
 
     def zero_grad(self, set_to_none=True):
         for g in self.param_groups:
@@ -87,6 +107,15 @@ class FusedAdam(object):
         e = self.entries[name]
         p = e['buf'][i0:i1]
         g = grad.contiguous()
+        if 'sched' in e:
+            tab = e['lr_table']
+            N.check(self._lib.p2l_adam_step_sched(N.ptr(p), N.ptr(g), N.ptr(e['m'][i0:i1]),
+                                                  N.ptr(e['v'][i0:i1]), N.i64(p.numel()), N.ptr(tab),
+                                                  int(tab.numel()), N.f32(self.betas[0]), N.f32(self.betas[1]),
+                                                  N.f32(self.eps),
+                                                  C.c_void_p(e['steps'][i0:i1].data_ptr()), int(i1 - i0),
+                                                  N.stream()), 'p2l_adam_step_sched')
+            return
         N.check(self._lib.p2l_adam_step_dev(N.ptr(p), N.ptr(g), N.ptr(e['m'][i0:i1]),
                                             N.ptr(e['v'][i0:i1]), N.i64(p.numel()), N.f32(e['lr']),
                                             N.f32(self.betas[0]), N.f32(self.betas[1]),
@@ -192,6 +221,9 @@ class VariableManager():
         in the reference (variable_manager.py:83-146), plus `regularizer`: a callable
         `r(x [b, *shape]) -> [b]` the closure adds to the per-sample loss of an input
         variable (after the hooks, before the backward; e.g. `LF.NoiseRegularizer`).
+        `learning_rate` is a float or an `LRSchedule` (lr_schedule.py): the rate of a sample's k-th
+        step is then `schedule.value(k - 1)`, on the fused path and on the generic one alike; a
+        fresh optimizer (every `initialize()`) starts the schedule again.
         """
         if variable_name in self.variable_info:
             print('variable `{}`` already exists.'.format(variable_name))
@@ -298,11 +330,13 @@ class VariableManager():
 
             if spec['optimizer'] is not optim.Adam:
                 all_adam = False
+            sched = spec['learning_rate'] if isinstance(spec['learning_rate'], LRSchedule) else None
             for d in data:
-                params_to_optimize.append(
-                    {'params': d.requires_grad_(True),
-                     'lr': spec['learning_rate']}
-                )
+                group = {'params': d.requires_grad_(True),
+                         'lr': spec['learning_rate'] if sched is None else sched.value(0)}
+                if sched is not None:
+                    group['lr_schedule'] = sched     # (the closure sets 'lr' from it before every opt.step)
+                params_to_optimize.append(group)
             fused_entries.append({'name': v, 'buf': buf, 'lr': spec['learning_rate'],
                                   'leaves': data})
 
