@@ -51,6 +51,15 @@ extern "C" {
  *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
  *   p2l_add_inplace, p2l_sg2_noise_relayout, p2l_area_pool3_to_nhwc16, p2l_area_pool_nchw,
  *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd, p2l_l2_loss_fwd/_bwd, p2l_adam_step_sched.
+ * The conv launches -- p2l_conv_fwd(_ex), p2l_conv_dgrad_arb(_ws) -- refuse in the same way, for the operands that
+ * are PRESENT, a pitch below the row it pitches: x_ld < Cin; y_ld, yp_ld, res_ld, mask_ld, P2LArb.x_ld < n_store;
+ * pro_bstride, P2LArb.st_bstride, P2LConvExtra.oscale_bstride in 1 .. row - 1 (0 = shared by the images);
+ * P2LArb.skip_ld < skip_C or skip_C > n_store; P2LArb.ds / dt NULL, dsdt_bstride < Cout or no multiple of four; on a
+ * split-K launch with the 16-byte finish, P2LArb.x_ld / skip_ld no multiple of four; and a w_floats > 0 below the
+ * packed size of the launch.  A split-K
+ * launch whose finish would be the scalar kernel (some pitch FIELD, even that of an absent operand, no multiple of
+ * four) and that carries P2LConvExtra.oscale / noise or P2L_ACT_LRELU_SQRT2 returns P2L_EUNSUP: that kernel has
+ * none of the three terms.
  * Every OTHER entry point checks only what its own comment states (a shape or alignment constraint, an unsupported
  * size): it does not test its pointers or its batch size, and a caller must not rely on it to. */
 

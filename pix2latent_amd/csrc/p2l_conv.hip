@@ -1269,7 +1269,9 @@ static int effective_splitk(const P2LConv* d);
 // the 16-byte finish kernel of a split-K launch: every pitch it touches a multiple of four floats
 // (descriptor only: p2l_conv_amax_slots and the launch must agree)
 static bool finish_v4_ok(const P2LConv* d) {
-#ifdef P2L_AB_SCALAR_FINISH           // (A/B build: the 4-byte finish kernel for every split-K launch)
+#ifdef P2L_AB_SCALAR_FINISH           // (A/B build: the 4-byte finish kernel for every split-K launch.  That kernel has no
+                                      //  oscale / noise / leaky-ReLU term: such a launch -- StyleGAN2's styled convs -- is
+                                      //  refused with P2L_EUNSUP in this build, which therefore serves BigGAN only)
   return false;
 #endif
   return d->n_store % 4 == 0 && d->Cout % 4 == 0 && d->y_ld % 4 == 0 && d->yp_ld % 4 == 0 &&
@@ -1368,6 +1370,18 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   if ((y && d->y_ld % 4) || (yp && d->yp_ld % 4) || (res && d->res_ld % 4) ||
       (mask && d->mask_ld % 4))
     return P2L_EINVAL;
+  // every pitch of an operand that is present covers the row the kernels read or write at it: a shorter one
+  // sends the stores through the neighbouring rows and past the end of the buffer
+  if ((y && d->y_ld < d->n_store) || (yp && d->yp_ld < d->n_store) || (res && d->res_ld < d->n_store) ||
+      (mask && d->mask_ld < d->n_store))
+    return P2L_EINVAL;
+  if (d->pro != P2L_PRO_NONE && d->pro_bstride != 0 && d->pro_bstride < d->Cin) return P2L_EINVAL;
+  if (arb) {
+    if (arb->x && arb->x_ld < d->n_store) return P2L_EINVAL;
+    if (arb->st_bstride != 0 && arb->st_bstride < d->n_store) return P2L_EINVAL;
+    if (arb->skip && (arb->skip_C < 0 || arb->skip_C > d->n_store || arb->skip_ld < arb->skip_C)) return P2L_EINVAL;
+  }
+  if (ex && ex->oscale && ex->oscale_bstride != 0 && ex->oscale_bstride < d->n_store) return P2L_EINVAL;
   {
     // element offsets are computed in 32 bits inside the kernel
     const int64_t px = (int64_t)d->B * d->H * d->W;
@@ -1395,8 +1409,13 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   if (ex) {
     k.oscale = ex->oscale; k.oscale_bstride = ex->oscale_bstride;
     k.noise = ex->noise; k.noise_w = ex->noise_w;
-    if (k.noise && d->y_ld != d->n_store && false) return P2L_EINVAL;
   }
+  // the scalar finish kernel of a split-K launch (conv_splitk_finish -> epilogue_quad: a pitch field that is no
+  // multiple of four, even that of an absent operand) has no demodulation, noise or leaky-ReLU term; the 16-byte
+  // one (epi_item) has all three
+  if ((k.oscale || k.noise || d->act == P2L_ACT_LRELU_SQRT2) && !finish_v4_ok(d) && !wino_shape(d) &&
+      effective_splitk(d) > 1)
+    return P2L_EUNSUP;
   if (k.partial && (arb || d->pool != P2L_POOL_NONE || d->splitk > 1)) return P2L_EUNSUP;
   if (arb) {
     // one image per tile for the in-kernel form; with split-K the finish kernel does it
@@ -1453,6 +1472,11 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     const size_t need = (use_h2 ? h2_bytes : 0) + (size_t)k.splitk * d->B * d->H * d->W * d->Cout * sizeof(float);
     if (!workspace || ws_bytes < need) return P2L_EWS;
     if (arb) k.arb_nblk = p2l_conv_arb_nblk_ws(d);      // finish kernel: one partial per quad
+    // the 16-byte finish kernel reads the fused backward's operands in 16-byte pieces, and the maxima slots were
+    // sized for it: refused here, before the slices are launched
+    if (arb && d->ups < 2 && !wino_shape(d) && finish_v4_ok(d) &&
+        (arb->x_ld % 4 || (arb->skip && arb->skip_ld % 4)))
+      return P2L_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
 
@@ -1757,9 +1781,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   }
   if (rc) return rc;
   if (k.splitk > 1) {
-    const bool arb_al = !arb || (k.arb_x_ld % 4 == 0 && (!k.arb_skip || k.arb_skip_ld % 4 == 0));
-    if (finish_v4_ok(d) && !arb_al) return P2L_EINVAL;   // (the maxima slots were sized for the 16-byte kernel)
-    if (finish_v4_ok(d)) {
+    if (finish_v4_ok(d)) {                               // (its arb pitches were checked in front of the launch)
       const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * (k.n_store >> 2);
       hipLaunchKernelGGL(conv_splitk_finish_v4, dim3(cdiv(total, 64)), dim3(256), 0, st, k);
     } else {
@@ -1816,10 +1838,17 @@ extern "C" int p2l_conv_arb_nblk_ws(const P2LConv* d) {
 
 static int dgrad_arb_unsplit(const P2LConv* d, const P2LArb* arb, const float* dy, const float* w,
                              float* dx, void* workspace, size_t ws_bytes, void* stream);
+// what p2l_arb_finish will check of ds / dt, in front of the conv launch that writes dx
+static int arb_outputs_ok(const P2LConv* d, const P2LArb* arb) {
+  if (!arb->ds || !arb->dt) return P2L_EINVAL;
+  if (arb->dsdt_bstride % 4 || arb->dsdt_bstride < d->Cout) return P2L_EINVAL;
+  return P2L_OK;
+}
 extern "C" int p2l_conv_dgrad_arb_ws(const P2LConv* d, const P2LArb* arb, const float* dy,
                                      const float* w, float* dx, void* workspace, size_t ws_bytes,
                                      void* stream) {
   if (!d || !arb || !dx) return P2L_EINVAL;
+  if (int rc0 = arb_outputs_ok(d, arb)) return rc0;
   P2LConv dd = *d;
   if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
   if (effective_splitk(&dd) <= 1) return dgrad_arb_unsplit(d, arb, dy, w, dx, workspace, ws_bytes, stream);
@@ -1836,6 +1865,7 @@ extern "C" int p2l_conv_dgrad_arb_ws(const P2LConv* d, const P2LArb* arb, const 
 static int dgrad_arb_unsplit(const P2LConv* d, const P2LArb* arb, const float* dy, const float* w,
                              float* dx, void* workspace, size_t ws_bytes, void* stream) {
   if (!d || !arb || !dx) return P2L_EINVAL;
+  if (int rc0 = arb_outputs_ok(d, arb)) return rc0;
   P2LConv dd = *d;
   dd.splitk = 1;
   if (dd.ups == 3) dd.pool = P2L_POOL_NONE;

@@ -19,7 +19,7 @@ SENT = 0x4EADBEEF                     # sentinel bit pattern (a finite float, ~1
 _RECORDS = []
 # test module -> the environment variable that names its record file (profiles/*_kernels_err.txt)
 _ERR_FILE_ENV = {'test_small_kernels_gpu': 'P2L_SMALL_ERR_FILE', 'test_loss_kernels_gpu': 'P2L_LOSS_ERR_FILE',
-                 'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE'}
+                 'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE', 'test_pw_kernels_gpu': 'P2L_PW_ERR_FILE'}
 
 
 class _Native(object):

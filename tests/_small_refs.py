@@ -2,8 +2,9 @@
 losses and the optimiser), written from the formulas in the header comments and the reference arithmetic they cite
 -- not from the kernels.  Forwards are direct restatements; every backward is autograd through its forward in
 float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks these functions against
-independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py and
-tests/test_glue_kernels_gpu.py hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py,
+tests/test_glue_kernels_gpu.py and tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
+restatements, host packers and the case tables) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
@@ -409,6 +410,665 @@ def sg2_blur_bwd(g, H, W):
     """du [B, H+2, W+2, C] of sum(blur4(u) * g): the transpose of the FIR, the whole frame"""
     B, C = g.shape[0], g.shape[-1]
     return vjp(blur4, [g.new_zeros(B, H + 2, W + 2, C)], g)
+
+
+def _cancellation_case(seed, Bn, P, Cc):
+    """x [Bn, P, C], s, t [Bn, C] in fp32.  Channels 0..15 (kind A): in 32 pixels x s + t cancels so that the twice
+    rounded fl(fl(x s) + t) is 0 but the once rounded fma(x, s, t) is the product's rounding error, of either sign.
+    Channels 16..31 (kind B, magnitudes near 2^-126): x s = (n + 1/2) 2^-149 with n odd and t = -n 2^-149 (and the
+    mirror image): fl(x s) is the even neighbour, so the twice rounded sum is 2^-149, and the once rounded one is the
+    tie 2^-150 -> 0.  The other pixels of the kind B channels hold +-64 .. 128: a is 0 or about 2^-120 there, a normal
+    number -- the bf16 pieces through which the 3x3 formats 1 and 2 are read back do not carry subnormals, so a
+    positive a below 2^-126 would read as 0 whatever the prologue decided.  Everything else is ordinary."""
+    D64 = torch.float64
+    g = torch.Generator().manual_seed(4000 + seed)
+    x = torch.randn(Bn, P, Cc, generator=g)
+    s = (0.5 + torch.rand(Bn, Cc, generator=g)) * torch.where(torch.rand(Bn, Cc, generator=g) < 0.5, -1.0, 1.0)
+    t = 0.3 * torch.randn(Bn, Cc, generator=g)
+    special = torch.zeros(Bn, P, Cc, dtype=torch.int8)
+    for b in range(Bn):
+        for c in range(32):
+            pix = torch.randperm(P, generator=g)[:32]
+            if c < 16:
+                xv = float(torch.randn(1, generator=g)) + 2.0
+                prod = torch.tensor(xv, dtype=torch.float32) * s[b, c]            # fl(x s)
+                x[b, pix, c], t[b, c] = xv, -prod
+                special[b, pix, c] = 1
+            else:
+                n = 2 * int(torch.randint(2 ** 21, 2 ** 22, (1,), generator=g)) + 1                # odd, < 2^23
+                sign = 1.0 if c % 2 == 0 else -1.0
+                x[b, :, c] = (64.0 + 64.0 * torch.rand(P, generator=g)) * torch.where(torch.rand(P, generator=g) < 0.5, -1.0, 1.0)
+                x[b, pix, c], s[b, c], t[b, c] = sign * (2 * n + 1) * 2.0 ** -24, 2.0 ** -126, -sign * n * 2.0 ** -149
+                special[b, pix, c] = 2
+    # both models of the decision on the host: fp64 holds the product exactly, and the sum wherever it cancels
+    once = (x.to(D64) * s.to(D64)[:, None] + t.to(D64)[:, None]).float()         # fma: ONE rounding
+    twice = x * s[:, None] + t[:, None]                                          # fp32 product, fp32 sum
+    A, B = special == 1, special == 2
+    assert int(A.sum()) >= 256 and int(B.sum()) >= 256
+    assert bool((twice[A] == 0).all()) and bool((once[A] != 0).all())
+    assert bool((once[A] > 0).any()) and bool((once[A] < 0).any())
+    assert bool((once[B] == 0).all()) and bool((twice[B] != 0).all())
+    assert bool((twice[B] > 0).any()) and bool((twice[B] < 0).any())
+    assert bool(((once <= 0) | (once >= 2.0 ** -126)).all())                      # every positive a is a normal number
+    return x, s, t, once > 0, twice > 0, A, B
+
+
+# ---- 1x1 convs (tests/test_pw_kernels_gpu.py) ----------------------------------------------------------------------
+# Activations are dense NHWC views [B, H, W, C] (the caller slices the pitch off), a weight is the [N, K] matrix the
+# launch applies (the forward conv's [O, I]; its transpose for the input gradient), prologue / arb vectors are
+# [1 or B, C].  Enumerations are those of include/p2l.h.
+ACT_NONE, ACT_RELU, ACT_TANH, ACT_LRELU_SQRT2 = 0, 1, 2, 3
+POOL_NONE, POOL_MAX, POOL_SUM = 0, 1, 2
+PRO_NONE, PRO_AFFINE_RELU, PRO_AFFINE = 0, 1, 2
+
+
+def fma(x, s, t):
+    """x s + t with ONE rounding in the dtype of x (fp32: through fp64, which holds the product exactly)"""
+    if x.dtype == torch.float32:
+        return (x.double() * s.double() + t.double()).float()
+    return x * s.to(x.dtype) + t.to(x.dtype)
+
+
+def pw_prologue(x, pro, s, t):
+    """-> a, and the same expression on absolute values (no ReLU)"""
+    if pro == PRO_NONE:
+        return x, x.abs()
+    s_, t_ = s.to(x.dtype)[:, None, None, :], t.to(x.dtype)[:, None, None, :]
+    a = fma(x, s_, t_)
+    return (torch.relu(a) if pro == PRO_AFFINE_RELU else a), x.abs() * s_.abs() + t_.abs()
+
+
+def quads(v):
+    """[B, H, W, C] -> the four pixels of every 2x2 quad, [B, H/2, W/2, C] each, in the order (0,0) (0,1) (1,0) (1,1)"""
+    return v[:, 0::2, 0::2], v[:, 0::2, 1::2], v[:, 1::2, 0::2], v[:, 1::2, 1::2]
+
+
+def quad_sum(v):
+    v0, v1, v2, v3 = quads(v)
+    return (v0 + v1) + (v2 + v3)
+
+
+def up2(r):                                         # nearest x 2 of [B, h, w, C]
+    return r.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+
+
+def conv1x1(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, oscale=None, noise=None, noise_w=0.0, bias=None,
+            res=None, res_ups=False, act=ACT_NONE, mask=None, n_store=None, pool=POOL_NONE, acc=None, floor=None):
+    """the 1x1 conv launch of include/p2l.h in the dtype of x, in the header's order:
+        a = prologue(x) ; v = alpha sum_k a w ; v = v oscale[b][n] + bias[n] + noise_w noise[b][pixel] + res ; act ;
+        mask ; channels < n_store ; 2x2 max / sum pool of what was stored.
+    oscale [B, N], noise [B, H, W], res [B, H, W, >= n_store] (res_ups: [B, H/2, W/2, ..]), mask like y.
+    `acc` replaces sum_k a w (a restatement's accumulator: every route feeds the same epilogue); `floor` [B, H, W, N]
+    is added to sum_k |a| |w| (h2_floor: the absolute term of the fp16 x 2 contract).
+    -> dict: y, den (sum |terms|: every operand's absolute value, activation and mask left out), yp, denp (pool sum:
+    the quad's sum; max: the quad's maximum), a, aabs"""
+    dt = x.dtype
+    w = w.to(dt)
+    Cout = w.shape[0]
+    n_store = Cout if n_store is None else n_store
+    a, aabs = pw_prologue(x, pro, s, t)
+    v = (a @ w.t() if acc is None else acc.to(dt)) * alpha
+    den = aabs @ w.abs().t()
+    den = (den if floor is None else den + floor.to(dt)) * abs(alpha)
+    if oscale is not None:
+        v = v * oscale.to(dt)[:, None, None, :]
+        den = den * oscale.to(dt).abs()[:, None, None, :]
+    if bias is not None:
+        v = v + bias.to(dt)
+        den = den + bias.to(dt).abs()
+    if noise is not None:
+        v = v + noise_w * noise.to(dt)[..., None]
+        den = den + abs(noise_w) * noise.to(dt).abs()[..., None]
+    v, den = v[..., :n_store], den[..., :n_store]
+    if res is not None:
+        r = res.to(dt)[..., :n_store]
+        r = up2(r) if res_ups else r
+        v = v + r
+        den = den + r.abs()
+    if act == ACT_RELU:
+        v = torch.relu(v)
+    elif act == ACT_TANH:
+        v = torch.tanh(v)
+    elif act == ACT_LRELU_SQRT2:
+        v = torch.where(v > 0, v * SQRT2, v * (SLOPE * SQRT2)) if dt == torch.float64 else \
+            v * torch.where(v > 0, torch.tensor(1.41421356237, dtype=dt), torch.tensor(0.2 * 1.41421356237).to(dt))
+    if mask is not None:
+        v = torch.where(mask.to(dt)[..., :n_store] > 0, v, torch.zeros_like(v))
+    out = dict(y=v, den=den, yp=None, denp=None, a=a, aabs=aabs)
+    if pool == POOL_MAX:
+        v0, v1, v2, v3 = quads(v)
+        d0, d1, d2, d3 = quads(den)
+        out['yp'] = torch.maximum(torch.maximum(v0, v1), torch.maximum(v2, v3))
+        out['denp'] = torch.maximum(torch.maximum(d0, d1), torch.maximum(d2, d3))
+    elif pool == POOL_SUM:
+        out['yp'], out['denp'] = quad_sum(v), quad_sum(den)
+    return out
+
+
+def conv1x1_arb(dy, w, x, s, t, alpha=1.0, pool_sum=False, nomask=False, skip=None, skip_C=0, skip_ups=False,
+                acc=None, floor=None):
+    """the input-gradient launch fused with the backward of a = max(x s + t, 0) (p2l_conv_dgrad_arb), in the dtype of
+    dy: da = alpha conv(dy, w) [2x2-summed when pool_sum], g = fma(x, s, t) > 0 ? da : 0 (nomask: g = da),
+    dx = g s + shortcut (channels < skip_C; skip_ups: the sum of the four children of a [B, 2H, 2W, ..] gradient),
+    ds = sum g x, dt = sum g over the pixels.  x is at the resolution of dx.
+    -> dict: dx, den_dx, ds, den_ds (sum |g x|), dt, den_dt (sum |g|), g, den_g (sum |terms| of da)"""
+    dtp = dy.dtype
+    w = w.to(dtp)
+    da = (dy @ w.t() if acc is None else acc.to(dtp)) * alpha
+    dend = dy.abs() @ w.abs().t()
+    dend = (dend if floor is None else dend + floor.to(dtp)) * abs(alpha)         # (h2_floor, as in conv1x1)
+    if pool_sum:
+        da, dend = quad_sum(da), quad_sum(dend)
+    x, s_, t_ = x.to(dtp), s.to(dtp)[:, None, None, :], t.to(dtp)[:, None, None, :]
+    g = da if nomask else torch.where(fma(x, s_, t_) > 0, da, torch.zeros_like(da))
+    dx, den = g * s_, dend * s_.abs()
+    if skip is not None and skip_C > 0:
+        sk = skip.to(dtp)[..., :skip_C]
+        ska = sk.abs()
+        if skip_ups:
+            sk, ska = quad_sum(sk), quad_sum(ska)
+        dx, den = dx.clone(), den.clone()
+        dx[..., :skip_C] += sk
+        den[..., :skip_C] += ska
+    gx = g * x
+    return dict(dx=dx, den_dx=den, ds=gx.sum(dim=(1, 2)), den_ds=gx.abs().sum(dim=(1, 2)), dt=g.sum(dim=(1, 2)),
+                den_dt=g.abs().sum(dim=(1, 2)), g=g, den_g=dend)
+
+
+def arb_finish_order32(part):
+    """partial [Bn, nblk, C] (one half) -> [Bn, C] in the order csrc/p2l_ops.hip documents for p2l_arb_finish, in
+    fp32: segment seg adds its rows seg, seg + 16, ... in four chains (row index / 16 mod 4), combined
+    ((0 + 1) + (2 + 3)); then the 16 segments in sequence"""
+    Bn, nblk, Cc = part.shape
+    segs = []
+    for seg in range(16):
+        ch = [torch.zeros(Bn, Cc) for _ in range(4)]
+        for j in range(seg, nblk, 16):
+            q = (j // 16) % 4
+            ch[q] = ch[q] + part[:, j]
+        segs.append((ch[0] + ch[1]) + (ch[2] + ch[3]))
+    out = segs[0]
+    for k in range(1, 16):
+        out = out + segs[k]
+    return out
+
+
+def npow2(v):
+    p = 1
+    while p < v:
+        p *= 2
+    return p
+
+
+def arb_sums32(g, x, H, W, pool_sum, split):
+    """ds, dt of fp32 g, x [B, Ho, Wo, C] (at the resolution of dx) for a launch on the H x W grid, the two stages
+    in the kernels' order.  Stage one, per 2x2 quad of the grid: its pixels (one under pool_sum) onto the item's
+    running sum in sequence, `sgx += g x` as a fused multiply-add, `sg += g`.  A split-K launch leaves one partial per
+    quad, row-major (either finish kernel).  An unsplit one leaves one per 128-pixel tile (choose_tile: TW =
+    min(16, W), TH = 128 / TW, one image per tile): the tile's quads row-major, eight per wave, meet in the tree
+    q ^ 1, q ^ 2, q ^ 4 and the four waves as (0 + 1) + (2 + 3) (epi_arb_reduce); tiles row-major.  Stage two:
+    p2l_arb_finish over the partials (arb_finish_order32)."""
+    def quad_partials(prod):
+        if pool_sum:
+            return prod(g, x, None)
+        acc = None
+        for gq, xq in zip(quads(g), quads(x)):
+            acc = prod(gq, xq, acc)
+        return acc
+
+    def stage(prod):
+        q = quad_partials(prod)                                           # [B, H/2, W/2, C]
+        Bn, Hq, Wq, Cc = q.shape
+        assert (Hq, Wq) == (H // 2, W // 2)
+        if split:
+            return arb_finish_order32(q.reshape(Bn, Hq * Wq, Cc))
+        TW = min(npow2(W), 16)
+        TH = min(128 // TW, npow2(H))
+        twh, thh = TW // 2, TH // 2
+        assert twh * thh == 32 and Hq % thh == 0 and Wq % twh == 0, 'one image per whole 128-pixel tile'
+        t = q.reshape(Bn, Hq // thh, thh, Wq // twh, twh, Cc).permute(0, 1, 3, 2, 4, 5)
+        t = t.reshape(Bn, -1, 4, 8, Cc)                                   # [B, tile, wave, quad of the wave, C]
+        w = ((t[:, :, :, 0] + t[:, :, :, 1]) + (t[:, :, :, 2] + t[:, :, :, 3])) + \
+            ((t[:, :, :, 4] + t[:, :, :, 5]) + (t[:, :, :, 6] + t[:, :, :, 7]))
+        return arb_finish_order32((w[:, :, 0] + w[:, :, 1]) + (w[:, :, 2] + w[:, :, 3]))
+    return (stage(lambda gq, xq, acc: gq * xq if acc is None else fma(gq, xq, acc)),
+            stage(lambda gq, xq, acc: gq if acc is None else acc + gq))
+
+
+# -- restatements of each route's accumulator, fp32 on the CPU (a [B, H, W, K] after the prologue, w [N, K]) --------
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def splitk_slices(K, kc, splitk):
+    """[(k_lo, k_hi)] of the K slices a request of `splitk` resolves to (conv_launch_impl: clamped to the chunk
+    count, then to whole chunks per slice)"""
+    nch = K // kc
+    sk = max(1, min(splitk, nch))
+    per = cdiv(nch, sk)
+    return [(z * per * kc, min(K, (z + 1) * per * kc)) for z in range(cdiv(nch, per))]
+
+
+def combine_slices(parts):
+    """the finish kernels' order: lane z sums slices z, z + 4, ...; then (z0 + z1) + (z2 + z3)"""
+    if len(parts) == 1:
+        return parts[0]
+    z = [torch.zeros_like(parts[0]) for _ in range(4)]
+    for i, p in enumerate(parts):
+        z[i % 4] = z[i % 4] + p
+    return (z[0] + z[1]) + (z[2] + z[3])
+
+
+def acc_fp32(a, w, splitk=1):
+    """route A (conv_mfma_kernel<1, ..>, exact fp32 products): one chain per output over k, per K slice"""
+    K = a.shape[-1]
+    kc = 32 if K % 32 == 0 else 16
+    wt = w.t().contiguous()
+    parts = []
+    for lo, hi in splitk_slices(K, kc, splitk):
+        acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
+        for k in range(lo, hi):
+            acc = acc + a[..., k:k + 1] * wt[k]
+        parts.append(acc)
+    return combine_slices(parts)
+
+
+def split3(x):
+    """x = h + m + l, three round-to-nearest bf16 pieces (split3 / store_bf3), as fp32 tensors"""
+    h = x.bfloat16().float()
+    r1 = x - h
+    m = r1.bfloat16().float()
+    return h, m, (r1 - m).bfloat16().float()
+
+
+def acc_bf3(a, w):
+    """route B (pw_bf3_kernel): per 16-channel step the six kept cross terms (a piece, w piece) in the kernel's
+    order (3,1) (1,3) (2,2) (2,1) (1,2) (1,1), each an fp32 sum of 16 exact products onto the accumulator"""
+    a1, a2, a3 = split3(a)
+    w1, w2, w3 = split3(w)
+    acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
+    for c in range(0, a.shape[-1], 16):
+        sl = slice(c, c + 16)
+        for p, q in ((a3, w1), (a1, w3), (a2, w2), (a2, w1), (a1, w2), (a1, w1)):
+            acc = acc + p[..., sl] @ q[:, sl].t()
+    return acc
+
+
+def h2_scales(mx):
+    """(scale, inv) = 2^(139 - E), 2^(E - 139), E the biased exponent of the fp32 maxima `mx` clamped to 40 .. 254:
+    a maximum with such an exponent lands in [2^12, 2^13)"""
+    E = ((mx.float().contiguous().view(torch.int32) >> 23) & 0xff).clamp(40, 254).double()
+    return (2.0 ** (139 - E)).float(), (2.0 ** (E - 139)).float()
+
+
+def split2(x):
+    """x = h + m, two round-to-nearest fp16 pieces, as fp32 tensors"""
+    h = x.half().float()
+    return h, (x - h).half().float()
+
+
+def acc_h2(a, w, amax, wmax, splitk=1):
+    """routes C and D (pw_h2_kernel): operands scaled by the power of two of h2_scales (activations per image from
+    amax [B], weights from wmax), two fp16 pieces each, per 16-channel step the three kept terms (m h) (h m) (h h);
+    32-channel stages in K slices; un-scaled exactly"""
+    xs, xinv = h2_scales(amax)
+    ws, winv = h2_scales(wmax.reshape(1))
+    ah, am = split2(a * xs.view(-1, 1, 1, 1))
+    wh, wm = split2(w * ws)
+    parts = []
+    for lo, hi in splitk_slices(a.shape[-1], 32, splitk):
+        acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
+        for c in range(lo, hi, 16):
+            sl = slice(c, c + 16)
+            for p, q in ((am, wh), (ah, wm), (ah, wh)):
+                acc = acc + p[..., sl] @ q[:, sl].t()
+        parts.append(acc * (xinv * winv).view(-1, 1, 1, 1))
+    return combine_slices(parts)
+
+
+def h2_floor(aabs, w, amax, wmax):
+    """what the fp16 x 2 contract adds to sum_k |a| |w|: 2^-13 (amax_b sum_k |w_nk| + wmax sum_k |a_pk|) -- in units
+    of 2^-24 that is 2^-37 of the image's maximum per term, the absolute precision the header promises for elements
+    more than 2^15 below it.  fp64, [B, H, W, N]"""
+    return 2.0 ** -13 * (amax.double().view(-1, 1, 1, 1) * w.double().abs().sum(1) +
+                         float(wmax) * aabs.double().sum(-1, keepdim=True))
+
+
+# -- host packers, from the header's description of P2L_WFMT_PW (bit for bit what the device packers write) -----------
+def _padded(w, N_pad, K_pad):
+    o = torch.zeros(N_pad, K_pad, dtype=torch.float32)
+    o[:w.shape[0], :w.shape[1]] = w
+    return o
+
+
+def pack_f32(w, N_pad, K_pad):
+    """[K_pad / KC][N_pad][KC] floats, KC = 32 when K_pad % 32 == 0 and 16 otherwise"""
+    kc = 32 if K_pad % 32 == 0 else 16
+    return _padded(w, N_pad, K_pad).view(N_pad, K_pad // kc, kc).permute(1, 0, 2).contiguous().flatten()
+
+
+def _rows16(p, N_pad, K_pad):
+    """[N_pad, K_pad] -> [K_pad / 16, N_pad / 32, 32 rows, 2 halves, 8]"""
+    return p.view(N_pad // 32, 32, K_pad // 16, 2, 8).permute(2, 0, 1, 3, 4)
+
+
+def pack_bf3(w, N_pad, K_pad):
+    """the bf16 x 3 image as int32 words: [K_pad / 16][N_pad / 32][32 rows][96 B], a row = [x1 k0-7 | x1 k8-15 | x2 ..
+    | x3 ..], the 16-byte chunk index XOR-ed with bit 3 of the row"""
+    out = torch.zeros(K_pad // 16, N_pad // 32, 32, 6, 8, dtype=torch.bfloat16)
+    row = torch.arange(32)
+    for i, piece in enumerate(split3(_padded(w, N_pad, K_pad))):
+        src = _rows16(piece.bfloat16(), N_pad, K_pad)
+        for half in (0, 1):
+            for bit in (0, 1):
+                rows = row[((row >> 3) & 1) == bit]
+                out[:, :, rows, (2 * i + half) ^ bit] = src[:, :, rows, half]
+    return out.view(torch.int16).flatten().view(torch.int32)
+
+
+def pack_h2(w, N_pad, K_pad):
+    """the fp16 x 2 image as int32 words: [K_pad / 16][N_pad / 32][32 rows][64 B], a row = [h k0-7 | h k8-15 | m k0-7
+    | m k8-15] of the weight times the layer's power of two, the chunk index XOR-ed with bits 2-3 of the row; then
+    four tail words, the first the bits of max |w|"""
+    wmax = w.abs().max().reshape(1) if w.numel() else torch.zeros(1)
+    scale, _ = h2_scales(wmax)
+    out = torch.zeros(K_pad // 16, N_pad // 32, 32, 4, 8, dtype=torch.float16)
+    row = torch.arange(32)
+    for i, piece in enumerate(split2(_padded(w, N_pad, K_pad) * scale)):
+        src = _rows16(piece.half(), N_pad, K_pad)
+        for half in (0, 1):
+            for bits in range(4):
+                rows = row[((row >> 2) & 3) == bits]
+                out[:, :, rows, (2 * i + half) ^ bits] = src[:, :, rows, half]
+    tail = torch.zeros(4, dtype=torch.int32)
+    tail[0] = wmax.float().view(torch.int32)[0]
+    return torch.cat([out.view(torch.int16).flatten().view(torch.int32), tail])
+
+
+def pack_pw(w, N_pad, K_pad):
+    """a P2L_WFMT_PW buffer as int32 words: fp32 layout | bf16 x 3 image | fp16 x 2 image | tail"""
+    return torch.cat([pack_f32(w, N_pad, K_pad).view(torch.int32), pack_bf3(w, N_pad, K_pad), pack_h2(w, N_pad, K_pad)])
+
+
+# -- the cases of tests/test_pw_kernels_gpu.py: shared with tests/test_small_refs.py, which holds every case's inputs
+#    to "the restatement's own figure is at most k / 4" on the host ---------------------------------------------------
+def _pwc(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, pro=PRO_NONE, pro_b=1, alpha=1.0, bias=False,
+             res=None, mask=False, act=ACT_NONE, pool=POOL_NONE, want_y=True, oscale=False, noise=False,
+             n_store=Cout, splitk=1, wfmt=0 if route == 'A' else 3, form=0, ws=route == 'D', amax=None, finish='v4')
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def pw_id(c):
+    d = _pwc(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+EPI = [dict(bias=True, alpha=0.5, res='same'), dict(res='ups', pro=PRO_AFFINE_RELU), dict(mask=True, pro=PRO_AFFINE),
+       dict(act=ACT_RELU, pool=POOL_MAX), dict(pool=POOL_SUM, want_y=False, pro=PRO_AFFINE, pro_b=0),
+       dict(act=ACT_TANH), dict(act=ACT_LRELU_SQRT2, oscale=True, noise=True, bias=True)]
+FORM_NO_PW, FORM_WINO_BF3 = 8, 32
+PW_FWD_CASES = [
+    # route A: TB = 8 with the last tile partly empty; TB = 2 and KC = 16; one image per tile; partial tiles; the
+    # 32-channel tiles choose_bn picks on a full grid; P2L_WFMT_PW buffers on the exact-fp32 kernel
+    _pwc('A', (4, 4), 9, 32, 32, **EPI[0]),
+    _pwc('A', (8, 8), 3, 48, 64, **EPI[1]),
+    _pwc('A', (8, 16), 1, 96, 96, **EPI[2]),
+    _pwc('A', (16, 16), 3, 160, 64, **EPI[3]),
+    _pwc('A', (16, 16), 1, 48, 32, **EPI[4]),
+    _pwc('A', (12, 20), 1, 32, 32, **EPI[5]),
+    _pwc('A', (6, 10), 3, 96, 96, n_store=68, pro=PRO_AFFINE_RELU, pro_b=0),
+    _pwc('A', (64, 64), 9, 64, 64),
+    _pwc('A', (16, 16), 3, 96, 64, wfmt=3, form=FORM_NO_PW, **EPI[6]),
+    _pwc('A', (8, 8), 3, 64, 96, wfmt=3, bias=True),                         # Cout % 64 != 0
+    _pwc('A', (12, 20), 3, 64, 64, wfmt=3, bias=True),                       # a partial grid
+    _pwc('A', (8, 8), 3, 64, 64, wfmt=3, bias=True),                         # a small grid without workspace
+    _pwc('A', (32, 32), 1, 64, 64, wfmt=3, form=FORM_NO_PW, act=ACT_RELU),
+    # route A in K slices: 5 chunks; the requests 3 and 8 resolve to 3 and 5 slices, 2 to slices of 3 and 2 chunks
+    _pwc('A', (8, 8), 3, 160, 64, splitk=2, ws=True, **EPI[0]),
+    _pwc('A', (16, 16), 3, 160, 64, splitk=3, ws=True, **EPI[3]),
+    _pwc('A', (8, 8), 9, 160, 32, splitk=8, ws=True, **EPI[2]),
+    _pwc('A', (16, 16), 1, 160, 64, splitk=8, ws=True, **EPI[6]),
+    _pwc('A', (8, 8), 3, 160, 64, splitk=3, ws=True, finish='scalar', **EPI[0]),
+    _pwc('A', (16, 16), 3, 160, 64, splitk=2, ws=True, finish='scalar', **EPI[3]),
+    _pwc('A', (8, 8), 3, 160, 64, splitk=8, ws=True, finish='scalar', res='ups', mask=True, act=ACT_TANH, n_store=36),
+    # route B
+    _pwc('B', (32, 32), 1, 64, 64, **EPI[0]),
+    _pwc('B', (8, 128), 3, 192, 128, **EPI[1]),
+    _pwc('B', (64, 16), 1, 64, 128, **EPI[2]),
+    _pwc('B', (24, 48), 3, 192, 64, **EPI[3]),
+    _pwc('B', (32, 32), 3, 64, 64, **EPI[4]),
+    _pwc('B', (32, 32), 3, 64, 128, n_store=100, **EPI[5]),
+    _pwc('B', (32, 32), 1, 192, 64, **EPI[6]),
+    _pwc('B', (64, 16), 3, 64, 64, pro=PRO_AFFINE_RELU, pro_b=0),
+    _pwc('B', (32, 32), 3, 64, 64, form=FORM_WINO_BF3, amax='true', bias=True),   # handed maxima, still bf16 x 3
+    # route C: true maxima without a prologue, raw maxima under a prologue, in_applied maxima
+    _pwc('C', (32, 32), 3, 64, 64, amax='true', **EPI[0]),
+    _pwc('C', (8, 128), 3, 192, 128, amax='raw', **EPI[1]),
+    _pwc('C', (24, 48), 3, 192, 64, amax='applied', **EPI[2]),
+    _pwc('C', (64, 16), 1, 64, 128, amax='true', **EPI[3]),
+    _pwc('C', (32, 32), 3, 64, 64, amax='raw', **EPI[4]),
+    _pwc('C', (32, 32), 3, 64, 128, amax='true', n_store=100, **EPI[5]),      # (its all-zero image: exactly 0)
+    _pwc('C', (32, 32), 3, 192, 64, amax='true', **EPI[6]),
+    _pwc('C', (64, 16), 3, 64, 64, amax='raw', pro=PRO_AFFINE_RELU, pro_b=0),
+    # route D: one, three and five 32-channel stages, in 1 .. 5 slices; maxima from the pass in front / handed over
+    _pwc('D', (4, 4), 9, 32, 64, **EPI[0]),
+    _pwc('D', (8, 8), 5, 96, 128, splitk=3, amax='raw', **EPI[1]),
+    _pwc('D', (8, 16), 3, 160, 64, splitk=2, **EPI[2]),
+    _pwc('D', (16, 16), 1, 160, 128, splitk=8, amax='true', **EPI[3]),
+    _pwc('D', (16, 16), 3, 96, 64, **EPI[4]),
+    _pwc('D', (8, 8), 3, 32, 64, n_store=36, **EPI[5]),
+    _pwc('D', (8, 8), 3, 160, 64, **EPI[6]),
+    _pwc('D', (8, 8), 3, 160, 64, splitk=3, **EPI[6]),
+    _pwc('D', (16, 16), 5, 96, 64, splitk=3, amax='applied', pro=PRO_AFFINE_RELU, bias=True),
+    _pwc('D', (8, 8), 3, 160, 64, splitk=8, finish='scalar', **EPI[0]),
+    _pwc('D', (8, 8), 3, 96, 64, pro=PRO_AFFINE_RELU, pro_b=0),
+]
+
+
+def _arbc(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, splitk=1, skip=None, pool_sum=False,
+             nomask=False, wfmt=0 if route == 'A' else 3, ws=route == 'D', amax='true' if route == 'C' else None,
+             pro=PRO_NONE, alpha=1.0)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def arb_id(c):
+    d = _arbc(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+ARB_VARIANTS = [dict(), dict(skip='same'), dict(skip='ups'), dict(pool_sum=True, skip='same'), dict(nomask=True)]
+PW_ARB_CASES = [_arbc(*base, **dict(kw, **v)) for base, kw in [
+    (('A', (8, 16), 1, 96, 64), {}), (('A', (16, 16), 3, 48, 96), {}), (('A', (8, 8), 3, 160, 64), dict(splitk=3, ws=True)),
+    (('B', (32, 32), 3, 64, 64), {}), (('C', (32, 32), 3, 192, 64), {}), (('D', (16, 16), 3, 96, 64), {}),
+    (('D', (8, 8), 3, 160, 128), dict(splitk=3))] for v in ARB_VARIANTS]
+
+
+def arb_inputs(g, c):
+    """dy [B, H, W, Cin], w [Cout, Cin] (the matrix the launch applies), x, s, t of the consumer at the resolution of
+    dx ([B, H/2, W/2, Cout] under pool_sum), the shortcut gradient with Cout channels (skip_C = Cout / 2)"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    rn = lambda *sh: torch.randn(*sh, generator=g)
+    mg = mags(B).view(B, 1, 1, 1)
+    Ho, Wo = (H // 2, W // 2) if c['pool_sum'] else (H, W)
+    i = dict(x=rn(B, H, W, Cin) * mg, w=rn(Cout, Cin) / math.sqrt(Cin))
+    if c['route'] in 'CD':
+        i['x'][1] = 0.0
+        i['x'][0, 0:2, 0:2] *= 2.0 ** -20
+    i['ax'] = rn(B, Ho, Wo, Cout) * mg.flip(0)
+    i['as'] = (0.5 + torch.rand(B, Cout, generator=g)) * torch.where(torch.rand(B, Cout, generator=g) < 0.5, -1.0, 1.0)
+    i['at'] = 0.3 * rn(B, Cout) * mg.flip(0).view(B, 1)
+    if c['skip'] == 'same':
+        i['skip'] = rn(B, Ho, Wo, Cout) * mg
+    elif c['skip'] == 'ups':
+        i['skip'] = rn(B, 2 * Ho, 2 * Wo, Cout) * mg
+    return i
+
+
+def arb_refs(c, i):
+    """-> conv1x1_arb's dict in fp64, the fp32 restatement's (its ds, dt in the kernels' two-stage order: arb_sums32)"""
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=c['Cout'] // 2 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    floor = h2_floor(i['x'].double().abs(), i['w'], pw_amax(c, i)[1], i['w'].abs().max()) if c['route'] in 'CD' else None
+    r64 = conv1x1_arb(i['x'].double(), i['w'].double(), i['ax'].double(), i['as'].double(), i['at'].double(),
+                      floor=floor, **kw)
+    r32 = conv1x1_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], acc=pw_acc32(c, i), **kw)
+    split = c['route'] in 'AD' and len(splitk_slices(c['Cin'], 32 if c['Cin'] % 32 == 0 else 16, c['splitk'])) > 1
+    r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], split)
+    return r64, r32
+
+
+def arb_positive(i):
+    """the same case with |dy| and |w|: no term of da cancels, so sum |terms of g| = |g| (fp16 x 2: but for the floor)
+    and the denominators sum |g x| and sum |g| carry the conv's own error of g -- the inputs on which ds and dt are
+    held to their bar.  (With signed operands a channel with a few live pixels has sum |g| as small as one cancelled
+    conv output: its figure measures that cancellation, without bound, and not the reduction; dx, whose denominator
+    is sum |terms|, is held on the signed inputs, and ds, dt there to `arb_bound`.)"""
+    return dict(i, x=i['x'].abs(), w=i['w'].abs())
+
+
+def arb_k(c):
+    """-> (k of dx, of ds, of dt).  dx: the conv's k (pw_k), the 2x2 sum of da (2), g s (1), the shortcut (1; the
+    children's tree and the sum: 3).  ds, dt on `arb_positive` inputs: the conv's k on every g (+ 1 for the floor's
+    share of sum |terms| on the fp16 x 2 routes), the sums (a quad's chain 4, the tile's tree of quads and waves 5, the
+    rows of p2l_arb_finish's chains, their tree 2, the 16 segments 15) and the product g x (1)"""
+    kg = pw_k(dict(c, oscale=False, bias=False, noise=False, res=None, act=ACT_NONE, pool=POOL_NONE)) + \
+        (2 if c['pool_sum'] else 0)
+    Ho, Wo = (c['H'] // 2, c['W'] // 2) if c['pool_sum'] else (c['H'], c['W'])
+    ksum = 4 + 5 + max(1, (Ho // 2) * (Wo // 2) // 64) + 2 + 15
+    return kg + 1 + {None: 0, 'same': 1, 'ups': 3}[c['skip']], kg + 1 + 1 + ksum, kg + 1 + ksum
+
+
+def arb_bound(c, r64, ax):
+    """a-priori bounds of |ds - ref|, |dt - ref| [B, C] in units of 2^-24 for operands of any sign: the conv's k on
+    sum |terms of g| of every LIVE pixel (times |x| for ds), the sums' k on sum |g x| / sum |g|"""
+    _, kds, kdt = arb_k(c)
+    kg = arb_k(c)[0] - 1 - {None: 0, 'same': 1, 'ups': 3}[c['skip']]
+    dg = r64['den_g'] * (r64['g'] != 0).double()
+    return (kg * (dg * ax.double().abs()).sum(dim=(1, 2)) + (kds - kg) * r64['den_ds'],
+            kg * dg.sum(dim=(1, 2)) + (kdt - kg) * r64['den_dt'])
+
+
+def mags(Bn, lo=-2.0, hi=2.0):
+    """one magnitude per image, 1e-2 .. 1e2"""
+    return 10.0 ** torch.linspace(lo, hi, Bn) if Bn > 1 else torch.tensor([3.0])
+
+
+def pw_inputs(g, c):
+    """the operands of a forward case on the host, dense fp32: every image at a magnitude of its own; routes C and D:
+    image 1 of a batch of three or more all zero and a 2x2 quad of image 0 2^-20 below its maximum; prologue: s in
+    0.5 + U(0, 1), t scaled to the image, one heavy channel (|s| x 50) away from the channel of the largest |x|"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    rn = lambda *sh: torch.randn(*sh, generator=g)
+    mg = mags(B)
+    i = dict(x=rn(B, H, W, Cin) * mg.view(B, 1, 1, 1), w=rn(Cout, Cin) / math.sqrt(Cin))
+    if c['route'] in 'CD':
+        if B >= 3:
+            i['x'][1] = 0.0
+        i['x'][0, 0:2, 0:2] *= 2.0 ** -20
+    xmax = i['x'].abs().amax(dim=(1, 2, 3))
+    out_mag = torch.where(xmax > 0, mg, torch.ones_like(mg)).view(B, 1, 1, 1)
+    if c['pro'] != PRO_NONE:
+        Bs = B if c['pro_b'] else 1
+        s = 0.5 + torch.rand(Bs, Cin, generator=g)
+        t = 0.3 * rn(Bs, Cin) * (xmax[:Bs].view(Bs, 1) if c['pro_b'] else xmax[xmax > 0].min())
+        for b in range(Bs):
+            big = int(i['x'][b].abs().amax(dim=(0, 1)).argmax())
+            s[b, (big + Cin // 2) % Cin] *= 50.0
+        i['s'], i['t'] = s, t
+    if c['bias']:
+        i['bias'] = 0.1 * rn(Cout)
+    if c['res'] == 'same':
+        i['res'] = rn(B, H, W, Cout) * out_mag
+    elif c['res'] == 'ups':
+        i['res'] = rn(B, H // 2, W // 2, Cout) * out_mag
+    if c['mask']:
+        i['mask'] = rn(B, H, W, Cout)
+    if c['oscale']:
+        i['oscale'] = 0.5 + torch.rand(B, Cout, generator=g)
+    if c['noise']:
+        i['noise'], i['noise_w'] = rn(B, H, W) * out_mag[..., 0], 0.3
+    return i
+
+
+def pw_amax(c, i):
+    """-> (what a case hands to P2LAmax.in [B] or None, amax_b [B]: the value the contract says the kernel scales by).
+    Pass in front: the true maximum of the prologue's result; handed raw maxima under a prologue:
+    (max |s| max |x| + max |t|) 1.001; in_applied: the handed maxima of |x s + t|; no prologue: the handed maxima"""
+    B = c['B']
+    x = i['x']
+    xmax = x.abs().amax(dim=(1, 2, 3))
+    if c['pro'] == PRO_NONE:
+        return (xmax if c['amax'] else None), xmax
+    s, t = i['s'].expand(B, -1), i['t'].expand(B, -1)
+    pre = fma(x, s[:, None, None, :], t[:, None, None, :])
+    if c['amax'] == 'raw':
+        return xmax, (s.abs().amax(1) * xmax + t.abs().amax(1)) * 1.001
+    if c['amax'] == 'applied':
+        m = pre.abs().amax(dim=(1, 2, 3))
+        return m, m * 1.001
+    a = torch.relu(pre) if c['pro'] == PRO_AFFINE_RELU else pre
+    return (xmax if c['amax'] else None), a.abs().amax(dim=(1, 2, 3))
+
+
+def pw_kwargs(c, i, dtype):
+    """the keyword arguments of conv1x1 for a case, operands in `dtype`"""
+    cv = lambda name: i[name].to(dtype) if name in i else None
+    return dict(pro=c['pro'], s=cv('s'), t=cv('t'), alpha=c['alpha'], oscale=cv('oscale'), noise=cv('noise'),
+                noise_w=i.get('noise_w', 0.0), bias=cv('bias'), res=cv('res'), res_ups=c['res'] == 'ups', act=c['act'],
+                mask=cv('mask'), n_store=c['n_store'], pool=c['pool'])
+
+
+def pw_acc32(c, i, route=None):
+    """the fp32 restatement of the accumulator of a case on route `route` (default: its own)"""
+    route = route or c['route']
+    a, _ = pw_prologue(i['x'], c['pro'], i.get('s'), i.get('t'))
+    if route == 'A':
+        return acc_fp32(a, i['w'], c['splitk'])
+    if route == 'B':
+        return acc_bf3(a, i['w'])
+    return acc_h2(a, i['w'], pw_amax(c, i)[1], i['w'].abs().max(), c['splitk'] if route == 'D' else 1)
+
+
+def pw_refs(c, i, route=None):
+    """-> fp64 reference (conv1x1's dict, den with the fp16 x 2 floor on routes C and D) and the fp32 restatement's"""
+    route = route or c['route']
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    floor = None
+    if route in 'CD':
+        _, aabs = pw_prologue(i64['x'], c['pro'], i64.get('s'), i64.get('t'))
+        floor = h2_floor(aabs, i['w'], pw_amax(c, i)[1], i['w'].abs().max())
+    r64 = conv1x1(i64['x'], i64['w'], floor=floor, **pw_kwargs(c, i, torch.float64))
+    r32 = conv1x1(i['x'], i['w'], acc=pw_acc32(c, i, route), **pw_kwargs(c, i, torch.float32))
+    return r64, r32
+
+
+def pw_k(c, route=None, pooled=False):
+    """the bar's k of a forward case, counted from the route's arithmetic: per k of the deepest K slice the
+    additions onto the accumulator (fp32 MFMA: a product and an addition; bf16 x 3: six cross terms of exact
+    products; fp16 x 2: three) and the slices in order; bf16 x 3: the pieces to 2^-24 relative of either operand (2)
+    and the dropped terms <= 2^-23 (2); fp16 x 2: the pieces to 2^-22 relative of either operand (8), the dropped
+    term (4) and the absolute floor that `h2_floor` puts into the denominator (1); the prologue's fma or product and
+    sum (2); alpha, oscale, bias, noise (a product and a sum), residual one each; tanh 2; the leaky ReLU's factor
+    sqrt 2 on everything before it and its own rounding; the pool's sum: two additions deep"""
+    route = route or c['route']
+    K = c['Cin']
+    sl = splitk_slices(K, 32 if (route == 'D' or K % 32 == 0) else 16, c['splitk']) if route in 'AD' else [(0, K)]
+    deep = max(hi - lo for lo, hi in sl)
+    k = {'A': 2, 'B': 6, 'C': 3, 'D': 3}[route] * deep + (len(sl) - 1) + {'A': 0, 'B': 4, 'C': 13, 'D': 13}[route]
+    k += (2 if c['pro'] != PRO_NONE else 0) + 1 + c['oscale'] + c['bias'] + 2 * c['noise'] + (c['res'] is not None)
+    if c['act'] == ACT_TANH:
+        k += 2
+    if c['act'] == ACT_LRELU_SQRT2:
+        k = 1.5 * k + 1
+    return k + 2 if pooled and c['pool'] == POOL_SUM else k
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import _small_refs as R
+from _small_refs import _cancellation_case
 from _pin import D64, G, N, SENT, Out, _gen, _record_file, d64, draw, hold, is_sentinel, randn, seeded  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -396,22 +397,7 @@ def test_affine_relu_bwd(dev, N, Cc, H, W, Bn):
 ARB_NBLK = [1, 15, 16, 17, 47, 48, 49, 63, 64, 65, 130]
 
 
-def _finish_order32(part):
-    """partial [Bn, nblk, C] (one half) -> [Bn, C] in the order csrc/p2l_ops.hip documents, in fp32: segment seg adds
-    its rows seg, seg + 16, ... in four chains (row index / 16 mod 4), combined ((0 + 1) + (2 + 3)); then the 16
-    segments in sequence"""
-    Bn, nblk, Cc = part.shape
-    segs = []
-    for seg in range(16):
-        ch = [torch.zeros(Bn, Cc) for _ in range(4)]
-        for j in range(seg, nblk, 16):
-            q = (j // 16) % 4
-            ch[q] = ch[q] + part[:, j]
-        segs.append((ch[0] + ch[1]) + (ch[2] + ch[3]))
-    out = segs[0]
-    for k in range(1, 16):
-        out = out + segs[k]
-    return out
+_finish_order32 = R.arb_finish_order32            # (shared with the 1x1 convs' ds / dt restatement)
 
 
 def _finish_case(g, Bn, nblk, Cc):
@@ -514,46 +500,6 @@ def test_arb_finish_deferred(dev, N):
 
 
 # ---- the backward takes the forward's decision -------------------------------------------------------------------
-def _cancellation_case(seed, Bn, P, Cc):
-    """x [Bn, P, C], s, t [Bn, C] in fp32.  Channels 0..15 (kind A): in 32 pixels x s + t cancels so that the twice
-    rounded fl(fl(x s) + t) is 0 but the once rounded fma(x, s, t) is the product's rounding error, of either sign.
-    Channels 16..31 (kind B, magnitudes near 2^-126): x s = (n + 1/2) 2^-149 with n odd and t = -n 2^-149 (and the
-    mirror image): fl(x s) is the even neighbour, so the twice rounded sum is 2^-149, and the once rounded one is the
-    tie 2^-150 -> 0.  The other pixels of the kind B channels hold +-64 .. 128: a is 0 or about 2^-120 there, a normal
-    number -- the bf16 pieces through which the 3x3 formats 1 and 2 are read back do not carry subnormals, so a
-    positive a below 2^-126 would read as 0 whatever the prologue decided.  Everything else is ordinary."""
-    g = torch.Generator().manual_seed(4000 + seed)
-    x = torch.randn(Bn, P, Cc, generator=g)
-    s = (0.5 + torch.rand(Bn, Cc, generator=g)) * torch.where(torch.rand(Bn, Cc, generator=g) < 0.5, -1.0, 1.0)
-    t = 0.3 * torch.randn(Bn, Cc, generator=g)
-    special = torch.zeros(Bn, P, Cc, dtype=torch.int8)
-    for b in range(Bn):
-        for c in range(32):
-            pix = torch.randperm(P, generator=g)[:32]
-            if c < 16:
-                xv = float(torch.randn(1, generator=g)) + 2.0
-                prod = torch.tensor(xv, dtype=torch.float32) * s[b, c]            # fl(x s)
-                x[b, pix, c], t[b, c] = xv, -prod
-                special[b, pix, c] = 1
-            else:
-                n = 2 * int(torch.randint(2 ** 21, 2 ** 22, (1,), generator=g)) + 1                # odd, < 2^23
-                sign = 1.0 if c % 2 == 0 else -1.0
-                x[b, :, c] = (64.0 + 64.0 * torch.rand(P, generator=g)) * torch.where(torch.rand(P, generator=g) < 0.5, -1.0, 1.0)
-                x[b, pix, c], s[b, c], t[b, c] = sign * (2 * n + 1) * 2.0 ** -24, 2.0 ** -126, -sign * n * 2.0 ** -149
-                special[b, pix, c] = 2
-    # both models of the decision on the host: fp64 holds the product exactly, and the sum wherever it cancels
-    once = (x.to(D64) * s.to(D64)[:, None] + t.to(D64)[:, None]).float()         # fma: ONE rounding
-    twice = x * s[:, None] + t[:, None]                                          # fp32 product, fp32 sum
-    A, B = special == 1, special == 2
-    assert int(A.sum()) >= 256 and int(B.sum()) >= 256
-    assert bool((twice[A] == 0).all()) and bool((once[A] != 0).all())
-    assert bool((once[A] > 0).any()) and bool((once[A] < 0).any())
-    assert bool((once[B] == 0).all()) and bool((twice[B] != 0).all())
-    assert bool((twice[B] > 0).any()) and bool((twice[B] < 0).any())
-    assert bool(((once <= 0) | (once >= 2.0 ** -126)).all())                      # every positive a is a normal number
-    return x, s, t, once > 0, twice > 0, A, B
-
-
 @pytest.mark.parametrize('taps,wfmt', [(1, 0), (1, 3), (9, 0), (9, 1), (9, 2)])
 def test_backward_mask_is_the_forwards_decision(dev, N, taps, wfmt):
     """{dx != 0} of p2l_affine_relu_bwd (da = 1, s != 0) == {a > 0}, a = what the conv's PRO_AFFINE_RELU prologue
