@@ -55,8 +55,9 @@ extern "C" {
  * are PRESENT, a pitch below the row it pitches: x_ld < Cin; y_ld, yp_ld, res_ld, mask_ld, P2LArb.x_ld < n_store;
  * pro_bstride, P2LArb.st_bstride, P2LConvExtra.oscale_bstride in 1 .. row - 1 (0 = shared by the images);
  * P2LArb.skip_ld < skip_C or skip_C > n_store; P2LArb.ds / dt NULL, dsdt_bstride < Cout or no multiple of four; on a
- * split-K launch with the 16-byte finish, P2LArb.x_ld / skip_ld no multiple of four; and a w_floats > 0 below the
- * packed size of the launch.  A split-K
+ * split-K launch with the 16-byte finish, P2LArb.x_ld / skip_ld no multiple of four; a w_floats > 0 below the
+ * packed size of the launch; and, on a launch that records maxima under the reader's affine (P2LAmax.out, next_s,
+ * next_t and p2l_conv_amax_slots > 0), P2LAmax.next_bstride in 1 .. n_store - 1.  A split-K
  * launch whose finish would be the scalar kernel (some pitch FIELD, even that of an absent operand, no multiple of
  * four) and that carries P2LConvExtra.oscale / noise or P2L_ACT_LRELU_SQRT2 returns P2L_EUNSUP: that kernel has
  * none of the three terms.

@@ -1465,6 +1465,8 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     if (nslots > 0 && direct_h2r(d) && !use_h2) return P2L_EWS;   // (... for the register-resident kernel: one block per tile)
     if (nslots > 0) { k.amax_out = am->out; k.amax_outp = am->outp; k.amax_out_n = nslots; }
     if (nslots > 0 && am->out && am->next_s && am->next_t && !arb) {
+      // the reader's affine is read as [B][next_bstride] rows of n_store floats, like oscale (0 = shared by the images)
+      if (am->next_bstride != 0 && am->next_bstride < d->n_store) return P2L_EINVAL;
       k.amax_ps = am->next_s; k.amax_pt = am->next_t; k.amax_pbstride = am->next_bstride;
     }
   }

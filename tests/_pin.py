@@ -19,7 +19,8 @@ SENT = 0x4EADBEEF                     # sentinel bit pattern (a finite float, ~1
 _RECORDS = []
 # test module -> the environment variable that names its record file (profiles/*_kernels_err.txt)
 _ERR_FILE_ENV = {'test_small_kernels_gpu': 'P2L_SMALL_ERR_FILE', 'test_loss_kernels_gpu': 'P2L_LOSS_ERR_FILE',
-                 'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE', 'test_pw_kernels_gpu': 'P2L_PW_ERR_FILE'}
+                 'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE', 'test_pw_kernels_gpu': 'P2L_PW_ERR_FILE',
+                 'test_wino_kernels_gpu': 'P2L_WINO_ERR_FILE'}
 
 
 class _Native(object):
@@ -166,6 +167,20 @@ def hold(name, case, got, ref64, denom64, got32, k):
     assert pool is not None, 'hold() outside a @seeded test'
     old = pool.get((name, case), (0.0, 0.0, k, 0))
     pool[(name, case)] = (max(old[0], fk), max(old[1], f32), k, old[3] + got.numel())
+
+
+def hold_k(name, case, got, ref64, denom64, k):
+    """pool a figure that is held to its counted k alone -- no restatement stands behind it (recorded with fp32 = inf)"""
+    f = fig(got, ref64, denom64)
+    pool = _DRAW['pool']
+    assert pool is not None, 'hold_k() outside a @seeded test'
+    old = pool.get((name, case), (0.0, float('inf'), k, 0))
+    pool[(name, case)] = (max(old[0], f), float('inf'), k, old[3] + got.numel())
+
+
+def note(name, case, got, ref64, denom64):
+    """pool a figure that is recorded and not judged (bar and k = inf)"""
+    hold_k(name, case, got, ref64, denom64, float('inf'))
 
 
 def d64(*ts):

@@ -3,8 +3,9 @@ losses and the optimiser), written from the formulas in the header comments and 
 -- not from the kernels.  Forwards are direct restatements; every backward is autograd through its forward in
 float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks these functions against
 independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py,
-tests/test_glue_kernels_gpu.py and tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
-restatements, host packers and the case tables) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+tests/test_glue_kernels_gpu.py, tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
+restatements, host packers and the case tables) and tests/test_wino_kernels_gpu.py (the Winograd 3x3 routes: the
+same) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
@@ -510,6 +511,18 @@ def conv1x1(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, oscale=None, noise=No
     v = (a @ w.t() if acc is None else acc.to(dt)) * alpha
     den = aabs @ w.abs().t()
     den = (den if floor is None else den + floor.to(dt)) * abs(alpha)
+    out = conv_epilogue(v, den, oscale, noise, noise_w, bias, res, res_ups, act, mask, n_store, pool)
+    out.update(a=a, aabs=aabs)
+    return out
+
+
+def conv_epilogue(v, den, oscale=None, noise=None, noise_w=0.0, bias=None, res=None, res_ups=False, act=ACT_NONE,
+                  mask=None, n_store=None, pool=POOL_NONE):
+    """the epilogue half of every conv launch (the shared epilogue item of csrc/p2l_conv_k.h), in the dtype of v: v =
+    alpha-scaled accumulator [B, H, W, N], den the same expression on absolute values.
+    -> dict: y, den, yp, denp"""
+    dt = v.dtype
+    n_store = v.shape[-1] if n_store is None else n_store
     if oscale is not None:
         v = v * oscale.to(dt)[:, None, None, :]
         den = den * oscale.to(dt).abs()[:, None, None, :]
@@ -534,7 +547,7 @@ def conv1x1(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, oscale=None, noise=No
             v * torch.where(v > 0, torch.tensor(1.41421356237, dtype=dt), torch.tensor(0.2 * 1.41421356237).to(dt))
     if mask is not None:
         v = torch.where(mask.to(dt)[..., :n_store] > 0, v, torch.zeros_like(v))
-    out = dict(y=v, den=den, yp=None, denp=None, a=a, aabs=aabs)
+    out = dict(y=v, den=den, yp=None, denp=None)
     if pool == POOL_MAX:
         v0, v1, v2, v3 = quads(v)
         d0, d1, d2, d3 = quads(den)
@@ -557,6 +570,13 @@ def conv1x1_arb(dy, w, x, s, t, alpha=1.0, pool_sum=False, nomask=False, skip=No
     da = (dy @ w.t() if acc is None else acc.to(dtp)) * alpha
     dend = dy.abs() @ w.abs().t()
     dend = (dend if floor is None else dend + floor.to(dtp)) * abs(alpha)         # (h2_floor, as in conv1x1)
+    return arb_epilogue(da, dend, x, s, t, pool_sum, nomask, skip, skip_C, skip_ups)
+
+
+def arb_epilogue(da, dend, x, s, t, pool_sum=False, nomask=False, skip=None, skip_C=0, skip_ups=False):
+    """the half of the fused input gradient behind da = alpha conv(dy, w) (dend: the same on absolute values), shared
+    by the 1x1 and the 3x3 launches -> conv1x1_arb's dict"""
+    dtp = da.dtype
     if pool_sum:
         da, dend = quad_sum(da), quad_sum(dend)
     x, s_, t_ = x.to(dtp), s.to(dtp)[:, None, None, :], t.to(dtp)[:, None, None, :]
@@ -934,23 +954,23 @@ def arb_positive(i):
     return dict(i, x=i['x'].abs(), w=i['w'].abs())
 
 
-def arb_k(c):
-    """-> (k of dx, of ds, of dt).  dx: the conv's k (pw_k), the 2x2 sum of da (2), g s (1), the shortcut (1; the
+def arb_k(c, conv_k=None):
+    """-> (k of dx, of ds, of dt); conv_k: the conv's count (default pw_k; the 3x3 cases: wino_k).  dx: the conv's k (pw_k), the 2x2 sum of da (2), g s (1), the shortcut (1; the
     children's tree and the sum: 3).  ds, dt on `arb_positive` inputs: the conv's k on every g (+ 1 for the floor's
     share of sum |terms| on the fp16 x 2 routes), the sums (a quad's chain 4, the tile's tree of quads and waves 5, the
     rows of p2l_arb_finish's chains, their tree 2, the 16 segments 15) and the product g x (1)"""
-    kg = pw_k(dict(c, oscale=False, bias=False, noise=False, res=None, act=ACT_NONE, pool=POOL_NONE)) + \
+    kg = (conv_k or pw_k)(dict(c, oscale=False, bias=False, noise=False, res=None, act=ACT_NONE, pool=POOL_NONE)) + \
         (2 if c['pool_sum'] else 0)
     Ho, Wo = (c['H'] // 2, c['W'] // 2) if c['pool_sum'] else (c['H'], c['W'])
     ksum = 4 + 5 + max(1, (Ho // 2) * (Wo // 2) // 64) + 2 + 15
     return kg + 1 + {None: 0, 'same': 1, 'ups': 3}[c['skip']], kg + 1 + 1 + ksum, kg + 1 + ksum
 
 
-def arb_bound(c, r64, ax):
+def arb_bound(c, r64, ax, conv_k=None):
     """a-priori bounds of |ds - ref|, |dt - ref| [B, C] in units of 2^-24 for operands of any sign: the conv's k on
     sum |terms of g| of every LIVE pixel (times |x| for ds), the sums' k on sum |g x| / sum |g|"""
-    _, kds, kdt = arb_k(c)
-    kg = arb_k(c)[0] - 1 - {None: 0, 'same': 1, 'ups': 3}[c['skip']]
+    kdx, kds, kdt = arb_k(c, conv_k)
+    kg = kdx - 1 - {None: 0, 'same': 1, 'ups': 3}[c['skip']]
     dg = r64['den_g'] * (r64['g'] != 0).double()
     return (kg * (dg * ax.double().abs()).sum(dim=(1, 2)) + (kds - kg) * r64['den_ds'],
             kg * dg.sum(dim=(1, 2)) + (kdt - kg) * r64['den_dt'])
@@ -1069,6 +1089,384 @@ def pw_k(c, route=None, pooled=False):
     if c['act'] == ACT_LRELU_SQRT2:
         k = 1.5 * k + 1
     return k + 2 if pooled and c['pool'] == POOL_SUM else k
+
+
+# ---- Winograd F(2x2, 3x3) convs (tests/test_wino_kernels_gpu.py) ----------------------------------------------------
+# Routes of a taps = 9, ups = 0, P2L_WFMT_BF16X3W launch into csrc/p2l_wino.hip: W8 wino_conv_kernel (8x16-pixel blocks,
+# bf16 x 3), W16 wino16s_conv_kernel (16x16, bf16 x 3), H the same kernel in fp16 x 2 (blk 8 / 16: its two block
+# shapes), HS its K-sliced small-grid form with conv_splitk_finish4; F is the exact-fp32 direct kernel (P2L_WFMT_F32),
+# every case's twin.  A weight is the [N, K, 3, 3] correlation kernel the launch applies.  Frequencies are numbered
+# 4 i + j, i the row of B^T d / G g and j the column, as in the packed image.
+WFMT_BF16X3W = 2
+FORM_WINO_ANY, FORM_WINO_8X16, FORM_WINO_H2_8X16, FORM_WINO_H2_16X16 = 2, 4, 64, 128
+WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
+
+
+def wino_U(w):
+    """G g G^T in fp64: [N, K, 3, 3] -> [16, N, K]"""
+    u = torch.einsum('ia,nkab,jb->ijnk', WINO_G, w.double(), WINO_G)
+    return u.reshape(16, w.shape[0], w.shape[1])
+
+
+def _wino_bt(d0, d1, d2, d3, absolute):
+    """the four rows of B^T d as p2l_wino.hip:133 writes them out: d0 - d2, d1 + d2, d2 - d1, d1 - d3 (absolute: of
+    |B^T| |d|)"""
+    if absolute:
+        return d0 + d2, d1 + d2, d2 + d1, d1 + d3
+    return d0 - d2, d1 + d2, d2 - d1, d1 - d3
+
+
+def wino_V(a, absolute=False):
+    """B^T d B of every 4x4 patch of the zero-padded a [B, H, W, K], in the dtype of a and in the kernels' two stages:
+    the rows (one addition of two patch rows each), then the same combination of the columns -> [16, B, H/2, W/2, K]"""
+    B, H, W, K = a.shape
+    ap = F.pad(a, (0, 0, 1, 1, 1, 1))
+    Hq, Wq = H // 2, W // 2
+    out = []
+    for r in _wino_bt(*[ap[:, i:i + 2 * Hq:2] for i in range(4)], absolute):
+        out.extend(_wino_bt(*[r[:, :, j:j + 2 * Wq:2] for j in range(4)], absolute))
+    return torch.stack(out)
+
+
+def wino_out(M, absolute=False):
+    """A^T M A in the kernels' order: T0 = (m0 + m1) + m2, T1 = (m1 - m2) - m3 down the rows, then the same along the
+    columns.  M [16, B, H/2, W/2, N] -> [B, H, W, N]"""
+    def at(m0, m1, m2, m3):
+        if absolute:
+            return (m0 + m1) + m2, (m1 + m2) + m3
+        return (m0 + m1) + m2, (m1 - m2) - m3
+    T0, T1 = zip(*[at(M[j], M[4 + j], M[8 + j], M[12 + j]) for j in range(4)])
+    v00, v01 = at(*T0)
+    v10, v11 = at(*T1)
+    _, B, Hq, Wq, Nn = M.shape
+    y = torch.stack([torch.stack([v00, v01], dim=3), torch.stack([v10, v11], dim=3)], dim=2)    # [B, Hq, 2, Wq, 2, N]
+    return y.reshape(B, 2 * Hq, 2 * Wq, Nn)
+
+
+def wino_acc_bf3(V, U):
+    """W8 / W16: V [16, M, K], U [16, N, K] in fp32; per 16-channel chunk and frequency the six kept cross terms
+    (activation piece, weight piece) in the order both kernels issue them: (1,1) (1,2) (1,3) (2,1) (2,2) (3,1)"""
+    v1, v2, v3 = split3(V)
+    u1, u2, u3 = split3(U)
+    acc = torch.zeros(16, V.shape[1], U.shape[1])
+    for c in range(0, V.shape[2], 16):
+        sl = slice(c, c + 16)
+        for p, q in ((v1, u1), (v1, u2), (v1, u3), (v2, u1), (v2, u2), (v3, u1)):
+            acc = acc + torch.bmm(p[:, :, sl], q[:, :, sl].transpose(1, 2))
+    return acc
+
+
+def wino_acc_h2(V, U, lo, hi):
+    """H / HS: the scaled V, U in two fp16 pieces, channels lo .. hi; per chunk and frequency (h h) (h m) (m h)"""
+    vh, vm = split2(V)
+    uh, um = split2(U)
+    acc = torch.zeros(16, V.shape[1], U.shape[1])
+    for c in range(lo, hi, 16):
+        sl = slice(c, c + 16)
+        for p, q in ((vh, uh), (vh, um), (vm, uh)):
+            acc = acc + torch.bmm(p[:, :, sl], q[:, :, sl].transpose(1, 2))
+    return acc
+
+
+def wino_acc32(c, i, route=None):
+    """the fp32 restatement of a route's result in front of alpha and the epilogue, [B, H, W, N]: U = G g G^T in fp64
+    rounded once; the input transform on the prologue's result (H, HS: times the image's power of two -- the scales
+    are those of the RAW maxima, h2_scales' range leaves the transform its factor 4 and U its 2.25); the chunks; the
+    output transform; H, HS: un-scaled exactly; HS: every slice through the output transform on its own
+    (chunks_per_split = chunks / slices), then ((z0 + z1) + (z2 + z3)) as conv_splitk_finish4 adds them"""
+    route = route or c['route']
+    a, _ = pw_prologue(i['x'], c['pro'], i.get('s'), i.get('t'))
+    B, H, W, K = a.shape
+    Nn = i['w'].shape[0]
+    U = wino_U(i['w']).float()
+    shape = (16, B, H // 2, W // 2, Nn)
+    if route in ('W8', 'W16'):
+        return wino_out(wino_acc_bf3(wino_V(a).reshape(16, -1, K), U).reshape(shape))
+    xs, xinv = h2_scales(pw_amax(c, i)[1])
+    ws, winv = h2_scales(i['w'].abs().max().reshape(1))
+    V, Us = wino_V(a * xs.view(-1, 1, 1, 1)).reshape(16, -1, K), U * ws
+    sk = c['splitk'] if route == 'HS' else 1
+    per = (K // 16 // sk) * 16
+    parts = [wino_out(wino_acc_h2(V, Us, z * per, (z + 1) * per).reshape(shape)) * (xinv * winv).view(-1, 1, 1, 1)
+             for z in range(sk)]
+    if sk == 1:
+        return parts[0]
+    parts += [torch.zeros_like(parts[0])] * (4 - sk)
+    return (parts[0] + parts[1]) + (parts[2] + parts[3])
+
+
+def wino_den(aabs, w):
+    """den_w = |A^T| (sum_k |U| (.) |B^T| |a| |B|) |A|: sum |terms| of the arithmetic the Winograd kernels perform, in
+    the dtype of aabs, [B, H, W, N]"""
+    B, H, W, K = aabs.shape
+    Ua = wino_U(w).abs().to(aabs.dtype)
+    M = torch.bmm(wino_V(aabs, True).reshape(16, -1, K), Ua.transpose(1, 2))
+    return wino_out(M.reshape(16, B, H // 2, W // 2, w.shape[0]), True)
+
+
+def wino_h2_floor(aabs, w, amax, wmax):
+    """the absolute term of the fp16 x 2 contract in the transform domain, fp64 [B, H, W, N].  The header: an element
+    more than 2^15 below the maximum of its image gets a denormal second piece -- "2^-37 of the maximum in absolute
+    terms".  The operands the Winograd kernel splits are V = B^T a B times the image's power of two 2^p and U times
+    the layer's 2^q, with amax 2^p and wmax 2^q in [2^12, 2^13) (h2_scales on the maxima the kernel scales by: of the
+    raw image, or the bound (max |s| max |x| + max |t|) 1.001, or the handed-over |x s + t| maxima times 1.001; max
+    |w| from the weight tail).  h + m misses a scaled value by at most half an fp16 subnormal step, 2^-25, i.e. V by
+    2^-25 / 2^p <= 2^-37 amax and U by 2^-37 wmax.  To first order the product of a frequency is then off by at most
+    2^-37 (amax |U| + wmax |V|), |V| <= |B^T| |a| |B|: summed over k and taken through |A^T| . |A| like the products
+    themselves, in units of 2^-24 that is what this function returns,
+        |A^T| ( 2^-13 (amax_b sum_k |U_nk| + wmax sum_k (|B^T| |a| |B|)_k) ) |A|
+    -- h2_floor with |B^T| |a| |B| and |U| in place of |a| and |w|"""
+    B, H, W, K = aabs.shape
+    Ua = wino_U(w).abs()                                                      # [16, N, K]
+    Va = wino_V(aabs.double(), True)                                          # [16, B, Hq, Wq, K]
+    f = 2.0 ** -13 * (amax.double().view(1, B, 1, 1, 1) * Ua.sum(2).view(16, 1, 1, 1, -1) +
+                      float(wmax) * Va.sum(-1, keepdim=True))
+    return wino_out(f, True)
+
+
+def conv3x3(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, acc=None, floor=None, **epi):
+    """the stride-1 3x3 conv launch of include/p2l.h in the dtype of x: a = prologue(x); zero padding AFTER the
+    prologue; v = alpha sum a w; then conv_epilogue(**epi), the epilogue conv1x1 ends in.  w [N, K, 3, 3].  `acc`
+    replaces the conv (a restatement's result), `floor` (wino_h2_floor) is added to both denominators.
+    -> conv1x1's dict with den / denp on den_w (wino_den) and den_d / denp_d on the direct sum_taps,k |a| |w|"""
+    dt = x.dtype
+    w = w.to(dt)
+    a, aabs = pw_prologue(x, pro, s, t)
+    nchw = lambda v: v.permute(0, 3, 1, 2)
+    v = F.conv2d(nchw(a), w, padding=1).permute(0, 2, 3, 1) if acc is None else acc.to(dt)
+    den_d = F.conv2d(nchw(aabs), w.abs(), padding=1).permute(0, 2, 3, 1)
+    den_w = wino_den(aabs, w)
+    if floor is not None:
+        den_w, den_d = den_w + floor.to(dt), den_d + floor.to(dt)
+    out = conv_epilogue(v * alpha, den_w * abs(alpha), **epi)
+    direct = conv_epilogue(v * alpha, den_d * abs(alpha), **epi)
+    out.update(a=a, aabs=aabs, den_d=direct['den'], denp_d=direct['denp'])
+    return out
+
+
+def conv3x3_arb(dy, w, x, s, t, alpha=1.0, acc=None, floor=None, **kw):
+    """p2l_conv_dgrad_arb on a 3x3 launch: da = alpha conv3x3(dy, w), then arb_epilogue -> conv1x1_arb's dict on
+    den_w, and den_dx_d on the direct denominator"""
+    dtp = dy.dtype
+    w = w.to(dtp)
+    nchw = lambda v: v.permute(0, 3, 1, 2)
+    da = (F.conv2d(nchw(dy), w, padding=1).permute(0, 2, 3, 1) if acc is None else acc.to(dtp)) * alpha
+    den_w, den_d = wino_den(dy.abs(), w), F.conv2d(nchw(dy.abs()), w.abs(), padding=1).permute(0, 2, 3, 1)
+    if floor is not None:
+        den_w, den_d = den_w + floor.to(dtp), den_d + floor.to(dtp)
+    out = arb_epilogue(da, den_w * abs(alpha), x, s, t, **kw)
+    out['den_dx_d'] = arb_epilogue(da, den_d * abs(alpha), x, s, t, **kw)['den_dx']
+    return out
+
+
+def _wc(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, pro=PRO_NONE, pro_b=1, alpha=1.0, bias=False,
+             res=None, mask=False, act=ACT_NONE, pool=POOL_NONE, want_y=True, oscale=False, noise=False,
+             n_store=Cout, splitk=1, amax=None, blk=16 if route == 'H' else 0, relu_like=False, own=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def wino_id(c):
+    d = _wc(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+def wino_form(c, route=None):
+    """P2LConv.form of a case: W8 forced (own: left to the dispatch, which takes the 8x16 kernel where H % 16 != 0),
+    W16 = the 16x16 kernel kept on bf16 x 3, H with its block shape, HS by the product's own rule (form 0)"""
+    route = route or c['route']
+    if route == 'W8':
+        return FORM_WINO_ANY | (0 if c['own'] else FORM_WINO_8X16)
+    if route == 'W16':
+        return FORM_WINO_ANY | FORM_WINO_BF3
+    blk = {0: 0, 8: FORM_WINO_H2_8X16, 16: FORM_WINO_H2_16X16}[c['blk']]
+    return blk if route == 'HS' else FORM_WINO_ANY | blk
+
+
+# every term of EPI on every route; n_store < Cout rides on the tanh entry, the shared prologue on EPI[4]
+WINO_SHAPES = {'8x16': ((8, 16), 1, 16, 64), '16x16': ((16, 16), 2, 16, 64), '24x16': ((24, 16), 2, 32, 64),
+               '16x32': ((16, 32), 3, 48, 128), '32x16': ((32, 16), 1, 80, 192), '32x32': ((32, 32), 2, 64, 64),
+               'hs2': ((16, 16), 2, 256, 512), 'hs4': ((32, 16), 1, 512, 256)}
+
+
+def _wsh(route, name, **kw):
+    HW, B, Cin, Cout = WINO_SHAPES[name]
+    return _wc(route, HW, B, Cin, Cout, **kw)
+
+
+WINO_FWD_CASES = [
+    _wsh('W8', '8x16', **EPI[0]),
+    _wsh('W8', '16x16', **EPI[1]),
+    _wsh('W8', '24x16', own=True, **EPI[2]),
+    _wsh('W8', '16x32', **EPI[3]),
+    _wsh('W8', '32x16', relu_like=True, **EPI[4]),
+    _wsh('W8', '32x32', n_store=36, **EPI[5]),
+    _wsh('W8', '16x16', **EPI[6]),
+    _wsh('W16', '16x16', **EPI[2]),
+    _wsh('W16', '16x32', **EPI[0]),
+    _wsh('W16', '32x16', **EPI[1]),
+    _wsh('W16', '32x32', relu_like=True, **EPI[3]),
+    _wsh('W16', '16x32', **EPI[4]),
+    _wsh('W16', '32x16', n_store=100, **EPI[5]),
+    _wsh('W16', '32x32', **EPI[6]),
+    # H: the pass in front (amax None), maxima handed over (true / raw under a prologue), in_applied; both blocks
+    _wsh('H', '16x16', blk=8, **EPI[3]),
+    _wsh('H', '16x32', blk=16, amax='true', **EPI[0]),
+    _wsh('H', '32x16', blk=8, amax='raw', **EPI[1]),
+    _wsh('H', '32x32', blk=16, amax='applied', **EPI[2]),
+    _wsh('H', '16x32', blk=8, **EPI[4]),
+    _wsh('H', '16x32', blk=16, amax='true', n_store=100, **EPI[5]),           # (its all-zero image: exactly 0)
+    _wsh('H', '32x16', blk=16, relu_like=True, **EPI[6]),
+    _wsh('H', '32x32', blk=8, amax='raw', pro=PRO_AFFINE_RELU, pro_b=0),
+    _wsh('HS', 'hs2', splitk=2, **EPI[0]),
+    _wsh('HS', 'hs2', splitk=2, amax='raw', **EPI[1]),
+    _wsh('HS', 'hs4', splitk=4, amax='applied', **EPI[2]),
+    _wsh('HS', 'hs4', splitk=4, relu_like=True, **EPI[3]),
+    _wsh('HS', 'hs2', splitk=2, blk=16, **EPI[4]),
+    _wsh('HS', 'hs4', splitk=4, n_store=100, amax='true', **EPI[5]),
+    _wsh('HS', 'hs2', splitk=2, blk=8, **EPI[6]),
+]
+
+
+def wino_inputs(g, c):
+    """pw_inputs' operands for a 3x3 case (H, HS: its fp16 x 2 inputs -- the quad 2^-20 below the maximum, the all-zero
+    image of a batch of three, the heavy channel under a prologue), w [Cout, Cin, 3, 3]; relu_like: a non-negative
+    image; PRO_AFFINE: |t| of 2 .. 5 units of the image, so that padding in front of the prologue is far off"""
+    i = pw_inputs(g, dict(c, route='C' if c['route'] in ('H', 'HS') else 'A'))
+    i['w'] = torch.randn(c['Cout'], c['Cin'], 3, 3, generator=g) / math.sqrt(9 * c['Cin'])
+    if c['relu_like']:
+        i['x'] = torch.relu(i['x'])
+    if c['pro'] == PRO_AFFINE:
+        sign = torch.where(torch.rand(i['t'].shape, generator=g) < 0.5, -1.0, 1.0)
+        xmax = i['x'].abs().amax(dim=(1, 2, 3))
+        unit = xmax[:i['t'].shape[0]].view(-1, 1) if c['pro_b'] else xmax[xmax > 0].min()
+        i['t'] = sign * (2.0 + 3.0 * torch.rand(i['t'].shape, generator=g)) * 0.3 * unit
+    return i
+
+
+def wino_refs(c, i, route=None):
+    """-> conv3x3's dict in fp64 (H, HS: both denominators with wino_h2_floor) and the route's fp32 restatement's
+    (route F, the exact-fp32 twin: no restatement, None)"""
+    route = route or c['route']
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    floor = None
+    if route in ('H', 'HS'):
+        _, aabs = pw_prologue(i64['x'], c['pro'], i64.get('s'), i64.get('t'))
+        floor = wino_h2_floor(aabs, i['w'], pw_amax(c, i)[1], i['w'].abs().max())
+    r64 = conv3x3(i64['x'], i64['w'], floor=floor, **pw_kwargs(c, i, torch.float64))
+    if route == 'F':
+        return r64, None
+    return r64, conv3x3(i['x'], i['w'], acc=wino_acc32(c, i, route), **pw_kwargs(c, i, torch.float32))
+
+
+def wino_k(c, route=None, pooled=False):
+    """the bar's k of a 3x3 case, counted like pw_k.  Winograd routes: the rounding of U (1); the two additions of the
+    input transform (2); per k of the deepest slice the additions onto the accumulator (bf16 x 3: six cross terms,
+    fp16 x 2: three) and the slices; the pieces and dropped terms with pw_k's constants (bf16 x 3: 2 + 2; fp16 x 2: 8
+    + 4 + 1 for the floor in the denominator); the output transform, two additions down the rows and two along the
+    columns (4).  Route F, the exact-fp32 direct kernel: a product and an addition per tap and k.  Then pw_k's
+    prologue and epilogue terms"""
+    route = route or c['route']
+    K = c['Cin']
+    if route == 'F':
+        k = 2 * 9 * K
+    else:
+        bf3 = route in ('W8', 'W16', 'WS')                 # (WS: the K-sliced launch that was left on bf16 x 3)
+        sk = c['splitk'] if route in ('HS', 'WS') else 1
+        k = 1 + 2 + (6 if bf3 else 3) * (K // sk) + (sk - 1) + (4 if bf3 else 13) + 4
+    k += (2 if c['pro'] != PRO_NONE else 0) + 1 + c['oscale'] + c['bias'] + 2 * c['noise'] + (c['res'] is not None)
+    if c['act'] == ACT_TANH:
+        k += 2
+    if c['act'] == ACT_LRELU_SQRT2:
+        k = 1.5 * k + 1
+    return k + 2 if pooled and c['pool'] == POOL_SUM else k
+
+
+def wino_onehot(c, tap, seed=0):
+    """exact inputs: x with single power-of-two pixels at the corners, the edges, the seams of the 8x16 / 16x16 blocks
+    and the interior, each in a channel of its own chunk; w with single power-of-two entries on tap (a, b) at a few
+    (cout, cin).  G g G^T, B^T d B and A^T M A then hold sums of at most four powers of two within a few binades --
+    exact in fp32, in three bf16 and in two fp16 pieces"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    x, w = torch.zeros(B, H, W, Cin), torch.zeros(Cout, Cin, 3, 3)
+    spots = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H // 2, 0), (H - 1, W // 2 - 1),
+             (7, 15), (8, 15) if H > 8 else (7, 14), (7, W - 1), (H // 2, W // 2), (3, 5), (4, 6)]
+    spots += [(15, 15), (16, 16), (15, 16), (16, 15)] if H > 16 and W > 16 else \
+        [(7, 16), (8, 16)] if W > 16 else [(15, 7), (16, 8)] if H > 16 else []
+    for n, (py, px) in enumerate(spots):
+        x[(n + seed) % B, py, px, (5 * (n + seed)) % Cin] = 2.0 ** ((n + seed) % 5 - 2)
+    for n in range(10):
+        ci = (5 * (n + seed)) % Cin                                          # (channels the first ten pixels sit in)
+        w[(37 * n + seed) % Cout, ci, tap // 3, tap % 3] = 2.0 ** (n % 3 - 1) * (-1.0) ** n
+    return dict(x=x, w=w)
+
+
+def direct_h2_k(c, slices):
+    """k of the direct fp16 x 2 3x3 kernel in `slices` K slices, counted like pw_k's routes C / D over the nine taps;
+    the case's epilogue: alpha and bias"""
+    return 3 * 9 * (c['Cin'] // slices) + (slices - 1) + 13 + 1 + c['bias']
+
+
+def direct_h2_floor(x, w):
+    """h2_floor over the nine taps (the direct kernel splits a and w themselves), fp64 [B, H, W, N]"""
+    xa, wa = x.double().abs(), w.double().abs()
+    near = F.conv2d(xa.permute(0, 3, 1, 2), torch.ones(1, xa.shape[-1], 3, 3, dtype=torch.float64), padding=1)
+    return 2.0 ** -13 * (xa.amax(dim=(1, 2, 3)).view(-1, 1, 1, 1) * wa.sum(dim=(1, 2, 3)) +
+                         float(wa.max()) * near.permute(0, 2, 3, 1))
+
+
+def producer_amax(y, next_s=None, next_t=None):
+    """[B]: what a maxima producer records for the y it stored, over all its slots: max |y|, or max |fma(y, s, t)| of
+    the affine its reader will fuse (one rounding: the epilogue's y s + t is a fused multiply-add)"""
+    v = y if next_s is None else fma(y, next_s[:, None, None], next_t[:, None, None])
+    return v.abs().amax(dim=(1, 2, 3))
+
+
+def _wac(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, splitk=1, skip=None, pool_sum=False,
+             nomask=False, amax=None, blk=16 if route == 'H' else 0, pro=PRO_NONE, alpha=1.0, own=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def wino_arb_id(c):
+    d = _wac(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+# the launch's Cin -> Cout: the gradient of the 64 -> 64 and 128 -> 48 forward convs, and the 2-slice HS shape
+WINO_ARB_CASES = [_wac(*base, **dict(kw, **v)) for base, kw in [
+    (('W8', (16, 16), 2, 64, 64), {}), (('W16', (16, 16), 2, 64, 64), {}), (('H', (16, 16), 2, 64, 64), dict(blk=8)),
+    (('W8', (16, 32), 2, 48, 128), {}), (('W16', (16, 32), 2, 48, 128), {}),
+    (('H', (16, 32), 2, 48, 128), dict(amax='true')), (('HS', (16, 16), 2, 256, 512), dict(splitk=2))]
+    for v in ARB_VARIANTS]
+
+
+def wino_arb_inputs(g, c):
+    i = arb_inputs(g, dict(c, route='C' if c['route'] in ('H', 'HS') else 'A'))
+    i['w'] = torch.randn(c['Cout'], c['Cin'], 3, 3, generator=g) / math.sqrt(9 * c['Cin'])
+    return i
+
+
+def wino_arb_refs(c, i):
+    """-> conv3x3_arb's dict in fp64 and the route's fp32 restatement's, ds and dt in the kernels' two stages
+    (arb_sums32: an unsplit launch leaves one partial per 8x16-pixel tile in both block shapes, its quads row-major,
+    one row per wave; the K-sliced one one per quad)"""
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=c['Cout'] // 2 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    floor = None
+    if c['route'] in ('H', 'HS'):
+        floor = wino_h2_floor(i['x'].double().abs(), i['w'], pw_amax(c, i)[1], i['w'].abs().max())
+    r64 = conv3x3_arb(i['x'].double(), i['w'].double(), i['ax'].double(), i['as'].double(), i['at'].double(),
+                      floor=floor, **kw)
+    r32 = conv3x3_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], acc=wino_acc32(c, i), **kw)
+    r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], c['route'] == 'HS')
+    return r64, r32
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

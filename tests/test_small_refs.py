@@ -646,3 +646,173 @@ def test_dgrad_restatements_stay_under_a_quarter_of_k(case):
             f = _fig(p32[name], p64[name], p64['den_' + name])
             assert f <= k / 4.0, (name, f, k)
     _draws(body)
+
+
+# ---- Winograd 3x3 convs: the references, restatements and cases of tests/test_wino_kernels_gpu.py -------------------
+@pytest.mark.parametrize('pro,pro_b', [(0, 1), (1, 1), (2, 0)])
+@pytest.mark.parametrize('epi', range(len(R.EPI)))
+def test_conv3x3_is_conv2d_with_the_epilogue(epi, pro, pro_b):
+    """conv3x3 in fp64 == F.conv2d(padding=1) on the prologue's result + the epilogue written out once more; den_d is
+    the same expression on absolute values; den_w is the transform-domain sum written with the matrices B^T, G, A^T
+    on unfolded patches, and bounds the result"""
+    c = R._wc('W8', (4, 6), 3, 16, 32, **dict(R.EPI[epi], pro=pro, pro_b=pro_b, n_store=24))
+    i = {k: (v.to(D) if torch.is_tensor(v) else v) for k, v in R.wino_inputs(_g(150 + epi), c).items()}
+    got = R.conv3x3(i['x'], i['w'], **R.pw_kwargs(c, i, D))
+    a = i['x'].permute(0, 3, 1, 2)
+    if pro:
+        a = a * i['s'].expand(3, -1)[:, :, None, None] + i['t'].expand(3, -1)[:, :, None, None]
+        a = F.relu(a) if pro == R.PRO_AFFINE_RELU else a
+    v = c['alpha'] * F.conv2d(a, i['w'], padding=1)
+    if c['oscale']:
+        v = v * i['oscale'][:, :, None, None]
+    if c['noise']:
+        v = v + i['noise_w'] * i['noise'][:, None]
+    if c['bias']:
+        v = v + i['bias'][None, :, None, None]
+    if c['res']:
+        r = i['res'].permute(0, 3, 1, 2)
+        v = v + (F.interpolate(r, scale_factor=2, mode='nearest') if c['res'] == 'ups' else r)
+    v = {0: lambda u: u, 1: F.relu, 2: torch.tanh, 3: lambda u: F.leaky_relu(u, 0.2) * R.SQRT2}[c['act']](v)
+    if c['mask']:
+        v = v * (i['mask'].permute(0, 3, 1, 2) > 0)
+    v = v[:, :24]
+    assert (got['y'].permute(0, 3, 1, 2) - v).abs().max().item() < 1e-12 * v.abs().max().item()
+    if c['pool']:
+        p = F.max_pool2d(v, 2) if c['pool'] == R.POOL_MAX else F.avg_pool2d(v, 2) * 4
+        assert (got['yp'].permute(0, 3, 1, 2) - p).abs().max().item() < 1e-12 * v.abs().max().item()
+    lr = R.SQRT2 if c['act'] == 3 else 1
+    for den in ('den', 'den_d'):
+        assert bool((got['y'].abs() <= got[den] * (1 + 1e-12) * lr).all()), den
+    pos = {k: (v_.abs() if torch.is_tensor(v_) else abs(v_) if k == 'noise_w' else v_) for k, v_ in i.items()}
+    kw = dict(R.pw_kwargs(c, pos, D), act=R.ACT_NONE, mask=None)
+    assert (R.conv3x3(pos['x'], pos['w'], **kw)['y'] - got['den_d']).abs().max().item() < 1e-12 * got['den_d'].max().item()
+    # den_w of the bare conv, patch by patch with the matrices
+    BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=D).abs()
+    AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=D).abs()
+    aabs = F.pad(got['aabs'].permute(0, 3, 1, 2), (1, 1, 1, 1))
+    d = aabs.unfold(2, 4, 2).unfold(3, 4, 2)                                          # [B, K, Hq, Wq, 4, 4]
+    Vm = torch.einsum('ip,bkyxpq,jq->bkyxij', BT, d, BT)
+    Um = torch.einsum('ia,nkab,jb->nkij', R.WINO_G, i['w'], R.WINO_G).abs()
+    Ym = torch.einsum('ui,bnyxij,vj->byuxvn', AT, torch.einsum('bkyxij,nkij->bnyxij', Vm, Um), AT).reshape(3, 4, 6, 32)
+    assert (R.wino_den(got['aabs'], i['w']) - Ym).abs().max().item() < 1e-12 * Ym.max().item()
+
+
+@pytest.mark.parametrize('v', range(len(R.ARB_VARIANTS)))
+def test_conv3x3_arb_is_autograd_through_the_forward(v):
+    """dx, ds, dt of conv3x3_arb == autograd in fp64 through relu(x s + t) -> up2 -> the 3x3 conv whose input gradient
+    the launch computes (the launch applies the transposed, mirrored kernel), shortcut added"""
+    c = R._wac('W8', (4, 6), 2, 16, 32, **R.ARB_VARIANTS[v])
+    i = {k: t.to(D) for k, t in R.wino_arb_inputs(_g(170 + v), c).items()}
+    pre = i['ax'] * i['as'][:, None, None] + i['at'][:, None, None]
+    i['ax'] = torch.where(pre.abs() < 1e-3 * i['at'].abs()[:, None, None], i['ax'] + 1.0, i['ax'])
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=16 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    got = R.conv3x3_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], **kw)
+    wf = i['w'].permute(1, 0, 2, 3).flip(2, 3)            # the forward conv [Cin, Cout, 3, 3] of this input gradient
+
+    def fwd(x, s, t):
+        a = x * s[:, None, None] + t[:, None, None]
+        a = a if c['nomask'] else torch.relu(a)
+        a = R.up2(a) if c['pool_sum'] else a
+        return F.conv2d(a.permute(0, 3, 1, 2), wf, padding=1).permute(0, 2, 3, 1)
+    dx, ds, dt = R.vjp(fwd, [i['ax'], i['as'], i['at']], i['x'])
+    if c['skip']:
+        sk = i['skip'][..., :16]
+        dx[..., :16] += sk.reshape(2, dx.shape[1], 2, dx.shape[2], 2, 16).sum(dim=(2, 4)) if c['skip'] == 'ups' else sk
+    for name, want in (('dx', dx), ('ds', ds), ('dt', dt)):
+        assert (got[name] - want).abs().max().item() < 1e-12 * want.abs().max().item(), name
+    assert bool((got['dx'].abs() <= got['den_dx'] * (1 + 1e-12)).all())
+    assert bool((got['dx'].abs() <= got['den_dx_d'] * (1 + 1e-12)).all())
+
+
+@pytest.mark.parametrize('case', R.WINO_FWD_CASES, ids=R.wino_id)
+def test_winograd_forward_restatements_stay_under_a_quarter_of_k(case):
+    """for every case's generator and shape the fp32 restatement of its route is within k / 4 of the fp64 reference on
+    den_w: k and the fp16 x 2 floor were not set from the kernels.  Under PRO_AFFINE padding in FRONT of the prologue
+    would be more than 100 bars off at the border"""
+    def body(gen):
+        i = R.wino_inputs(gen('wino', R.wino_id(case)), case)
+        r64, r32 = R.wino_refs(case, i)
+        for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+            if r64[out] is not None:
+                f = _fig(r32[out], r64[out], r64[den])
+                assert f <= R.wino_k(case, None, pooled) / 4.0, (out, f, R.wino_k(case, None, pooled))
+        if case['pro'] == R.PRO_AFFINE and case['act'] == R.ACT_NONE and not case['mask']:
+            kw = R.pw_kwargs(case, i, D)
+            a, _ = R.pw_prologue(i['x'].double(), case['pro'], i['s'].double(), i['t'].double())
+            t_ = i['t'].double().expand(case['B'], -1)[:, None, None, :]
+            ap = F.pad(a - t_, (0, 0, 1, 1, 1, 1)) + t_                   # x s padded, t added after: the halo holds t
+            wrong = F.conv2d(ap.permute(0, 3, 1, 2), i['w'].double()).permute(0, 2, 3, 1) * case['alpha']
+            wrong = R.conv_epilogue(wrong, r64['den'], **{k: v for k, v in kw.items() if k not in ('pro', 's', 't', 'alpha')})
+            for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+                if r64[out] is None:
+                    continue
+                err = (wrong[out] - r64[out]).abs() / r64[den] / R.U
+                border = torch.ones(err.shape[1:3], dtype=torch.bool)
+                border[1:-1, 1:-1] = False
+                xmax = i['x'].abs().amax(dim=(1, 2, 3))
+                b0 = int(torch.where(xmax > 0, xmax, xmax.max()).argmin())    # (a shared t is scaled to this image)
+                live = r64[den][b0][border] > 0
+                bar = min(R.wino_k(case, None, pooled), 4.0 * _fig(r32[out], r64[out], r64[den]))
+                assert float(err[b0][border][live].median()) > 100 * bar, (out, bar)
+                assert float(err[:, ~border].max()) < 1e-3
+    _draws(body)
+
+
+@pytest.mark.parametrize('case', R.WINO_ARB_CASES, ids=R.wino_arb_id)
+def test_winograd_dgrad_restatements_stay_under_a_quarter_of_k(case):
+    def body(gen):
+        i = R.wino_arb_inputs(gen('warb', R.wino_arb_id(case)), case)
+        kdx, kds, kdt = R.arb_k(case, R.wino_k)
+        r64, r32 = R.wino_arb_refs(case, i)
+        f = _fig(r32['dx'], r64['dx'], r64['den_dx'])
+        assert f <= kdx / 4.0, ('dx', f, kdx)
+        for name, bound in zip(('ds', 'dt'), R.arb_bound(case, r64, i['ax'], R.wino_k)):
+            assert bool(((r32[name].double() - r64[name]).abs() <= bound * R.U).all()), name
+        p64, p32 = R.wino_arb_refs(case, R.arb_positive(i))
+        for name, k in (('ds', kds), ('dt', kdt)):
+            f = _fig(p32[name], p64[name], p64['den_' + name])
+            assert f <= k / 4.0, (name, f, k)
+    _draws(body)
+
+
+@pytest.mark.parametrize('tap', range(9))
+def test_winograd_one_hot_inputs_are_exact_in_every_restatement(tap):
+    """single power-of-two pixels and weights go through G g G^T, B^T d B, the bf16 x 3 / fp16 x 2 pieces and A^T M A
+    without a rounding: all three restatements give the fp64 result bit for bit, and it is not all zero"""
+    for route, shape, kw in (('W8', '16x32', {}), ('H', '16x32', {}), ('HS', 'hs2', dict(splitk=2))):
+        c = R._wsh(route, shape, **kw)
+        for seed in range(3):
+            i = R.wino_onehot(c, tap, seed)
+            r64, r32 = R.wino_refs(c, i)
+            assert torch.equal(r32['y'].double(), r64['y']), (route, seed)
+            assert int((r64['y'] != 0).sum()) >= 3, (route, seed)
+
+
+def test_winograd_headroom_of_the_fp16_scales():
+    """an image maximum nextafter(2^e, 0) in the +, -, -, + pattern that drives B^T d B to 4 max: times the image's
+    power of two the transformed value stays below 2^15, finite in fp16, and the two pieces hold it to 2^-22; U = G g
+    G^T stays below 2.25 max |w|"""
+    m = torch.tensor(2.0 ** 5).nextafter(torch.tensor(0.0))
+    x = torch.zeros(1, 8, 16, 16)
+    x[0, 1, 1, 3], x[0, 1, 3, 3], x[0, 3, 1, 3], x[0, 3, 3, 3] = m, -m, -m, m
+    xs, _ = R.h2_scales(x.abs().amax(dim=(1, 2, 3)))
+    V = R.wino_V(x * xs.view(-1, 1, 1, 1))
+    assert float(V.abs().max()) == float(4 * m * xs[0]) < 2.0 ** 15
+    h, l = R.split2(V)
+    assert bool(torch.isfinite(h).all()) and bool(((h.double() + l.double() - V.double()).abs() <= 2.0 ** -22 * V.abs().double()).all())
+    w = torch.full((64, 16, 3, 3), 0.7)
+    assert float(R.wino_U(w).abs().max()) <= 2.25 * 0.7 * (1 + 1e-12)
+
+
+def test_winograd_case_tables():
+    """every EPI term on every route; both H blocks and all three sources of its maxima; the HS slice counts"""
+    for route in ('W8', 'W16', 'H', 'HS'):
+        cs = [c for c in R.WINO_FWD_CASES if c['route'] == route]
+        for e in R.EPI:
+            assert any(all(c[k] == v for k, v in e.items()) for c in cs), (route, e)
+        assert any(c['n_store'] < c['Cout'] for c in cs) and any(c['pro'] and not c['pro_b'] for c in cs)
+    hs = [c for c in R.WINO_FWD_CASES if c['route'] == 'H']
+    assert set((c['blk'], c['amax']) for c in hs) >= set([(8, None), (16, 'true'), (8, 'raw'), (16, 'applied')])
+    assert len(set(R.wino_id(c) for c in R.WINO_FWD_CASES)) == len(R.WINO_FWD_CASES)
+    assert len(set(R.wino_arb_id(c) for c in R.WINO_ARB_CASES)) == len(R.WINO_ARB_CASES)
