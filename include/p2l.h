@@ -381,9 +381,22 @@ enum {
   /* the fp16 x 2 sub-pixel FORWARD kernel with one output phase per block (four blocks stage the same patch) instead *
    * of two on one staged patch (round 6, bit-identical; tests, A/B)                                              */
   P2L_FORM_NO_SP_PAIR = 2048,
-  P2L_FORM_SP_PAIR = 4096       /* ... two phases per block for every sub-pixel forward launch (default: the        *
+  P2L_FORM_SP_PAIR = 4096,      /* ... two phases per block for every sub-pixel forward launch (default: the        *
                                  * transposed convs with 64-channel tiles only)                                   */
+  /* The fp16 x 2 Winograd and full-tile 1x1 kernels carry their epilogue compiled for the kinds of launch the  *
+   * plans make (p2l_conv_epilogue_class != 0); this bit runs the shared run-time item instead: same bits       *
+   * (tests, A/B)                                                                                               */
+  P2L_FORM_GENERIC_EPI = 8192
 };
+/* Which compiled epilogue a launch gets: 0 = the shared item, otherwise the class (csrc/p2l_conv_k.h EPI_*) of
+ * the kernel instantiation that runs it.  Decided from the launch descriptor -- the route it takes and which
+ * operands are present (only whether a pointer is NULL is looked at, and whether `workspace` / `ws_bytes` let the
+ * launch take its fp16 x 2 form) -- never from d->B.  Takes what p2l_conv_fwd_ex (arb == NULL) or
+ * p2l_conv_dgrad_arb_ws (arb != NULL, y = dx) would be given.  A pure host function: no device call, no
+ * allocation; a descriptor the launch would refuse gives 0. */
+int p2l_conv_epilogue_class(const P2LConv* d, const P2LConvExtra* ex, const P2LArb* arb, const float* bias,
+                            const float* res, const float* mask, const float* y, const float* yp,
+                            const void* workspace, size_t ws_bytes);
 /* K slices of a small-grid Winograd layer: 3x3 layers with 16..63 blocks of 8x16 pixels x 64
  * channels per image (H, W multiples of 16) run the 16x16 Winograd kernel with the input channels
  * cut into this many slices (2 or 4; >= 8 chunks of 16 channels each) and the deterministic

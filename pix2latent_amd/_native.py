@@ -178,6 +178,7 @@ FORM_NO_SP_SKIP = 1024
 FORM_NO_SP_PAIR = 2048
 FORM_SP_PAIR = 4096
 FORM_NO_H2R = 256                                    # the chunked direct kernel where the register-resident one would run
+FORM_GENERIC_EPI = 8192                              # the shared run-time epilogue item where a compiled one would run
 
 
 def default_wfmt():
@@ -274,7 +275,7 @@ PRO_NONE, PRO_AFFINE_RELU, PRO_AFFINE = 0, 1, 2
 # every symbol include/p2l.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     'p2l_version', 'p2l_strerror', 'p2l_last_hip_error',
-    'p2l_conv_workspace_bytes', 'p2l_conv_amax_slots', 'p2l_selftest_amaxreg', 'p2l_conv_suggest_splitk', 'p2l_conv_fwd', 'p2l_conv_fwd_ex',
+    'p2l_conv_workspace_bytes', 'p2l_conv_amax_slots', 'p2l_conv_epilogue_class', 'p2l_selftest_amaxreg', 'p2l_conv_suggest_splitk', 'p2l_conv_fwd', 'p2l_conv_fwd_ex',
     'p2l_pack_conv_weight', 'p2l_pack_conv_weight_subpix', 'p2l_pack_conv_weight_bf3',
     'p2l_pack_conv_weight_bf3w', 'p2l_packed_weight_floats', 
     'p2l_pack_conv_weight_bf3t',
@@ -357,6 +358,7 @@ def lib():
         # the small entry points that take an int64_t count or a float: a bare Python number would travel as C int
         vp, i32, i64_, f32_ = C.c_void_p, C.c_int, C.c_int64, C.c_float
         _lib.p2l_relu_mask.argtypes = [vp, i32, vp, i32, vp, i32, i64_, i32, vp]
+        _lib.p2l_conv_epilogue_class.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
         _lib.p2l_tanh_bwd16.argtypes = [vp, vp, i64_, vp]
         _lib.p2l_clamp.argtypes = [vp, i64_, f32_, f32_, vp]
         _lib.p2l_adam_step.argtypes = [vp, vp, vp, vp, i64_, f32_, f32_, f32_, f32_, i32, vp]

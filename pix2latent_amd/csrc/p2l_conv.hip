@@ -1344,7 +1344,8 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
                             const float* bias, const float* pro_s,
                             const float* pro_t, const float* res,
                             const float* mask, float* y, float* yp,
-                            void* workspace, size_t ws_bytes, void* stream) {
+                            void* workspace, size_t ws_bytes, void* stream, int* dry_class = nullptr) {
+  // dry_class: nothing is launched; *dry_class = the epilogue class the launch would run (p2l_conv_epilogue_class)
   if (!d || !x || !w) return P2L_EINVAL;
   if (d->taps != 1 && d->taps != 9) return P2L_EINVAL;
   const int kc = (d->taps == 9) ? 16 : (d->Cin % 32 == 0 ? 32 : 16);
@@ -1483,7 +1484,8 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   hipStream_t st = (hipStream_t)stream;
 
   int prof_slot = -1;
-  bool prof_ok = g_prof.on;
+  bool prof_ok = g_prof.on && !dry_class;
+  if (dry_class) *dry_class = EPI_GENERIC;   // (every route below answers in front of its first launch)
   if (prof_ok) {
     // an event pair recorded during stream capture becomes graph nodes and can never be read
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1542,6 +1544,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     } else {
       kw.splitk = 1;
     }
+    if (dry_class) { *dry_class = p2l_wino_epi_class(kw, d->pro); return P2L_OK; }
     rc = p2l_wino_launch(kw, d->pro, st);
     if (rc == P2L_OK && wino_sliced) {
       // the slices meet in the deterministic finish kernel of the direct path: fixed-order sum,
@@ -1569,6 +1572,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     kp.n_ntiles = d->Cout / 64;
     kp.nchunks = d->Cin / 64;
     kp.splitk = 1;
+    if (dry_class) { *dry_class = p2l_pw_epi_class(kp, d->pro); return P2L_OK; }
     rc = p2l_pw_launch(kp, d->pro, st);
     if (prof_slot >= 0) {
       if (k.amax_in != nullptr) g_prof.nprod[prof_slot] = 3;
@@ -1582,6 +1586,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     const int tm = thin_shape(d);
     const bool geom = k.tw_log == 4 && k.th_log == 3 && k.tb_log == 0 && !k.partial && !(ex && (ex->oscale || ex->noise));
     if (tm == 1 && geom) {
+      if (dry_class) return P2L_OK;
       ConvK kt = k;
       kt.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
       kt.splitk = 1;
@@ -1594,6 +1599,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
       return rc;
     }
     if (tm == 0 && geom && !arb && !res && !mask && d->pool == P2L_POOL_NONE && y) {
+      if (dry_class) return P2L_OK;
       ConvK kt = k;
       kt.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
       kt.nchunks = d->Cin / 16;
@@ -1648,6 +1654,10 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
       kh.hp = halo_pitch_h2(1 << k.tw_log);
       kh.w = w + (size_t)16 * d->Cout * d->Cin * 3 / 2;
       kh.w_tail = reinterpret_cast<const unsigned*>(kh.w + (size_t)16 * d->Cout * d->Cin);
+      if (dry_class) {                      // (the paired forward kernel, taps = 8, keeps the shared item)
+        *dry_class = d->ups == 3 ? p2l_h2_epi_class(kh, d->pro, 4) : EPI_GENERIC;
+        return P2L_OK;
+      }
       if (kh.amax_in == nullptr) {
         ConvK ka = kh;                      // the INPUT tensor: low-res (forward) / high-res frame (gradient)
         ka.H = k.ibH; ka.W = k.ibW;
@@ -1688,6 +1698,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     size_t lds_sp = (size_t)(a_lds_sp + 4 * bn) * (bf3 ? 24 : 20) * sizeof(float);
     const size_t lds_epi = (size_t)4 * 32 * (bn + 4) * sizeof(float);
     if (lds_epi > lds_sp) lds_sp = lds_epi;
+    if (dry_class) return P2L_OK;
     dim3 grid(k.n_mtiles * k.n_ntiles, d->ups == 2 ? 4 : 1), block(256);
 #define P2L_LAUNCH_SP(BNV, AIT, PROV)                                                     \
     do {                                                                                  \
@@ -1740,14 +1751,20 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     if (p2l_wino_weight_ok(d->Cout, d->Cin))
       kh.w += p2l_wino_weight_floats(d->Cout, d->Cin) + p2l_wino_h2_weight_floats(d->Cout, d->Cin);
     kh.w_tail = reinterpret_cast<const unsigned*>(kh.w + (size_t)9 * d->Cout * d->Cin);
+    const bool small = (a_rows * 4 <= 3 * 256) && TB == 1;
+    const bool h2r = direct_h2r(d) && k.splitk == 1 && !k.partial && TB == 1 && p2l_h2r_takes(kh);
+    if (dry_class) {                        // (the register-resident kernel has epilogues of its own)
+      *dry_class = h2r ? EPI_GENERIC : p2l_h2_epi_class(kh, d->pro, 9);
+      return P2L_OK;
+    }
     if (kh.amax_in == nullptr) {
       rc = p2l_amax_launch(kh, d->pro, st);
       if (rc) return rc;
     }
-    const bool small = (a_rows * 4 <= 3 * 256) && TB == 1;
-    const bool h2r = direct_h2r(d) && k.splitk == 1 && !k.partial && TB == 1 && p2l_h2r_takes(kh);
     rc = h2r ? p2l_h2r_launch(kh, d->pro, st) : p2l_h2_launch(kh, d->pro, 9, bn, small, st);
     if (prof_slot >= 0) { g_prof.nprod[prof_slot] = 3; g_prof.fam[prof_slot] = h2r ? P2L_PROF_FAM_DIRECT_H2R : P2L_PROF_FAM_DIRECT_H2; }
+  } else if (dry_class) {
+    return P2L_OK;
   } else
   if (d->taps == 9) {
     const bool small = (a_rows * 4 <= 3 * 256) && TB == 1;
@@ -1812,6 +1829,25 @@ extern "C" int p2l_conv_fwd_ex(const P2LConv* d, const P2LConvExtra* ex, const f
                                void* stream) {
   return conv_launch_impl(d, nullptr, ex, x, w, bias, pro_s, pro_t, res, mask, y, yp, workspace,
                           ws_bytes, stream);
+}
+
+extern "C" int p2l_conv_epilogue_class(const P2LConv* d, const P2LConvExtra* ex, const P2LArb* arb,
+                                       const float* bias, const float* res, const float* mask, const float* y,
+                                       const float* yp, const void* workspace, size_t ws_bytes) {
+  if (!d) return 0;
+  // x, w and the prologue vectors only have to be there: nothing is read through any pointer
+  const float* some = reinterpret_cast<const float*>(d);
+  P2LConv dd = *d;
+  if (arb) {                                             // (as p2l_conv_dgrad_arb_ws hands the launch on)
+    if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
+    if (effective_splitk(&dd) <= 1) dd.splitk = 1;
+    if (dd.pool == P2L_POOL_SUM) { yp = y; y = nullptr; }
+  }
+  int ec = 0;
+  const int rc = conv_launch_impl(&dd, arb, arb ? nullptr : ex, some, some, arb ? nullptr : bias, some, some,
+                                  arb ? nullptr : res, arb ? nullptr : mask, const_cast<float*>(y),
+                                  const_cast<float*>(yp), const_cast<void*>(workspace), ws_bytes, nullptr, &ec);
+  return rc == P2L_OK ? ec : 0;
 }
 
 extern "C" int p2l_conv_arb_fusable(const P2LConv* d) {

@@ -335,6 +335,186 @@ __device__ __forceinline__ void epi_item(const ConvK& k, f32x4 (&v)[4], int b, i
   }
 }
 
+// ---- the item compiled for ONE kind of launch -------------------------------------------------
+// epi_item decides every term at run time: a launch uses three or four of its dozen, the rest are tests
+// and control-flow merges around the four stores of a quad.  epi_item_ct<EC> performs exactly the
+// operations of epi_item for the launches of class EC, in epi_item's order, with nothing left to decide:
+// the bits do not change (tests/test_epilogue_forms_gpu.py).  A class takes a launch only on whole tiles
+// (!k.partial), osh == 0, without the StyleGAN2 terms (oscale, noise) and with k.y present; everything
+// else -- and every launch that carries P2L_FORM_GENERIC_EPI -- is epi_item's.
+enum {
+  EPI_GENERIC = 0,
+  EPI_BIAS_PS = 1,          // y = acc + bias; maxima of |y*ns + nt|            (GenBlock conv_0 .. conv_2)
+  EPI_BIAS_RES_PS = 2,      // ... + residual at the same resolution            (GenBlock conv_3, o_conv)
+  EPI_BIAS_RESUP_PS = 3,    // ... + residual read nearest-x2                   (GenBlock conv_3 of an up block)
+  EPI_BIAS_RELU = 4,        // y = relu(acc + bias); maxima of |y|              (VGG forward)
+  EPI_BIAS_RELU_POOL = 5,   // ... + 2x2 max pool to yp with its maxima         (VGG forward, last conv of a stage)
+  EPI_MASK = 6,             // y = mask > 0 ? acc : 0; maxima of |y|            (VGG input gradients)
+  EPI_ARB = 7,              // fused activation backward; maxima of |dx|        (GenBlock conv_3 .. conv_1 gradients)
+  EPI_ARB_SKIP = 8,         // ... + shortcut gradient at the same resolution   (GenBlock conv_0 gradient)
+  EPI_ARB_SKIP_UP = 9,      // ... + its 2x2 children summed (a+b)+(c+d)        (conv_0 gradient of an up block)
+  EPI_N_CLASSES = 10
+};
+struct EpiDesc {
+  bool bias;
+  int res;      // 0 none, 1 same resolution, 2 nearest-up
+  bool relu, mask;
+  int pool;     // 0 none, 1 max, 2 max with the maxima of yp
+  int amax;     // 0 none, 1 plain, 2 with the reader's affine (amax_ps / amax_pt)
+  int arb;      // 0 none, 1 plain, 2 skip, 3 skip with 2x2 children
+};
+constexpr EpiDesc epi_desc(int ec) {
+  switch (ec) {
+    case EPI_BIAS_PS:        return {true, 0, false, false, 0, 2, 0};
+    case EPI_BIAS_RES_PS:    return {true, 1, false, false, 0, 2, 0};
+    case EPI_BIAS_RESUP_PS:  return {true, 2, false, false, 0, 2, 0};
+    case EPI_BIAS_RELU:      return {true, 0, true, false, 0, 1, 0};
+    case EPI_BIAS_RELU_POOL: return {true, 0, true, false, 2, 1, 0};
+    case EPI_MASK:           return {false, 0, false, true, 0, 1, 0};
+    case EPI_ARB:            return {false, 0, false, false, 0, 1, 1};
+    case EPI_ARB_SKIP:       return {false, 0, false, false, 0, 1, 2};
+    case EPI_ARB_SKIP_UP:    return {false, 0, false, false, 0, 1, 3};
+    default:                 return {false, 0, false, false, 0, 0, 0};
+  }
+}
+// The class of a launch, from its descriptor alone (never from the batch: a candidate's code path must not
+// depend on who shares the launch).  A kernel family then keeps the classes it has instantiations for.
+inline int epi_class(const ConvK& k) {
+#ifdef P2L_AB_GENERIC_EPI               // (A/B builds: the shared item everywhere)
+  return EPI_GENERIC;
+#endif
+  if (k.form & P2L_FORM_GENERIC_EPI) return EPI_GENERIC;
+  if (k.partial || k.oscale || k.noise || !k.y || k.sp_mode == 1 || k.splitk > 1) return EPI_GENERIC;
+  if (!k.amax_out) return EPI_GENERIC;                  // (every class records the maxima of y)
+  if (k.arb_x) {
+    if (k.arb_nomask || k.pool != P2L_POOL_NONE || k.amax_outp) return EPI_GENERIC;
+    return !k.arb_skip ? EPI_ARB : (k.arb_skip_ups ? EPI_ARB_SKIP_UP : EPI_ARB_SKIP);
+  }
+  const bool ps = k.amax_ps != nullptr;
+  if (k.bias && !k.mask && k.act == P2L_ACT_NONE && k.pool == P2L_POOL_NONE && ps && !k.amax_outp)
+    return !k.res ? EPI_BIAS_PS : (k.res_ups ? EPI_BIAS_RESUP_PS : EPI_BIAS_RES_PS);
+  if (k.bias && !k.res && !k.mask && k.act == P2L_ACT_RELU && !ps) {
+    if (k.pool == P2L_POOL_NONE && !k.amax_outp) return EPI_BIAS_RELU;
+    if (k.pool == P2L_POOL_MAX && k.yp && k.amax_outp) return EPI_BIAS_RELU_POOL;
+    return EPI_GENERIC;
+  }
+  if (!k.bias && !k.res && k.mask && k.act == P2L_ACT_NONE && k.pool == P2L_POOL_NONE && !ps && !k.amax_outp)
+    return EPI_MASK;
+  return EPI_GENERIC;
+}
+// the (prologue, class) pairs the plans launch, per kernel family: what is instantiated
+inline int epi_class_wino(const ConvK& k, int pro) {
+  const int ec = epi_class(k);
+  if (pro == P2L_PRO_AFFINE_RELU) return ec == EPI_BIAS_PS ? ec : EPI_GENERIC;
+  if (pro == P2L_PRO_NONE)
+    return (ec == EPI_BIAS_RELU || ec == EPI_BIAS_RELU_POOL || ec == EPI_MASK || ec == EPI_ARB) ? ec : EPI_GENERIC;
+  return EPI_GENERIC;
+}
+inline int epi_class_h2(const ConvK& k, int pro, int taps) {
+  if (pro != P2L_PRO_NONE) return EPI_GENERIC;
+  const int ec = epi_class(k);
+  // (the masked 64 -> 64 gradients of the VGG run on the register-resident kernel, the wider ones in Winograd form)
+  if (taps == 9) return ec == EPI_ARB ? ec : EPI_GENERIC;
+  // sub-pixel input gradient (the forward form writes output phases: osh = 1)
+  if (taps == 4 && k.sp_mode == 2 && !k.sp_skip) return ec == EPI_ARB ? ec : EPI_GENERIC;
+  return EPI_GENERIC;
+}
+inline int epi_class_pw(const ConvK& k, int pro) {
+  const int ec = epi_class(k);
+  if (pro == P2L_PRO_AFFINE_RELU)
+    return (ec == EPI_BIAS_PS || ec == EPI_BIAS_RES_PS || ec == EPI_BIAS_RESUP_PS) ? ec : EPI_GENERIC;
+  if (pro == P2L_PRO_NONE)
+    return (ec == EPI_ARB || ec == EPI_ARB_SKIP || ec == EPI_ARB_SKIP_UP) ? ec : EPI_GENERIC;
+  return EPI_GENERIC;
+}
+
+template <int EC>
+__device__ __forceinline__ void epi_item_ct(const ConvK& k, f32x4 (&v)[4], int b, int oy0, int ox0,
+                                            int n, EpiSums& S) {
+  constexpr EpiDesc D = epi_desc(EC);
+  static_assert(EC > EPI_GENERIC && EC < EPI_N_CLASSES, "a class of its own");
+  const unsigned OW = (unsigned)k.obW;
+  const unsigned pix0 = ((unsigned)(b * k.obH) + (unsigned)oy0) * OW + (unsigned)ox0;
+  const unsigned sub[4] = {0u, 1u, OW, OW + 1u};
+  const unsigned ppix = (unsigned)((b * (k.H >> 1) + (oy0 >> 1)) * (k.W >> 1) + (ox0 >> 1));
+  // v arrives as acc * alpha, ROUNDED: epi_item multiplies it by a run-time oscale next, so nothing can be
+  // contracted into that product there.  Here the next operation is an addition, which hipcc would fuse with
+  // the caller's multiplication into one fma -- another rounding.  The values are made opaque instead.
+#pragma unroll
+  for (int s = 0; s < 4; ++s) asm("" : "+v"(v[s]));
+  if constexpr (D.arb == 0) {
+    // (epi_item: v*1 + bias4 with bias4 = 0 where there is none -- the addition stays, -0 + 0 = +0)
+    f32x4 bias4 = {0, 0, 0, 0};
+    if constexpr (D.bias) bias4 = ld4(k.bias, (unsigned)n);
+    f32x4 ns4 = {1.f, 1.f, 1.f, 1.f}, nt4 = {0, 0, 0, 0};
+    if constexpr (D.amax == 2) {
+      ns4 = ld4(k.amax_ps, (unsigned)(b * k.amax_pbstride + n));
+      nt4 = ld4(k.amax_pt, (unsigned)(b * k.amax_pbstride + n));
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned pix = pix0 + sub[s];
+      f32x4 t = v[s] + bias4;
+      if constexpr (D.res != 0) t += ld4(k.res, (D.res == 2 ? ppix : pix) * (unsigned)k.res_ld + (unsigned)n);
+      if constexpr (D.relu) t = act4(t, P2L_ACT_RELU);
+      if constexpr (D.mask) {
+        const f32x4 m = ld4(k.mask, pix * (unsigned)k.mask_ld + (unsigned)n);
+        t.x = m.x > 0.f ? t.x : 0.f; t.y = m.y > 0.f ? t.y : 0.f;
+        t.z = m.z > 0.f ? t.z : 0.f; t.w = m.w > 0.f ? t.w : 0.f;
+      }
+      st4(k.y, pix * (unsigned)k.y_ld + (unsigned)n, t);
+      if constexpr (D.amax == 2) S.amax = absmax4(S.amax, t * ns4 + nt4);
+      else if constexpr (D.amax == 1) S.amax = absmax4(S.amax, t);
+      v[s] = t;
+    }
+    if constexpr (D.pool != 0) {
+      f32x4 p;
+      p.x = fmaxf(fmaxf(v[0].x, v[1].x), fmaxf(v[2].x, v[3].x));
+      p.y = fmaxf(fmaxf(v[0].y, v[1].y), fmaxf(v[2].y, v[3].y));
+      p.z = fmaxf(fmaxf(v[0].z, v[1].z), fmaxf(v[2].z, v[3].z));
+      p.w = fmaxf(fmaxf(v[0].w, v[1].w), fmaxf(v[2].w, v[3].w));
+      st4(k.yp, ppix * (unsigned)k.yp_ld + (unsigned)n, p);
+      if constexpr (D.pool == 2) S.amaxp = absmax4(S.amaxp, p);
+    }
+  } else {
+    const f32x4 s4 = ld4(k.arb_s, (unsigned)(b * k.arb_bstride + n));
+    const f32x4 t4 = ld4(k.arb_t, (unsigned)(b * k.arb_bstride + n));
+    const bool has_skip = D.arb >= 2 && n < k.arb_skip_C;   // (the shortcut covers the first skip_C channels)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned pix = pix0 + sub[s];
+      const f32x4 xv = ld4(k.arb_x, pix * (unsigned)k.arb_x_ld + (unsigned)n);
+      const f32x4 pre = xv * s4 + t4;
+      f32x4 g = v[s];
+      g.x = pre.x > 0.f ? g.x : 0.f; g.y = pre.y > 0.f ? g.y : 0.f;
+      g.z = pre.z > 0.f ? g.z : 0.f; g.w = pre.w > 0.f ? g.w : 0.f;
+      f32x4 o = g * s4;
+      if (has_skip) {
+        const unsigned ld = (unsigned)k.arb_skip_ld;
+        if constexpr (D.arb == 3) {
+          const unsigned W2 = 2u * (unsigned)k.W;
+          const unsigned cq = ((unsigned)(b * 2 * k.H + 2 * (oy0 + (s >> 1)))) * W2 + 2u * (unsigned)(ox0 + (s & 1));
+          o += (ld4(k.arb_skip, cq * ld + n) + ld4(k.arb_skip, (cq + 1) * ld + n)) +
+               (ld4(k.arb_skip, (cq + W2) * ld + n) + ld4(k.arb_skip, (cq + W2 + 1) * ld + n));
+        } else {
+          o += ld4(k.arb_skip, pix * ld + (unsigned)n);
+        }
+      }
+      st4(k.y, pix * (unsigned)k.y_ld + (unsigned)n, o);
+      if constexpr (D.amax != 0) S.amax = absmax4(S.amax, o);
+      S.sgx += g * xv;
+      S.sg += g;
+    }
+  }
+}
+// EC = EPI_GENERIC: the shared item
+template <int EC>
+__device__ __forceinline__ void epi_item_of(const ConvK& k, f32x4 (&v)[4], int b, int oy0, int ox0,
+                                            int n, int osh, int ph_y, int ph_x, EpiSums& S) {
+  if constexpr (EC == EPI_GENERIC) epi_item(k, v, b, oy0, ox0, n, osh, ph_y, ph_x, S);
+  else epi_item_ct<EC>(k, v, b, oy0, ox0, n, S);
+}
+
 // ARB: per-(block, channel) partial sums of g*x and g.  Lanes with equal (lane % C4) hold the
 // same 4 channels for different quads; NW = 4 waves took part.  `slot` = row of arb_partial
 // ((image * arb_nblk + tile) of the 128-pixel tiling the caller sized the buffer for).
@@ -396,11 +576,12 @@ __device__ __forceinline__ void epi_arb_reduce(const ConvK& k, EpiSums& S, float
 // The second half of epilogue_vec: the dumps [4 pixel groups of 32][COLS + 4] are in `smem` and visible; wave w
 // works through pixel group w.  (Separate so that a kernel with another wave -> accumulator mapping --
 // p2l_h2r.hip: a wave owns 64 pixels x 32 channels -- can fill the same dumps and share everything behind.)
-template <int NT>
+// EC: the launch's epilogue class (EPI_GENERIC = the shared item, decided at run time)
+template <int NT, int EC = EPI_GENERIC>
 __device__ __forceinline__ void epilogue_vec_items(const ConvK& k, float* smem, int wave, int lane, int b0,
                                                    int y0, int x0, int n0, int tile_in_image, int osh,
                                                    int ph_y, int ph_x);
-template <int NT>
+template <int NT, int EC = EPI_GENERIC>
 __device__ __forceinline__ void epilogue_vec(const ConvK& k, const f32x16 (&acc)[NT],
                                              float* smem, int wave, int lane, int b0, int y0,
                                              int x0, int n0, int tile_in_image, int osh,
@@ -414,13 +595,14 @@ __device__ __forceinline__ void epilogue_vec(const ConvK& k, const f32x16 (&acc)
     for (int r = 0; r < 16; ++r)
       tb[((r & 3) + 8 * (r >> 2) + 4 * lhi) * EP + j * 32 + l31] = acc[j][r];
   __syncthreads();
-  epilogue_vec_items<NT>(k, smem, wave, lane, b0, y0, x0, n0, tile_in_image, osh, ph_y, ph_x);
+  epilogue_vec_items<NT, EC>(k, smem, wave, lane, b0, y0, x0, n0, tile_in_image, osh, ph_y, ph_x);
 }
-template <int NT>
+template <int NT, int EC>
 __device__ __forceinline__ void epilogue_vec_items(const ConvK& k, float* smem, int wave, int lane, int b0,
                                                    int y0, int x0, int n0, int tile_in_image, int osh,
                                                    int ph_y, int ph_x) {
   constexpr int COLS = NT * 32, EP = COLS + 4, C4 = COLS / 4, ITEMS = 8 * C4;
+  constexpr EpiDesc D = epi_desc(EC);
   float* tb = smem + wave * 32 * EP;
 
   const int TWh = (1 << k.tw_log) >> 1, THh = (1 << k.th_log) >> 1;
@@ -440,16 +622,16 @@ __device__ __forceinline__ void epilogue_vec_items(const ConvK& k, float* smem, 
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       v[s] = *reinterpret_cast<const f32x4*>(tb + (4 * q + s) * EP + c4 * 4) * k.alpha;
-    epi_item(k, v, b, oy0, ox0, n, osh, ph_y, ph_x, Sx);
+    epi_item_of<EC>(k, v, b, oy0, ox0, n, osh, ph_y, ph_x, Sx);
   }
   static_assert(ITEMS == 64 || ITEMS == 128, "one or two items per lane");
-  if (k.arb_x != nullptr)
+  if (EC == EPI_GENERIC ? k.arb_x != nullptr : D.arb != 0)
     epi_arb_reduce<COLS, C4>(k, S, smem, wave, lane, threadIdx.x,
                              (size_t)b0 * k.arb_nblk + tile_in_image, n0, &S2);
   S.amax = fmaxf(S.amax, S2.amax); S.amaxp = fmaxf(S.amaxp, S2.amaxp);
   // this block's partial maxima of what it stored (one per wave), for the launch that reads the
   // tensor next (P2LAmax; the launcher only sets the pointers for tiles inside one image)
-  if (k.amax_out != nullptr || k.amax_outp != nullptr) {
+  if (EC == EPI_GENERIC ? (k.amax_out != nullptr || k.amax_outp != nullptr) : (D.amax != 0 || D.pool == 2)) {
     float m = S.amax, mp = S.amaxp;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); mp = fmaxf(mp, __shfl_xor(mp, o, 64)); }
@@ -457,8 +639,8 @@ __device__ __forceinline__ void epilogue_vec_items(const ConvK& k, float* smem, 
       const int nph = osh ? 4 : 1;
       const size_t slot = (size_t)b0 * k.amax_out_n +
                           (((size_t)tile_in_image * k.n_ntiles + n0 / COLS) * nph + (osh ? ph_y * 2 + ph_x : 0)) * 4 + wave;
-      if (k.amax_out != nullptr) k.amax_out[slot] = m;
-      if (k.amax_outp != nullptr) k.amax_outp[slot] = mp;
+      if (EC == EPI_GENERIC ? k.amax_out != nullptr : D.amax != 0) k.amax_out[slot] = m;
+      if (EC == EPI_GENERIC ? k.amax_outp != nullptr : D.pool == 2) k.amax_outp[slot] = mp;
     }
   }
 }
@@ -468,6 +650,11 @@ __device__ __forceinline__ void epilogue_vec_items(const ConvK& k, float* smem, 
 
 // bf16x3 form of the 1x1 conv (p2l_pw.hip)
 int p2l_pw_launch(const p2lconv::ConvK& k, int pro, hipStream_t st);
+// the epilogue class (p2lconv::EPI_*) a launch of the fp16 x 2 full-tile kernel / of the fp16 x 2 Winograd kernel
+// runs with: p2l_pw_launch / p2l_wino_launch pick their instantiation with it
+int p2l_pw_epi_class(const p2lconv::ConvK& k, int pro);
+int p2l_wino_epi_class(const p2lconv::ConvK& k, int pro);
+int p2l_h2_epi_class(const p2lconv::ConvK& k, int pro, int taps);     // conv_h2_kernel<9 | 4, ..>
 
 // 3-channel image ends of the pipeline (p2l_thin.hip)
 size_t p2l_thin_weight_floats(int N_pad, int K_pad);

@@ -55,8 +55,10 @@ __device__ __forceinline__ int h2c(int c, int row) { return c ^ ((row >> 2) & 3)
 // one staged patch, two sets of accumulators, the epilogue once per phase; blockIdx.y = ph_y).  With a phase per block
 // (TAPS = 4) four blocks split and wrote the same patch: these launches are bound by staging and the global -> LDS
 // path, not by the matrix pipe.  Same products in the same order per output: bit-identical (P2L_FORM_NO_SP_PAIR).
-template <int TAPS, int BN, int A_ITERS, int PRO, bool SKIP = false>
+// EC: the epilogue compiled for the launch's class (p2l_conv_k.h EPI_*; unsplit TAPS 9 | 4 launches), 0 = the shared item
+template <int TAPS, int BN, int A_ITERS, int PRO, bool SKIP = false, int EC = EPI_GENERIC>
 __global__ __launch_bounds__(256, 2) void conv_h2_kernel(const ConvK k) {
+  static_assert(EC == EPI_GENERIC || TAPS == 9 || (TAPS == 4 && !SKIP), "compiled epilogues: direct 3x3 and sub-pixel input gradient");
   constexpr bool SUBPIX = (TAPS == 4 || TAPS == 8);
   constexpr int NP = (TAPS == 8) ? 2 : 1;            // output phases per block
   constexpr int NT = BN / 32;                        // accumulators per wave and phase
@@ -484,8 +486,8 @@ __global__ __launch_bounds__(256, 2) void conv_h2_kernel(const ConvK k) {
                            tile_in_image, 1, ph_y, p);
         }
       } else {
-        epilogue_vec<NT>(k, reinterpret_cast<f32x16 (&)[NT]>(acc[0]), smem, wave, lane, b0, y0, x0, n0, tile_in_image,
-                         sp_fwd ? 1 : 0, ph_y, ph_x);
+        epilogue_vec<NT, EC>(k, reinterpret_cast<f32x16 (&)[NT]>(acc[0]), smem, wave, lane, b0, y0, x0, n0,
+                             tile_in_image, sp_fwd ? 1 : 0, ph_y, ph_x);
       }
     }
   }
@@ -610,6 +612,12 @@ size_t p2l_h2_lds_bytes(const ConvK& k, int taps, int bn) {
   return (size_t)(main_floats + 2 * TB + 16) * sizeof(float);
 }
 
+// (unsplit launches of the direct 3x3 kernel and of the sub-pixel input gradient, no fused prologue)
+int p2l_h2_epi_class(const ConvK& k, int pro, int taps) {
+  if (k.splitk > 1) return EPI_GENERIC;
+  return epi_class_h2(k, pro, taps);
+}
+
 // k: the ConvK conv_launch_impl built for the direct / sub-pixel kernel (tile geometry, k.hp, sp_mode,
 // nchunks, splitk ...) with k.w = the fp16 x 2 image, k.w_tail, k.amax | k.amax_in set.  taps = 9 | 4.
 int p2l_h2_launch(const ConvK& k, int pro, int taps, int bn, bool small, hipStream_t st) {
@@ -620,9 +628,10 @@ int p2l_h2_launch(const ConvK& k, int pro, int taps, int bn, bool small, hipStre
     if ((TAPS == 4 || TAPS == 8) && k.sp_skip) P2L_H2K(TAPS, BNV, AIT, PROV, (TAPS == 4 || TAPS == 8)); \
     else P2L_H2K(TAPS, BNV, AIT, PROV, false);                                                \
   } while (0)
-#define P2L_H2K(TAPS, BNV, AIT, PROV, SKIPV)                                                  \
+#define P2L_H2K(TAPS, BNV, AIT, PROV, SKIPV) P2L_H2KE(TAPS, BNV, AIT, PROV, SKIPV, EPI_GENERIC)
+#define P2L_H2KE(TAPS, BNV, AIT, PROV, SKIPV, ECV)                                            \
   do {                                                                                        \
-    auto kfn = conv_h2_kernel<TAPS, BNV, AIT, PROV, SKIPV>;                                   \
+    auto kfn = conv_h2_kernel<TAPS, BNV, AIT, PROV, SKIPV, ECV>;                              \
     static std::atomic<bool> attr_set{false};                                                 \
     if (!attr_set) {                                                                          \
       (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -637,7 +646,16 @@ int p2l_h2_launch(const ConvK& k, int pro, int taps, int bn, bool small, hipStre
     else if (pro == P2L_PRO_AFFINE_RELU) P2L_H2L(TAPS, BNV, AIT, P2L_PRO_AFFINE_RELU);        \
     else P2L_H2L(TAPS, BNV, AIT, P2L_PRO_AFFINE);                                             \
   } while (0)
-  if (taps == 9) {
+  // the epilogue compiled for the launch's class where there is one (same bits; p2l_conv_k.h epi_item_ct)
+#define P2L_H2E(TAPS, ECV)                                                                    \
+  do {                                                                                        \
+    if (bn == 64) { if (small) P2L_H2KE(TAPS, 64, 3, P2L_PRO_NONE, false, ECV); else P2L_H2KE(TAPS, 64, 5, P2L_PRO_NONE, false, ECV); } \
+    else          { if (small) P2L_H2KE(TAPS, 32, 3, P2L_PRO_NONE, false, ECV); else P2L_H2KE(TAPS, 32, 5, P2L_PRO_NONE, false, ECV); } \
+  } while (0)
+  const int ec = p2l_h2_epi_class(k, pro, taps);
+  if (ec == EPI_ARB && taps == 9) P2L_H2E(9, EPI_ARB);
+  else if (ec == EPI_ARB && taps == 4) P2L_H2E(4, EPI_ARB);
+  else if (taps == 9) {
     if (bn == 64) { if (small) P2L_H2P(9, 64, 3); else P2L_H2P(9, 64, 5); }
     else          { if (small) P2L_H2P(9, 32, 3); else P2L_H2P(9, 32, 5); }
   } else if (taps == 8) {
@@ -647,8 +665,10 @@ int p2l_h2_launch(const ConvK& k, int pro, int taps, int bn, bool small, hipStre
     if (bn == 64) { if (small) P2L_H2P(4, 64, 3); else P2L_H2P(4, 64, 5); }
     else          { if (small) P2L_H2P(4, 32, 3); else P2L_H2P(4, 32, 5); }
   }
+#undef P2L_H2E
 #undef P2L_H2P
 #undef P2L_H2L
 #undef P2L_H2K
+#undef P2L_H2KE
   return p2l_check_launch();
 }

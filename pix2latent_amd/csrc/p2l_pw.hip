@@ -220,8 +220,10 @@ __device__ __forceinline__ void pw_store_split_h2(float* As, int row, int q4, in
 #ifndef P2L_PW_ABL
 #define P2L_PW_ABL 0
 #endif
-template <int PRO, bool SM = false>
-__global__ __launch_bounds__(256, SM ? 3 : 4) void pw_h2_kernel(const ConvK k) {   // (SM: per-item prologue operands, 130-160 VGPR)
+// EC: the epilogue compiled for the launch's class (p2l_conv_k.h EPI_*; full-tile form only), 0 = the shared item
+template <int PRO, bool SM = false, int EC = EPI_GENERIC>
+__global__ __launch_bounds__(256, SM ? 3 : 4) void pw_h2_kernel(const ConvK k) {
+  static_assert(!SM || EC == EPI_GENERIC, "the small-grid form keeps the shared item");   // (SM: per-item prologue operands, 130-160 VGPR)
   constexpr int KS = 32, VPP = KS / 4;
   constexpr int A_ITERS = 128 * VPP / 256;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -522,7 +524,7 @@ __global__ __launch_bounds__(256, SM ? 3 : 4) void pw_h2_kernel(const ConvK k) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] *= out_scale;  // (exact: a power of two)
     if (!(P2L_PW_ABL & 32) || acc[0][0] == 12345.678f)
-    epilogue_vec<2>(k, acc, smem, wave, lane, b0, y0, x0, n0, tile_in_image, 0, 0, 0);
+    epilogue_vec<2, EC>(k, acc, smem, wave, lane, b0, y0, x0, n0, tile_in_image, 0, 0, 0);
     return;
   }
   // small-grid form: registers 4g .. 4g+3 of a lane are quad Q = wave*8 + 2g + lhi (one image each)
@@ -615,6 +617,12 @@ int p2l_pw_pack_h2(const float* w_oihw, int O, int I, int N_pad, int K_pad, int 
   return p2l_check_launch();
 }
 
+// (the fp16 x 2 full-tile form: k.amax_in handed over, no small-grid slices)
+int p2l_pw_epi_class(const ConvK& k, int pro) {
+  if (k.amax_in == nullptr || k.amax != nullptr) return EPI_GENERIC;
+  return epi_class_pw(k, pro);
+}
+
 int p2l_pw_launch(const ConvK& k, int pro, hipStream_t st) {
   dim3 grid(k.n_mtiles * k.n_ntiles), block(256);
 #define P2L_PW(PRO)                                                                          \
@@ -627,15 +635,16 @@ int p2l_pw_launch(const ConvK& k, int pro, hipStream_t st) {
     }                                                                                        \
     hipLaunchKernelGGL((pw_bf3_kernel<PRO, 32>), grid, block, PwCfg<32>::LDS_BYTES, st, k);  \
   } while (0)
-#define P2L_PWH(PRO, SMV)                                                                    \
+#define P2L_PWH(PRO, SMV) P2L_PWHE(PRO, SMV, EPI_GENERIC)
+#define P2L_PWHE(PRO, SMV, ECV)                                                              \
   do {                                                                                       \
     static std::atomic<bool> attr_set{false};                                                \
     if (!attr_set) {                                                                         \
-      (void)hipFuncSetAttribute((const void*)pw_h2_kernel<PRO, SMV>,                         \
+      (void)hipFuncSetAttribute((const void*)pw_h2_kernel<PRO, SMV, ECV>,                    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
       attr_set = true;                                                                       \
     }                                                                                        \
-    hipLaunchKernelGGL((pw_h2_kernel<PRO, SMV>), gridh, block,                               \
+    hipLaunchKernelGGL((pw_h2_kernel<PRO, SMV, ECV>), gridh, block,                          \
                        PWH_LDS_BYTES + 128 + ((!SMV && PRO != P2L_PRO_NONE) ? (size_t)k.Cin * 8 : 0), st, k); \
   } while (0)
   if (k.amax_in != nullptr || k.amax != nullptr) {     // fp16 x 2 (conv_launch_impl decides)
@@ -648,12 +657,23 @@ int p2l_pw_launch(const ConvK& k, int pro, hipStream_t st) {
       else P2L_PWH(P2L_PRO_AFFINE, true);
       return p2l_check_launch();
     }
-    if (pro == P2L_PRO_NONE) P2L_PWH(P2L_PRO_NONE, false);
-    else if (pro == P2L_PRO_AFFINE_RELU) P2L_PWH(P2L_PRO_AFFINE_RELU, false);
-    else P2L_PWH(P2L_PRO_AFFINE, false);
+    // the epilogue compiled for the launch's class where there is one (same bits; p2l_conv_k.h epi_item_ct)
+    switch (p2l_pw_epi_class(k, pro)) {
+      case EPI_BIAS_PS:       P2L_PWHE(P2L_PRO_AFFINE_RELU, false, EPI_BIAS_PS); break;
+      case EPI_BIAS_RES_PS:   P2L_PWHE(P2L_PRO_AFFINE_RELU, false, EPI_BIAS_RES_PS); break;
+      case EPI_BIAS_RESUP_PS: P2L_PWHE(P2L_PRO_AFFINE_RELU, false, EPI_BIAS_RESUP_PS); break;
+      case EPI_ARB:           P2L_PWHE(P2L_PRO_NONE, false, EPI_ARB); break;
+      case EPI_ARB_SKIP:      P2L_PWHE(P2L_PRO_NONE, false, EPI_ARB_SKIP); break;
+      case EPI_ARB_SKIP_UP:   P2L_PWHE(P2L_PRO_NONE, false, EPI_ARB_SKIP_UP); break;
+      default:
+        if (pro == P2L_PRO_NONE) P2L_PWH(P2L_PRO_NONE, false);
+        else if (pro == P2L_PRO_AFFINE_RELU) P2L_PWH(P2L_PRO_AFFINE_RELU, false);
+        else P2L_PWH(P2L_PRO_AFFINE, false);
+    }
     return p2l_check_launch();
   }
 #undef P2L_PWH
+#undef P2L_PWHE
   if (pro == P2L_PRO_NONE) P2L_PW(P2L_PRO_NONE);
   else if (pro == P2L_PRO_AFFINE_RELU) P2L_PW(P2L_PRO_AFFINE_RELU);
   else P2L_PW(P2L_PRO_AFFINE);

@@ -370,9 +370,12 @@ constexpr TxTableH kTxH{};
 // size.  Re-tiling along M changes no output's summation order: same transform, same products, same
 // chunk order, same partial sums per 8x16-pixel tile, same maxima slots -- bit-identical to the 16x16 form
 // (tests/test_kernels_gpu.py).  A step of the multiply phase is fragment (fi, m) = (s / MT, s % MT).
-template <int PRO, int ABL = 0, bool H2 = false, int MT = 2>
+// EC: the epilogue compiled for the launch's class (p2l_conv_k.h EPI_*; never a split-K launch), 0 = the shared item
+template <int PRO, int ABL = 0, bool H2 = false, int MT = 2, int EC = EPI_GENERIC>
 __global__ __launch_bounds__(256 * MT, 1) void wino16s_conv_kernel(const ConvK k) {
   static_assert(MT == 2 || (MT == 1 && H2), "the 4-wave block exists in the fp16 x 2 arithmetic only");
+  static_assert(EC == EPI_GENERIC || (H2 && ABL == 0), "compiled epilogues: the fp16 x 2 product kernel");
+  constexpr EpiDesc ED = epi_desc(EC);
   constexpr int THREADS = 256 * MT, TILES = 32 * MT, NW = 4 * MT, NF = 4 / MT;
   constexpr int RAW_ROWS = (8 * MT + 2) * 18, RAW_FLOATS = RAW_ROWS * WN_RAW_PITCH, V_FLOATS = 16 * TILES * 16;
   constexpr int FV = TILES * 16;                         // floats of one frequency of V
@@ -869,7 +872,8 @@ __global__ __launch_bounds__(256 * MT, 1) void wino16s_conv_kernel(const ConvK k
   const int e_t = tid >> 3, e_c4 = tid & 7;             // item: (tile, 4 channels)
   const int ety = e_t >> 3, etx = e_t & 7;
   float* red = raw;                                      // [2 kinds][NW waves][32]
-  const bool split = k.splitk > 1;
+  const bool split = EC == EPI_GENERIC && k.splitk > 1;
+  const bool with_arb = EC == EPI_GENERIC ? k.arb_x != nullptr : ED.arb != 0;
   const float alpha = (split ? 1.f : k.alpha) * out_scale;   // (the finish kernel scales the sum)
   float blk_amax = 0.f, blk_amaxp = 0.f;
 #pragma unroll
@@ -923,11 +927,11 @@ __global__ __launch_bounds__(256 * MT, 1) void wino16s_conv_kernel(const ConvK k
       } else if (ABL & 256) {                            // (lab) no stores at all
         if (v[0].x == 123.456f) k.y[0] = v[1].x + v[2].x + v[3].x;
       } else {
-        epi_item(k, v, b, y0 + 2 * ety, x0 + 2 * etx, nb + e_c4 * 4, 0, 0, 0, S);
+        epi_item_of<EC>(k, v, b, y0 + 2 * ety, x0 + 2 * etx, nb + e_c4 * 4, 0, 0, 0, S);
       }
     }
     if (j == 0) { P2L_TR(4, 62); }
-    if (k.arb_x != nullptr && !split) {
+    if (with_arb && !split) {
       f32x4 sgx = S.sgx, sg = S.sg;
 #pragma unroll
       for (int o = 8; o < 64; o <<= 1) {
@@ -960,7 +964,7 @@ __global__ __launch_bounds__(256 * MT, 1) void wino16s_conv_kernel(const ConvK k
 #undef P2L_TR
   // this block's partial maxima of what it stored (one per wave), for the launch that reads the tensor
   // next (P2LAmax)
-  if ((k.amax_out != nullptr || k.amax_outp != nullptr) && !split) {
+  if (EC == EPI_GENERIC ? ((k.amax_out != nullptr || k.amax_outp != nullptr) && !split) : (ED.amax != 0 || ED.pool == 2)) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       blk_amax = fmaxf(blk_amax, __shfl_xor(blk_amax, o, 64));
@@ -971,8 +975,8 @@ __global__ __launch_bounds__(256 * MT, 1) void wino16s_conv_kernel(const ConvK k
       // which one ran): an 8x16 block is the upper / lower half (by & 1) of its 16x16 tile
       const size_t t16 = MT == 2 ? (size_t)tile_in_image : (size_t)(by >> 1) * k.tiles_x + bx;
       const size_t slot = (size_t)b * k.amax_out_n + (t16 * k.n_ntiles + (n0 >> 6)) * 8 + (MT == 2 ? 0 : (by & 1) * 4) + wave;
-      if (k.amax_out != nullptr) k.amax_out[slot] = blk_amax;
-      if (k.amax_outp != nullptr) k.amax_outp[slot] = blk_amaxp;
+      if (EC == EPI_GENERIC ? k.amax_out != nullptr : ED.amax != 0) k.amax_out[slot] = blk_amax;
+      if (EC == EPI_GENERIC ? k.amax_outp != nullptr : ED.pool == 2) k.amax_outp[slot] = blk_amaxp;
     }
   }
 }
@@ -1166,6 +1170,13 @@ static void* g_lab_trace = nullptr;
 extern "C" int p2l_lab_set(int abl, void* trace) { g_lab_abl = abl; g_lab_trace = trace; return P2L_OK; }
 #endif
 
+// (the fp16 x 2 product kernel, both block shapes: whole 16x16 tiles, k.amax set, no K slices)
+int p2l_wino_epi_class(const ConvK& k, int pro) {
+  if (k.H % 16 != 0 || k.W % 16 != 0 || (k.form & P2L_FORM_WINO_8X16) || k.amax == nullptr || k.splitk > 1)
+    return EPI_GENERIC;
+  return epi_class_wino(k, pro);
+}
+
 int p2l_wino_launch(const ConvK& k_in, int pro, hipStream_t st) {
   ConvK k = k_in;
   if (k.H % 16 == 0 && k.W % 16 == 0 && !(k.form & P2L_FORM_WINO_8X16)) {
@@ -1237,22 +1248,37 @@ int p2l_wino_launch(const ConvK& k_in, int pro, hipStream_t st) {
     }                                                                                        \
     hipLaunchKernelGGL(wino16s_conv_kernel<PRO>, grid, block, W16_LDS_BYTES, st, k);         \
   } while (0)
-#define P2L_W16H(PRO, MTV, LDSB)                                                             \
+#define P2L_W16H(PRO, MTV, LDSB) P2L_W16HE(PRO, MTV, LDSB, EPI_GENERIC)
+#define P2L_W16HE(PRO, MTV, LDSB, ECV)                                                       \
   do {                                                                                       \
     static std::atomic<bool> attr_set{false};                                                \
     if (!attr_set) {                                                                         \
-      (void)hipFuncSetAttribute((const void*)wino16s_conv_kernel<PRO, 0, true, MTV>,         \
+      (void)hipFuncSetAttribute((const void*)wino16s_conv_kernel<PRO, 0, true, MTV, ECV>,    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
       attr_set = true;                                                                       \
     }                                                                                        \
     if (k.amax_in == nullptr)                                                                \
       hipLaunchKernelGGL(wino_amax_kernel<PRO>, dim3(64, k.B), dim3(256), 0, st, k);         \
-    hipLaunchKernelGGL((wino16s_conv_kernel<PRO, 0, true, MTV>), grid, block, LDSB, st, k);  \
+    hipLaunchKernelGGL((wino16s_conv_kernel<PRO, 0, true, MTV, ECV>), grid, block, LDSB, st, k); \
   } while (0)
+  // the epilogue compiled for the launch's class where there is one (same bits; p2l_conv_k.h epi_item_ct)
+#define P2L_W16HC(MTV, LDSB)                                                                                \
+  switch (ec) {                                                                                             \
+    case EPI_BIAS_PS:        P2L_W16HE(P2L_PRO_AFFINE_RELU, MTV, LDSB, EPI_BIAS_PS); break;                 \
+    case EPI_BIAS_RELU:      P2L_W16HE(P2L_PRO_NONE, MTV, LDSB, EPI_BIAS_RELU); break;                      \
+    case EPI_BIAS_RELU_POOL: P2L_W16HE(P2L_PRO_NONE, MTV, LDSB, EPI_BIAS_RELU_POOL); break;                 \
+    case EPI_MASK:           P2L_W16HE(P2L_PRO_NONE, MTV, LDSB, EPI_MASK); break;                           \
+    case EPI_ARB:            P2L_W16HE(P2L_PRO_NONE, MTV, LDSB, EPI_ARB); break;                            \
+    default:                                                                                                \
+      if (pro == P2L_PRO_NONE) P2L_W16H(P2L_PRO_NONE, MTV, LDSB);                                           \
+      else if (pro == P2L_PRO_AFFINE_RELU) P2L_W16H(P2L_PRO_AFFINE_RELU, MTV, LDSB);                        \
+      else P2L_W16H(P2L_PRO_AFFINE, MTV, LDSB);                                                             \
+  }
     if (k.amax != nullptr) {                           // fp16 x 2 arithmetic (conv_launch_impl decides)
       // Block shape from the GRID (round 5): while the 16x16 blocks of the launch leave half the CUs
       // without one, 8x16-pixel blocks of 4 waves -- twice as many, one wave per SIMD, about half as long.
       // Bit-identical results and maxima slots (MT in the kernel), so the batch may decide.
+      const int ec = p2l_wino_epi_class(k, pro);
       const long blocks16 = (long)k.n_mtiles * k.n_ntiles * k.splitk;
       const bool half = (k.form & P2L_FORM_WINO_H2_8X16) ||
                         (!(k.form & P2L_FORM_WINO_H2_16X16) && blocks16 <= 128);
@@ -1261,16 +1287,14 @@ int p2l_wino_launch(const ConvK& k_in, int pro, hipStream_t st) {
         k.n_mtiles = k.B * k.tiles_x * k.tiles_y;
         grid = dim3(k.n_mtiles * k.n_ntiles, k.splitk);
         block = dim3(256);
-        if (pro == P2L_PRO_NONE) P2L_W16H(P2L_PRO_NONE, 1, W8_LDS_BYTES);
-        else if (pro == P2L_PRO_AFFINE_RELU) P2L_W16H(P2L_PRO_AFFINE_RELU, 1, W8_LDS_BYTES);
-        else P2L_W16H(P2L_PRO_AFFINE, 1, W8_LDS_BYTES);
+        P2L_W16HC(1, W8_LDS_BYTES)
         return p2l_check_launch();
       }
-      if (pro == P2L_PRO_NONE) P2L_W16H(P2L_PRO_NONE, 2, W16_LDS_BYTES);
-      else if (pro == P2L_PRO_AFFINE_RELU) P2L_W16H(P2L_PRO_AFFINE_RELU, 2, W16_LDS_BYTES);
-      else P2L_W16H(P2L_PRO_AFFINE, 2, W16_LDS_BYTES);
+      P2L_W16HC(2, W16_LDS_BYTES)
       return p2l_check_launch();
     }
+#undef P2L_W16HC
+#undef P2L_W16HE
 #undef P2L_W16H
     if (pro == P2L_PRO_NONE) P2L_W16S(P2L_PRO_NONE);
     else if (pro == P2L_PRO_AFFINE_RELU) P2L_W16S(P2L_PRO_AFFINE_RELU);
