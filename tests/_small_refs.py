@@ -5,7 +5,7 @@ float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks
 independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py,
 tests/test_glue_kernels_gpu.py, tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
 restatements, host packers and the case tables) and tests/test_wino_kernels_gpu.py (the Winograd 3x3 routes: the
-same) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+same) and tests/test_direct_kernels_gpu.py (the direct 3x3 routes, ups 0 / 1: the same) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
@@ -679,10 +679,11 @@ def combine_slices(parts):
     return (z[0] + z[1]) + (z[2] + z[3])
 
 
-def acc_fp32(a, w, splitk=1):
-    """route A (conv_mfma_kernel<1, ..>, exact fp32 products): one chain per output over k, per K slice"""
+def acc_fp32(a, w, splitk=1, kc=None):
+    """route A (conv_mfma_kernel<1, ..>, exact fp32 products): one chain per output over k, per K slice; kc: the
+    columns of one chunk (default: the 1x1 kernel's 32 / 16 channels; the 3x3 kernels' im2col: 9 x 16)"""
     K = a.shape[-1]
-    kc = 32 if K % 32 == 0 else 16
+    kc = kc or (32 if K % 32 == 0 else 16)
     wt = w.t().contiguous()
     parts = []
     for lo, hi in splitk_slices(K, kc, splitk):
@@ -701,17 +702,22 @@ def split3(x):
     return h, m, (r1 - m).bfloat16().float()
 
 
-def acc_bf3(a, w):
+def acc_bf3(a, w, splitk=1, kc=None):
     """route B (pw_bf3_kernel): per 16-channel step the six kept cross terms (a piece, w piece) in the kernel's
-    order (3,1) (1,3) (2,2) (2,1) (1,2) (1,1), each an fp32 sum of 16 exact products onto the accumulator"""
+    order (3,1) (1,3) (2,2) (2,1) (1,2) (1,1), each an fp32 sum of 16 exact products onto the accumulator; in K
+    slices of whole chunks of kc columns where the launch is sliced (the direct 3x3 kernel: kc = 9 x 16)"""
     a1, a2, a3 = split3(a)
     w1, w2, w3 = split3(w)
-    acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
-    for c in range(0, a.shape[-1], 16):
-        sl = slice(c, c + 16)
-        for p, q in ((a3, w1), (a1, w3), (a2, w2), (a2, w1), (a1, w2), (a1, w1)):
-            acc = acc + p[..., sl] @ q[:, sl].t()
-    return acc
+    K = a.shape[-1]
+    parts = []
+    for lo, hi in splitk_slices(K, kc or K, splitk):
+        acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
+        for c in range(lo, hi, 16):
+            sl = slice(c, c + 16)
+            for p, q in ((a3, w1), (a1, w3), (a2, w2), (a2, w1), (a1, w2), (a1, w1)):
+                acc = acc + p[..., sl] @ q[:, sl].t()
+        parts.append(acc)
+    return combine_slices(parts)
 
 
 def h2_scales(mx):
@@ -727,16 +733,16 @@ def split2(x):
     return h, (x - h).half().float()
 
 
-def acc_h2(a, w, amax, wmax, splitk=1):
+def acc_h2(a, w, amax, wmax, splitk=1, kc=32):
     """routes C and D (pw_h2_kernel): operands scaled by the power of two of h2_scales (activations per image from
     amax [B], weights from wmax), two fp16 pieces each, per 16-channel step the three kept terms (m h) (h m) (h h);
-    32-channel stages in K slices; un-scaled exactly"""
+    32-channel stages (kc; the direct 3x3 kernels: chunks of 9 x 16 im2col columns) in K slices; un-scaled exactly"""
     xs, xinv = h2_scales(amax)
     ws, winv = h2_scales(wmax.reshape(1))
     ah, am = split2(a * xs.view(-1, 1, 1, 1))
     wh, wm = split2(w * ws)
     parts = []
-    for lo, hi in splitk_slices(a.shape[-1], 32, splitk):
+    for lo, hi in splitk_slices(a.shape[-1], kc, splitk):
         acc = torch.zeros(a.shape[:-1] + (w.shape[0],), dtype=a.dtype)
         for c in range(lo, hi, 16):
             sl = slice(c, c + 16)
@@ -1224,18 +1230,23 @@ def wino_h2_floor(aabs, w, amax, wmax):
     return wino_out(f, True)
 
 
-def conv3x3(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, acc=None, floor=None, **epi):
-    """the stride-1 3x3 conv launch of include/p2l.h in the dtype of x: a = prologue(x); zero padding AFTER the
-    prologue; v = alpha sum a w; then conv_epilogue(**epi), the epilogue conv1x1 ends in.  w [N, K, 3, 3].  `acc`
-    replaces the conv (a restatement's result), `floor` (wino_h2_floor) is added to both denominators.
-    -> conv1x1's dict with den / denp on den_w (wino_den) and den_d / denp_d on the direct sum_taps,k |a| |w|"""
+def conv3x3(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, acc=None, floor=None, ups=False, den_w=True, **epi):
+    """the stride-1 3x3 conv launch of include/p2l.h in the dtype of x: a = prologue(x); ups (P2LConv.ups = 1): x
+    is the low-resolution [B, H/2, W/2, K] tensor, the prologue runs on it, then nearest x 2 (`up2`); zero padding
+    AFTER the prologue (and the upsample); v = alpha sum a w; then conv_epilogue(**epi), the epilogue conv1x1 ends
+    in -- res_ups and the pool as before, on the H x W output.  w [N, K, 3, 3].  `acc` replaces the conv (a
+    restatement's result), `floor` (wino_h2_floor / direct_h2_floor) is added to both denominators.
+    -> conv1x1's dict with den / denp on den_w (wino_den) and den_d / denp_d on the direct sum_taps,k |a| |w|;
+    den_w = False (the direct routes): den / denp are den_d / denp_d"""
     dt = x.dtype
     w = w.to(dt)
     a, aabs = pw_prologue(x, pro, s, t)
+    if ups:
+        a, aabs = up2(a), up2(aabs)
     nchw = lambda v: v.permute(0, 3, 1, 2)
     v = F.conv2d(nchw(a), w, padding=1).permute(0, 2, 3, 1) if acc is None else acc.to(dt)
     den_d = F.conv2d(nchw(aabs), w.abs(), padding=1).permute(0, 2, 3, 1)
-    den_w = wino_den(aabs, w)
+    den_w = wino_den(aabs, w) if den_w else den_d
     if floor is not None:
         den_w, den_d = den_w + floor.to(dt), den_d + floor.to(dt)
     out = conv_epilogue(v * alpha, den_w * abs(alpha), **epi)
@@ -1244,14 +1255,17 @@ def conv3x3(x, w, pro=PRO_NONE, s=None, t=None, alpha=1.0, acc=None, floor=None,
     return out
 
 
-def conv3x3_arb(dy, w, x, s, t, alpha=1.0, acc=None, floor=None, **kw):
-    """p2l_conv_dgrad_arb on a 3x3 launch: da = alpha conv3x3(dy, w), then arb_epilogue -> conv1x1_arb's dict on
-    den_w, and den_dx_d on the direct denominator"""
+def conv3x3_arb(dy, w, x, s, t, alpha=1.0, acc=None, floor=None, ups=False, den_w=True, **kw):
+    """p2l_conv_dgrad_arb on a 3x3 launch: da = alpha conv3x3(dy, w) (ups: of the nearest x 2 of the low-resolution
+    dy, as in conv3x3), then arb_epilogue -> conv1x1_arb's dict on den_w, and den_dx_d on the direct denominator
+    (den_w = False, the direct routes: both are the direct one)"""
     dtp = dy.dtype
     w = w.to(dtp)
+    dy = up2(dy) if ups else dy
     nchw = lambda v: v.permute(0, 3, 1, 2)
     da = (F.conv2d(nchw(dy), w, padding=1).permute(0, 2, 3, 1) if acc is None else acc.to(dtp)) * alpha
-    den_w, den_d = wino_den(dy.abs(), w), F.conv2d(nchw(dy.abs()), w.abs(), padding=1).permute(0, 2, 3, 1)
+    den_d = F.conv2d(nchw(dy.abs()), w.abs(), padding=1).permute(0, 2, 3, 1)
+    den_w = wino_den(dy.abs(), w) if den_w else den_d
     if floor is not None:
         den_w, den_d = den_w + floor.to(dtp), den_d + floor.to(dtp)
     out = arb_epilogue(da, den_w * abs(alpha), x, s, t, **kw)
@@ -1404,18 +1418,40 @@ def wino_onehot(c, tap, seed=0):
     return dict(x=x, w=w)
 
 
-def direct_h2_k(c, slices):
-    """k of the direct fp16 x 2 3x3 kernel in `slices` K slices, counted like pw_k's routes C / D over the nine taps;
-    the case's epilogue: alpha and bias"""
-    return 3 * 9 * (c['Cin'] // slices) + (slices - 1) + 13 + 1 + c['bias']
+def direct_k(c, route=None, pooled=False):
+    """the bar's k of a stride-1 direct 3x3 case (ups 0 / 1), counted like pw_k and wino_k's route-F branch from the
+    arithmetic of csrc/p2l_conv.hip, p2l_h2.hip and p2l_h2r.hip.  A K slice is whole 16-channel chunks, a chunk nine
+    taps of 16 channels: `deep` = the 9 x channels im2col columns of the deepest slice (splitk_slices on chunks of
+    144 columns).  Per column onto the accumulator -- F (fp32 MFMA): a product and an addition (2); B (bf16 x 3):
+    the six cross terms of exact products (6); H, R (fp16 x 2): three (3).  Then the slices, summed in the finish
+    kernels' order (slices - 1); B: the pieces to 2^-24 relative of either operand (2) and the dropped terms <= 2^-23
+    (2); H, R: the pieces to 2^-22 of either operand (8), the dropped term (4) and the absolute floor that
+    `direct_h2_floor` puts into the denominator (1).  The nearest upsample of ups = 1 copies values: no term.  Then
+    pw_k's prologue and epilogue terms: the prologue's fma (2); alpha, oscale, bias, noise (a product and a sum),
+    residual one each; tanh 2; the leaky ReLU's factor sqrt 2 on everything before it and its own rounding; the
+    pool's sum two additions deep.  R counts as H: the same order on the same pieces (the header of p2l_h2r.hip)"""
+    route = route or c['route']
+    sl = splitk_slices(9 * c['Cin'], 144, c['splitk'])
+    deep = max(hi - lo for lo, hi in sl)
+    k = {'F': 2, 'B': 6, 'H': 3, 'R': 3}[route] * deep + (len(sl) - 1) + {'F': 0, 'B': 4, 'H': 13, 'R': 13}[route]
+    k += (2 if c['pro'] != PRO_NONE else 0) + 1 + c['oscale'] + c['bias'] + 2 * c['noise'] + (c['res'] is not None)
+    if c['act'] == ACT_TANH:
+        k += 2
+    if c['act'] == ACT_LRELU_SQRT2:
+        k = 1.5 * k + 1
+    return k + 2 if pooled and c['pool'] == POOL_SUM else k
 
 
-def direct_h2_floor(x, w):
-    """h2_floor over the nine taps (the direct kernel splits a and w themselves), fp64 [B, H, W, N]"""
-    xa, wa = x.double().abs(), w.double().abs()
+def direct_h2_floor(aabs, w, amax=None, wmax=None, ups=False):
+    """h2_floor over the nine taps (the direct kernel splits a and w themselves), fp64 [B, H, W, N]: aabs the
+    prologue's absolute values (no prologue: |x|) at the resolution of x, upsampled here under ups = 1; amax [B] the
+    maxima the kernel scales by (pw_amax; default: those of aabs), wmax max |w|"""
+    xa, wa = aabs.double(), w.double().abs()
+    amax = xa.amax(dim=(1, 2, 3)) if amax is None else amax.double()
+    wmax = float(wa.max()) if wmax is None else float(wmax)
+    xa = up2(xa) if ups else xa
     near = F.conv2d(xa.permute(0, 3, 1, 2), torch.ones(1, xa.shape[-1], 3, 3, dtype=torch.float64), padding=1)
-    return 2.0 ** -13 * (xa.amax(dim=(1, 2, 3)).view(-1, 1, 1, 1) * wa.sum(dim=(1, 2, 3)) +
-                         float(wa.max()) * near.permute(0, 2, 3, 1))
+    return 2.0 ** -13 * (amax.view(-1, 1, 1, 1) * wa.sum(dim=(1, 2, 3)) + wmax * near.permute(0, 2, 3, 1))
 
 
 def producer_amax(y, next_s=None, next_t=None):
@@ -1466,6 +1502,276 @@ def wino_arb_refs(c, i):
                       floor=floor, **kw)
     r32 = conv3x3_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], acc=wino_acc32(c, i), **kw)
     r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], c['route'] == 'HS')
+    return r64, r32
+
+
+# ---- direct 3x3 convs, stride 1, ups 0 / 1 (tests/test_direct_kernels_gpu.py) ---------------------------------------
+# Routes of a taps = 9 launch that the Winograd kernels do not take: F conv_mfma_kernel<9, .., BF3 = false>
+# (P2L_WFMT_F32), B the same kernel in bf16 x 3 (wfmt 'bf3': P2L_WFMT_BF16X3; 'bf3w': P2L_WFMT_BF16X3W kept on it with
+# P2L_FORM_NO_WINO | P2L_FORM_WINO_BF3; ups = 1 always), H conv_h2_kernel<9, ..> (fp16 x 2, chunked), R conv_h2r_kernel
+# (64 -> 64, whole 8x16 tiles; seq: P2L_FORM_H2R_SEQ_EPI, the shared epilogue item).  H, W are those of the OUTPUT (ups
+# = 1: x is [B, H/2, W/2, Cin]).  A weight is the [N, K, 3, 3] correlation kernel the launch applies.
+WFMT_BF16X3 = 1
+FORM_NO_WINO, FORM_NO_H2R, FORM_H2R_SEQ_EPI = 1, 256, 512
+
+
+def direct_tile(H, W):
+    """(TW, TH, TB) of choose_tile (csrc/p2l_conv.hip): 128 pixels, TW = min(16, npow2(W)), TH up to npow2(H), the
+    rest images"""
+    TW = min(npow2(W), 16)
+    TH = min(128 // TW, npow2(H))
+    return TW, TH, 128 // (TW * TH)
+
+
+def direct_cols(a):
+    """im2col of the zero-padded a [B, H, W, K] with the K axis in the order all three kernels walk it (read off their
+    loops: `for c in chunks` outside, the unrolled `tap = u / NT` inside, 16 channels per MFMA group; tap = 3 dy + dx
+    reads pixel (y + dy - 1, x + dx - 1)): 16-channel chunk, tap, channel -> [B, H, W, 9 K]"""
+    B, H, W, K = a.shape
+    ap = F.pad(a, (0, 0, 1, 1, 1, 1))
+    taps = torch.stack([ap[:, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)], dim=3)    # [B, H, W, 9, K]
+    return taps.reshape(B, H, W, 9, K // 16, 16).permute(0, 1, 2, 4, 3, 5).reshape(B, H, W, 9 * K)
+
+
+def direct_wmat(w):
+    """[N, K, 3, 3] -> [N, 9 K] in direct_cols' order"""
+    N, K = w.shape[:2]
+    return w.reshape(N, K // 16, 16, 9).permute(0, 1, 3, 2).reshape(N, 9 * K)
+
+
+def direct_acc32(c, i, route=None):
+    """the fp32 restatement of a route's accumulator in front of alpha and the epilogue, [B, H, W, N]: the prologue
+    (on the low-resolution x under ups = 1, then up2), zero padding, and acc_fp32 / acc_bf3 / acc_h2 on the im2col in
+    the kernels' order with chunks of 9 x 16 columns.  R shares H's restatement and never slices"""
+    route = route or c['route']
+    a, _ = pw_prologue(i['x'], c['pro'], i.get('s'), i.get('t'))
+    a = up2(a) if c['ups'] else a
+    cols, wm = direct_cols(a), direct_wmat(i['w'])
+    if route == 'F':
+        return acc_fp32(cols, wm, c['splitk'], 144)
+    if route == 'B':
+        return acc_bf3(cols, wm, c['splitk'], 144)
+    return acc_h2(cols, wm, pw_amax(c, i)[1], i['w'].abs().max(), c['splitk'] if route == 'H' else 1, 144)
+
+
+def _dc(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, pro=PRO_NONE, pro_b=1, alpha=1.0, bias=False,
+             res=None, mask=False, act=ACT_NONE, pool=POOL_NONE, want_y=True, oscale=False, noise=False,
+             n_store=Cout, splitk=1, amax=None, ups=0, wfmt='bf3', seq=False, finish='v4', relu_like=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def direct_id(c):
+    d = _dc(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+def direct_form(c, route=None):
+    """-> (P2LConv.wfmt, P2LConv.form) of a case on `route`"""
+    route = route or c['route']
+    if route == 'F':
+        return 0, 0
+    if route == 'B':
+        if c['wfmt'] == 'bf3':
+            return WFMT_BF16X3, 0
+        return WFMT_BF16X3W, 0 if c['ups'] else FORM_NO_WINO | FORM_WINO_BF3
+    if route == 'H':
+        return WFMT_BF16X3W, FORM_NO_WINO | FORM_NO_H2R
+    return WFMT_BF16X3W, FORM_H2R_SEQ_EPI if c['seq'] else 0
+
+
+# the smallest shapes at which each form of choose_tile / choose_bn / direct_split exists
+DIRECT_SHAPES = {
+    '4x4': ((4, 4), 5, 32, 64),            # eight images per tile, the last tile with three empty slots
+    '8x8': ((8, 8), 3, 48, 64),            # two images per tile
+    '32x4': ((32, 4), 2, 32, 96),          # one image per tile on the A_ITERS = 5 form; BN = 32 by the remainder
+    '8x16': ((8, 16), 1, 32, 128),         # the `small` form, one tile; BN = 64 on a small grid
+    '16x16': ((16, 16), 2, 16, 64),        # ... two tiles
+    '12x20': ((12, 20), 2, 32, 64),        # partial tiles in both directions
+    '24x16': ((24, 16), 1, 16, 64),        # three whole tile rows
+    '6x6': ((6, 6), 3, 32, 64),            # two images per tile, both partial
+    '16x32': ((16, 32), 3, 64, 64),        # route R: four tiles per image, a block's range changes image
+    '64x64': ((64, 64), 10, 16, 64),       # choose_bn's grid rule: n64 = 320 -> BN = 32 with Cout % 64 == 0
+    'k8': ((8, 8), 3, 256, 64),            # p2l_conv_suggest_splitk: 8 slices
+    'k4': ((16, 16), 2, 128, 64),          # ... 4
+    'k4s': ((4, 4), 5, 128, 128),          # ... 4, eight images per tile
+    'k3': ((8, 8), 3, 128, 64),            # 8 chunks, a request of 3: slices of 3 + 3 + 2
+}
+
+
+def _dsh(route, name, **kw):
+    HW, B, Cin, Cout = DIRECT_SHAPES[name]
+    return _dc(route, HW, B, Cin, Cout, **kw)
+
+
+def _direct_fb(r, w):
+    """the cases routes F and B share (B: `w` alternates its two weight formats)"""
+    w = w if r == 'B' else 'bf3'
+    return [
+        _dsh(r, '4x4', **EPI[0]), _dsh(r, '8x8', wfmt=w, **EPI[1]), _dsh(r, '32x4', **EPI[2]),
+        _dsh(r, '16x16', wfmt=w, **EPI[3]), _dsh(r, '8x16', **EPI[4]), _dsh(r, '12x20', wfmt=w, n_store=36, **EPI[5]),
+        _dsh(r, '24x16', **EPI[6]), _dsh(r, '6x6', wfmt=w, bias=True, pro=PRO_AFFINE_RELU, pro_b=0),
+        _dsh(r, '64x64', act=ACT_RELU),
+        # ups = 1: nearest x 2 inside the staging, the prologue on the low-resolution tensor
+        _dsh(r, '8x8', ups=1, wfmt='bf3w', **EPI[0]), _dsh(r, '16x16', ups=1, wfmt='bf3w', **EPI[2]),
+        _dsh(r, '16x32', ups=1, wfmt='bf3w', **EPI[1]),
+        # K slices through conv_splitk_finish_v4, and one through the scalar conv_splitk_finish
+        _dsh(r, 'k8', splitk=8, wfmt=w, **EPI[0]), _dsh(r, 'k4', splitk=4, **EPI[3]),
+        _dsh(r, 'k4s', splitk=4, wfmt=w, **EPI[2]), _dsh(r, 'k3', splitk=3, **EPI[6]),
+        _dsh(r, 'k3', splitk=4, ups=1, wfmt='bf3w', **EPI[4]),
+        _dsh(r, 'k8', splitk=8, finish='scalar', wfmt=w, **EPI[0]),
+    ]
+
+
+DIRECT_FWD_CASES = _direct_fb('F', 'bf3') + _direct_fb('B', 'bf3w') + [
+    # H: maxima from the pass in front (amax None), handed over (true / raw under a prologue), in_applied
+    _dsh('H', '4x4', **EPI[0]), _dsh('H', '8x8', amax='raw', **EPI[1]), _dsh('H', '32x4', amax='applied', **EPI[2]),
+    _dsh('H', '16x16', amax='true', **EPI[3]), _dsh('H', '8x16', **EPI[4]),
+    _dsh('H', '12x20', amax='true', n_store=36, **EPI[5]), _dsh('H', '24x16', **EPI[6]),
+    _dsh('H', '6x6', bias=True, pro=PRO_AFFINE_RELU, pro_b=0, amax='raw'),
+    _dsh('H', '16x32', act=ACT_TANH),                                         # (its all-zero image: exactly 0)
+    _dsh('H', '64x64', act=ACT_RELU, amax='true'),
+    _dsh('H', 'k8', splitk=8, **EPI[0]), _dsh('H', 'k4', splitk=4, amax='true', **EPI[3]),
+    _dsh('H', 'k4s', splitk=4, amax='applied', **EPI[2]), _dsh('H', 'k3', splitk=3, **EPI[6]),
+    _dsh('H', 'k8', splitk=8, finish='scalar', amax='raw', **EPI[1]),
+    # R: EPI 1 (plain), 2 (mask), 3 (max pool) by the epilogue; everything else on the shared item (seq)
+    _dsh('R', '16x32', bias=True, act=ACT_RELU), _dsh('R', '16x32', amax='applied', **EPI[2]),
+    _dsh('R', '16x32', amax='true', **EPI[3]), _dsh('R', '16x32', seq=True, **EPI[0]),
+    _dsh('R', '16x32', seq=True, amax='raw', **EPI[1]), _dsh('R', '16x32', seq=True, **EPI[4]),
+    _dsh('R', '16x32', seq=True, n_store=36, **EPI[5]), _dsh('R', '16x32', seq=True, amax='true', **EPI[6]),
+]
+
+
+def direct_inputs(g, c):
+    """wino_inputs' operands for a direct case (H, R: the fp16 x 2 inputs -- the quad 2^-20 below the maximum, the
+    all-zero image of a batch of three, the heavy channel under a prologue; PRO_AFFINE: |t| of 2 .. 5 units of the
+    image) with the images of one launch scaled very differently on top of their magnitudes: the first x 1e-6, the
+    last x 3e4 -- x, a per-image t, the residual and the noise alike (a prologue shared by the batch keeps pw_inputs'
+    magnitudes: one t has to fit every image).  ups = 1: x is every other pixel of the draw, [B, H/2, W/2, Cin]"""
+    i = wino_inputs(g, dict(c, route='H' if c['route'] in 'HR' else 'W8'))
+    B = c['B']
+    if c['ups']:
+        i['x'] = i['x'][:, ::2, ::2].contiguous()
+    if B >= 2 and (c['pro'] == PRO_NONE or c['pro_b']):
+        f = torch.ones(B)
+        f[0], f[B - 1] = 1e-6, 3e4
+        i['x'] = i['x'] * f.view(B, 1, 1, 1)
+        if 't' in i:
+            i['t'] = i['t'] * f.view(B, 1)
+        if 'res' in i:
+            i['res'] = i['res'] * f.view(B, 1, 1, 1)
+        if 'noise' in i:
+            i['noise'] = i['noise'] * f.view(B, 1, 1)
+    return i
+
+
+def direct_refs(c, i, route=None, restate=True):
+    """-> conv3x3's dict in fp64 on den_d (H, R: plus direct_h2_floor) and the route's fp32 restatement's (restate =
+    False: None)"""
+    route = route or c['route']
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    floor = None
+    if route in 'HR':
+        _, aabs = pw_prologue(i64['x'], c['pro'], i64.get('s'), i64.get('t'))
+        floor = direct_h2_floor(aabs, i['w'], pw_amax(c, i)[1], i['w'].abs().max(), bool(c['ups']))
+    ups = bool(c['ups'])
+    r64 = conv3x3(i64['x'], i64['w'], floor=floor, ups=ups, den_w=False, **pw_kwargs(c, i, torch.float64))
+    if not restate:
+        return r64, None
+    r32 = conv3x3(i['x'], i['w'], acc=direct_acc32(c, i, route), ups=ups, den_w=False,
+                  **pw_kwargs(c, i, torch.float32))
+    return r64, r32
+
+
+def direct_spots(H, W, B):
+    """(image, y, x) of the one-hot pixels: the corners, the edges, both sides of every seam of choose_tile's tiles,
+    the last row / column (of a partial tile where the grid has one), the interior, and the first pixel and the last
+    of the second image (in a multi-image tile: the neighbour of image 0's halo)"""
+    TW, TH, TB = direct_tile(H, W)
+    sp = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1), (0, 0, W // 2), (0, H // 2, 0),
+          (0, H - 1, W // 2 - 1), (0, H // 2, W - 1), (0, H // 2, W // 2), (0, 1, 1), (0, H - 2, W - 2)]
+    for ys in range(TH, H, TH):
+        sp += [(0, ys - 1, W // 3), (0, ys, W // 3), (0, ys - 1, W - 1), (0, ys, 0)]
+    for xs in range(TW, W, TW):
+        sp += [(0, H // 3, xs - 1), (0, H // 3, xs), (0, 0, xs - 1), (0, H - 1, xs)]
+    if B > 1:
+        sp += [(1, 0, 0), (1, H - 1, W - 1), (B - 1, 0, W - 1), (B - 1, H - 1, 0)]
+    out = []
+    for s in sp:
+        if s not in out:
+            out.append(s)
+    return out
+
+
+def direct_onehot(c, tap, seed=0):
+    """exact inputs: x with single power-of-two pixels at direct_spots (ups = 1: on the low-resolution grid), one per
+    channel in turn; w with single power-of-two entries on tap (a, b) at a few (cout, cin).  Every output is a sum
+    of a few powers of two within a few binades: exact in fp32, in three bf16 and in two fp16 pieces"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    h, w_ = (H // 2, W // 2) if c['ups'] else (H, W)
+    x, w = torch.zeros(B, h, w_, Cin), torch.zeros(Cout, Cin, 3, 3)
+    spots = direct_spots(h, w_, B)
+    for n, (b, py, px) in enumerate(spots):
+        x[b, py, px, (5 * (n + seed)) % Cin] = 2.0 ** ((n + seed) % 5 - 2)
+    for n in range(min(len(spots), Cin)):
+        ci = (5 * (n + seed)) % Cin
+        w[(37 * n + seed) % Cout, ci, tap // 3, tap % 3] = 2.0 ** (n % 3 - 1) * (-1.0) ** n
+    return dict(x=x, w=w)
+
+
+def _dac(route, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, splitk=1, skip=None, pool_sum=False,
+             nomask=False, amax=None, pro=PRO_NONE, alpha=1.0, ups=0, wfmt='bf3', seq=False, finish='v4',
+             amax_out=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def direct_arb_id(c):
+    d = _dac(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+# the launch's Cin -> Cout.  Unsplit: one image per tile (F, B, H; R on the shared item); in K slices on the multi-image
+# 4x4 / 8x8 tiles, where the finish kernel does the backward per quad.  amax_out: the launch records the maxima of dx
+# (P2LArb.amax.out) -- what the plans' gradient launches do, and what makes the plain variant on H the class EPI_ARB
+# with its compiled epilogue (csrc/p2l_conv_k.h epi_class); every other variant and case runs the shared item
+DIRECT_ARB_CASES = [_dac(*base, **dict(kw, **v)) for base, kw in [
+    (('F', (16, 16), 2, 32, 64), {}), (('B', (16, 16), 2, 32, 64), {}), (('B', (24, 16), 2, 16, 96), dict(wfmt='bf3w')),
+    (('H', (16, 16), 2, 32, 64), {}), (('H', (16, 32), 2, 64, 64), dict(amax='true')),
+    (('H', (16, 16), 2, 16, 64), dict(amax_out=True)), (('H', (32, 4), 2, 32, 96), dict(amax_out=True)),
+    (('R', (16, 32), 2, 64, 64), dict(seq=True)),
+    (('F', (4, 4), 5, 128, 128), dict(splitk=4)), (('B', (8, 8), 3, 128, 64), dict(splitk=3)),
+    (('H', (8, 8), 3, 256, 64), dict(splitk=8)), (('H', (4, 4), 5, 128, 128), dict(splitk=4, amax='true'))]
+    for v in ARB_VARIANTS]
+
+
+def direct_arb_inputs(g, c):
+    i = arb_inputs(g, dict(c, route='C' if c['route'] in 'HR' else 'A'))
+    i['w'] = torch.randn(c['Cout'], c['Cin'], 3, 3, generator=g) / math.sqrt(9 * c['Cin'])
+    return i
+
+
+def direct_arb_refs(c, i):
+    """-> conv3x3_arb's dict in fp64 on the direct denominator (H, R: plus direct_h2_floor) and the route's fp32
+    restatement's, ds and dt in the kernels' two stages (arb_sums32: an unsplit launch leaves one partial per
+    128-pixel tile through epilogue_vec_items -- the register-resident kernel fills the same dumps --, a K-sliced one
+    one per quad)"""
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=c['Cout'] // 2 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    floor = None
+    if c['route'] in 'HR':
+        floor = direct_h2_floor(i['x'].abs(), i['w'], pw_amax(c, i)[1], i['w'].abs().max())
+    r64 = conv3x3_arb(i['x'].double(), i['w'].double(), i['ax'].double(), i['as'].double(), i['at'].double(),
+                      floor=floor, den_w=False, **kw)
+    r32 = conv3x3_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], acc=direct_acc32(c, i), den_w=False, **kw)
+    split = len(splitk_slices(9 * c['Cin'], 144, c['splitk'])) > 1
+    r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], split)
     return r64, r32
 
 

@@ -816,3 +816,198 @@ def test_winograd_case_tables():
     assert set((c['blk'], c['amax']) for c in hs) >= set([(8, None), (16, 'true'), (8, 'raw'), (16, 'applied')])
     assert len(set(R.wino_id(c) for c in R.WINO_FWD_CASES)) == len(R.WINO_FWD_CASES)
     assert len(set(R.wino_arb_id(c) for c in R.WINO_ARB_CASES)) == len(R.WINO_ARB_CASES)
+
+
+# ---- direct 3x3 convs: the references, restatements and cases of tests/test_direct_kernels_gpu.py -------------------
+@pytest.mark.parametrize('pro,pro_b', [(0, 1), (1, 1), (2, 0)])
+@pytest.mark.parametrize('epi', range(len(R.EPI)))
+def test_conv3x3_ups_is_nearest_interpolate_plus_conv2d(epi, pro, pro_b):
+    """ups = 1 in fp64: the prologue on the low-resolution x, F.interpolate(mode='nearest'), F.conv2d(padding=1), the
+    epilogue written out once more (res_ups and the pool on the output grid); den_d is the same expression on
+    absolute values"""
+    c = R._dc('F', (8, 12), 3, 16, 32, **dict(R.EPI[epi], pro=pro, pro_b=pro_b, n_store=24, ups=1))
+    i = {k: (v.to(D) if torch.is_tensor(v) else v) for k, v in R.direct_inputs(_g(190 + epi), c).items()}
+    assert i['x'].shape == (3, 4, 6, 16)
+    got = R.conv3x3(i['x'], i['w'], ups=True, den_w=False, **R.pw_kwargs(c, i, D))
+    a = i['x'].permute(0, 3, 1, 2)
+    if pro:
+        a = a * i['s'].expand(3, -1)[:, :, None, None] + i['t'].expand(3, -1)[:, :, None, None]
+        a = F.relu(a) if pro == R.PRO_AFFINE_RELU else a
+    v = c['alpha'] * F.conv2d(F.interpolate(a, scale_factor=2, mode='nearest'), i['w'], padding=1)
+    if c['oscale']:
+        v = v * i['oscale'][:, :, None, None]
+    if c['noise']:
+        v = v + i['noise_w'] * i['noise'][:, None]
+    if c['bias']:
+        v = v + i['bias'][None, :, None, None]
+    if c['res']:
+        r = i['res'].permute(0, 3, 1, 2)
+        v = v + (F.interpolate(r, scale_factor=2, mode='nearest') if c['res'] == 'ups' else r)
+    v = {0: lambda u: u, 1: F.relu, 2: torch.tanh, 3: lambda u: F.leaky_relu(u, 0.2) * R.SQRT2}[c['act']](v)
+    if c['mask']:
+        v = v * (i['mask'].permute(0, 3, 1, 2) > 0)
+    v = v[:, :24]
+    assert got['y'].shape == (3, 8, 12, 24)
+    assert (got['y'].permute(0, 3, 1, 2) - v).abs().max().item() < 1e-12 * v.abs().max().item()
+    if c['pool']:
+        p = F.max_pool2d(v, 2) if c['pool'] == R.POOL_MAX else F.avg_pool2d(v, 2) * 4
+        assert (got['yp'].permute(0, 3, 1, 2) - p).abs().max().item() < 1e-12 * v.abs().max().item()
+    lr = R.SQRT2 if c['act'] == 3 else 1
+    assert torch.equal(got['den'], got['den_d'])
+    assert bool((got['y'].abs() <= got['den_d'] * (1 + 1e-12) * lr).all())
+    pos = {k: (v_.abs() if torch.is_tensor(v_) else abs(v_) if k == 'noise_w' else v_) for k, v_ in i.items()}
+    kw = dict(R.pw_kwargs(c, pos, D), act=R.ACT_NONE, mask=None)
+    den = R.conv3x3(pos['x'], pos['w'], ups=True, den_w=False, **kw)['y']
+    assert (den - got['den_d']).abs().max().item() < 1e-12 * got['den_d'].max().item()
+
+
+@pytest.mark.parametrize('v', range(len(R.ARB_VARIANTS)))
+def test_conv3x3_arb_ups_is_autograd_through_the_forward(v):
+    """ups = 1 on the fused input gradient: da = conv3x3(up2(dy)) is the gradient of relu(x s + t) -> [up2 ->] the 3x3
+    conv -> 2x2 sum pool w.r.t. the conv's input; dx, ds, dt == autograd in fp64"""
+    c = R._dac('F', (4, 6), 2, 16, 32, **R.ARB_VARIANTS[v])
+    i = {k: t.to(D) for k, t in R.direct_arb_inputs(_g(210 + v), c).items()}
+    pre = i['ax'] * i['as'][:, None, None] + i['at'][:, None, None]
+    i['ax'] = torch.where(pre.abs() < 1e-3 * i['at'].abs()[:, None, None], i['ax'] + 1.0, i['ax'])
+    dy = i['x'][:, ::2, ::2].contiguous()                 # the low-resolution gradient the launch reads
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=16 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    got = R.conv3x3_arb(dy, i['w'], i['ax'], i['as'], i['at'], ups=True, den_w=False, **kw)
+    wf = i['w'].permute(1, 0, 2, 3).flip(2, 3)
+
+    def fwd(x, s, t):
+        a = x * s[:, None, None] + t[:, None, None]
+        a = a if c['nomask'] else torch.relu(a)
+        a = R.up2(a) if c['pool_sum'] else a
+        return R.quad_sum(F.conv2d(a.permute(0, 3, 1, 2), wf, padding=1).permute(0, 2, 3, 1))
+    dx, ds, dt = R.vjp(fwd, [i['ax'], i['as'], i['at']], dy)
+    if c['skip']:
+        sk = i['skip'][..., :16]
+        dx[..., :16] += sk.reshape(2, dx.shape[1], 2, dx.shape[2], 2, 16).sum(dim=(2, 4)) if c['skip'] == 'ups' else sk
+    for name, want in (('dx', dx), ('ds', ds), ('dt', dt)):
+        assert (got[name] - want).abs().max().item() < 1e-12 * want.abs().max().item(), name
+    assert bool((got['dx'].abs() <= got['den_dx'] * (1 + 1e-12)).all())
+    assert torch.equal(got['den_dx'], got['den_dx_d'])
+
+
+def test_direct_im2col_order_and_the_generalised_accumulators():
+    """direct_cols / direct_wmat: column ((chunk * 9 + tap) * 16 + channel) holds pixel (y + dy - 1, x + dx - 1) of
+    channel 16 chunk + channel and w[n, k, dy, dx]; their fp64 product is F.conv2d(padding=1); a chunk is 144
+    columns, so splitk_slices on them are the launch's slices of whole 16-channel chunks; with the default chunk
+    sizes acc_fp32 / acc_bf3 / acc_h2 are what they were for the 1x1 routes"""
+    g = _g(230)
+    a, w = torch.randn(2, 6, 4, 48, generator=g, dtype=D), torch.randn(32, 48, 3, 3, generator=g, dtype=D)
+    cols, wm = R.direct_cols(a), R.direct_wmat(w)
+    want = F.conv2d(a.permute(0, 3, 1, 2), w, padding=1).permute(0, 2, 3, 1)
+    assert (cols @ wm.t() - want).abs().max().item() < 1e-12
+    for chunk, tap, ch, y, x in ((0, 0, 0, 0, 0), (1, 5, 3, 2, 1), (2, 8, 15, 5, 3), (2, 2, 7, 0, 3), (1, 6, 9, 5, 0)):
+        col, dy, dx = (chunk * 9 + tap) * 16 + ch, tap // 3, tap % 3
+        assert torch.equal(wm[:, col], w[:, 16 * chunk + ch, dy, dx])
+        yy, xx = y + dy - 1, x + dx - 1
+        inside = 0 <= yy < 6 and 0 <= xx < 4
+        assert torch.equal(cols[:, y, x, col], a[:, yy, xx, 16 * chunk + ch] if inside else torch.zeros(2, dtype=D))
+    assert R.splitk_slices(9 * 128, 144, 3) == [(0, 432), (432, 864), (864, 1152)]          # 8 chunks: 3 + 3 + 2
+    assert R.splitk_slices(9 * 256, 144, 8) == [(z * 288, (z + 1) * 288) for z in range(8)]
+    a32, w32 = torch.randn(2, 4, 4, 96, generator=g), torch.randn(64, 96, generator=g)
+    assert torch.equal(R.acc_fp32(a32, w32, 2), R.acc_fp32(a32, w32, 2, 32))
+    assert torch.equal(R.acc_bf3(a32, w32), R.acc_bf3(a32, w32, 1, 96))
+    amax, wmax = a32.abs().amax(dim=(1, 2, 3)), w32.abs().max()
+    assert torch.equal(R.acc_h2(a32, w32, amax, wmax, 3), R.acc_h2(a32, w32, amax, wmax, 3, 32))
+    assert R.direct_tile(4, 4) == (4, 4, 8) and R.direct_tile(8, 8) == (8, 8, 2) and R.direct_tile(32, 4) == (4, 32, 1)
+    assert R.direct_tile(6, 6) == (8, 8, 2) and R.direct_tile(12, 20) == (16, 8, 1) and R.direct_tile(64, 64) == (16, 8, 1)
+
+
+@pytest.mark.parametrize('case', R.DIRECT_FWD_CASES, ids=R.direct_id)
+def test_direct_forward_restatements_stay_under_a_quarter_of_k(case):
+    """for every case's generator and shape the fp32 restatement of its route is within k / 4 of the fp64 reference on
+    den_d (H, R: plus direct_h2_floor): k and the floor were not set from the kernels.  Under PRO_AFFINE zero padding
+    applied in FRONT of the prologue would be more than 100 bars off at the border, so the cases see that mistake"""
+    def body(gen):
+        i = R.direct_inputs(gen('direct', R.direct_id(case)), case)
+        r64, r32 = R.direct_refs(case, i)
+        for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+            if r64[out] is not None:
+                f = _fig(r32[out], r64[out], r64[den])
+                assert f <= R.direct_k(case, None, pooled) / 4.0, (out, f, R.direct_k(case, None, pooled))
+        if case['pro'] == R.PRO_AFFINE and case['act'] == R.ACT_NONE and not case['mask']:
+            kw = R.pw_kwargs(case, i, D)
+            a, _ = R.pw_prologue(i['x'].double(), case['pro'], i['s'].double(), i['t'].double())
+            t_ = i['t'].double().expand(case['B'], -1)[:, None, None, :]
+            xs = R.up2(a - t_) if case['ups'] else a - t_
+            ap = F.pad(xs, (0, 0, 1, 1, 1, 1)) + t_                       # x s padded, t added after: the halo holds t
+            wrong = F.conv2d(ap.permute(0, 3, 1, 2), i['w'].double()).permute(0, 2, 3, 1) * case['alpha']
+            wrong = R.conv_epilogue(wrong, r64['den'], **{k: v for k, v in kw.items() if k not in ('pro', 's', 't', 'alpha')})
+            for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+                if r64[out] is None:
+                    continue
+                err = (wrong[out] - r64[out]).abs() / r64[den] / R.U
+                border = torch.ones(err.shape[1:3], dtype=torch.bool)
+                border[1:-1, 1:-1] = False
+                xmax = i['x'].abs().amax(dim=(1, 2, 3))
+                b0 = int(torch.where(xmax > 0, xmax, xmax.max()).argmin())    # (a shared t is scaled to this image)
+                live = r64[den][b0][border] > 0
+                bar = min(R.direct_k(case, None, pooled), 4.0 * _fig(r32[out], r64[out], r64[den]))
+                assert float(err[b0][border][live].median()) > 100 * bar, (out, bar)
+                assert float(err[:, ~border].max()) < 1e-3
+    _draws(body)
+
+
+@pytest.mark.parametrize('case', R.DIRECT_ARB_CASES, ids=R.direct_arb_id)
+def test_direct_dgrad_restatements_stay_under_a_quarter_of_k(case):
+    def body(gen):
+        i = R.direct_arb_inputs(gen('darb', R.direct_arb_id(case)), case)
+        kdx, kds, kdt = R.arb_k(case, R.direct_k)
+        r64, r32 = R.direct_arb_refs(case, i)
+        f = _fig(r32['dx'], r64['dx'], r64['den_dx'])
+        assert f <= kdx / 4.0, ('dx', f, kdx)
+        for name, bound in zip(('ds', 'dt'), R.arb_bound(case, r64, i['ax'], R.direct_k)):
+            assert bool(((r32[name].double() - r64[name]).abs() <= bound * R.U).all()), name
+        p64, p32 = R.direct_arb_refs(case, R.arb_positive(i))
+        for name, k in (('ds', kds), ('dt', kdt)):
+            f = _fig(p32[name], p64[name], p64['den_' + name])
+            assert f <= k / 4.0, (name, f, k)
+    _draws(body)
+
+
+@pytest.mark.parametrize('tap', range(9))
+def test_direct_one_hot_inputs_are_exact_in_every_restatement(tap):
+    """single power-of-two pixels and weights go through the fp32 chain, the bf16 x 3 and the fp16 x 2 pieces and the
+    slices without a rounding: all three restatements give the fp64 result bit for bit, and it is not all zero"""
+    for c in (R._dsh('F', '12x20'), R._dsh('B', '6x6'), R._dsh('H', '8x8'), R._dsh('R', '16x32'),
+              R._dsh('F', '16x16', ups=1), R._dsh('B', '8x8', ups=1, wfmt='bf3w'), R._dsh('H', 'k3', splitk=3),
+              R._dsh('B', 'k4s', splitk=4), R._dsh('F', 'k8', splitk=8)):
+        for seed in range(3):
+            i = R.direct_onehot(c, tap, seed)
+            r64, r32 = R.direct_refs(c, i)
+            assert torch.equal(r32['y'].double(), r64['y']), (R.direct_id(c), seed)
+            assert int((r64['y'] != 0).sum()) >= 3, (R.direct_id(c), seed)
+
+
+def test_direct_case_tables():
+    """every EPI term, n_store < Cout, both prologues and the shared one on every route; ups = 1 on F and B unsplit
+    and sliced; H and R with all three sources of their maxima; the K slices on F, B and H through both finish
+    kernels; every shape the tile, channel-tile and slice rules distinguish; the images of a launch 3e10 apart"""
+    for route in 'FBHR':
+        cs = [c for c in R.DIRECT_FWD_CASES if c['route'] == route]
+        for e in R.EPI:
+            assert any(all(c[k] == v for k, v in e.items()) for c in cs), (route, e)
+        assert any(c['n_store'] < c['Cout'] for c in cs) and any(c['pro'] and not c['pro_b'] for c in cs)
+        assert set(c['pro'] for c in cs) == set([0, 1, 2])
+        if route in 'FB':
+            assert any(c['ups'] and c['splitk'] == 1 for c in cs) and any(c['ups'] and c['splitk'] > 1 for c in cs)
+        if route in 'HR':
+            assert set(c['amax'] for c in cs) == set([None, 'true', 'raw', 'applied'])
+            assert not any(c['ups'] for c in cs)
+        if route != 'R':
+            assert set(len(R.splitk_slices(9 * c['Cin'], 144, c['splitk'])) for c in cs) >= set([1, 3, 4, 8])
+            assert any(c['finish'] == 'scalar' for c in cs)
+            assert set(R.direct_tile(c['H'], c['W']) for c in cs) >= set([(4, 4, 8), (8, 8, 2), (4, 32, 1), (16, 8, 1)])
+            assert any(c['H'] % R.direct_tile(c['H'], c['W'])[1] and R.direct_tile(c['H'], c['W'])[2] > 1 for c in cs)
+            assert any(c['Cout'] == 96 for c in cs) and any(c['B'] * c['H'] * c['W'] // 128 * (c['Cout'] // 64) >= 320 for c in cs)
+    b = [c for c in R.DIRECT_FWD_CASES if c['route'] == 'B']
+    assert set(R.direct_form(c)[0] for c in b) == set([R.WFMT_BF16X3, R.WFMT_BF16X3W])
+    assert len(set(R.direct_id(c) for c in R.DIRECT_FWD_CASES)) == len(R.DIRECT_FWD_CASES)
+    assert len(set(R.direct_arb_id(c) for c in R.DIRECT_ARB_CASES)) == len(R.DIRECT_ARB_CASES)
+    i = R.direct_inputs(_g(240), R._dsh('F', '8x8', **R.EPI[0]))
+    m = i['x'].abs().amax(dim=(1, 2, 3))
+    assert float(m[2] / m[0]) > 1e13 and float(i['res'][2].abs().max() / i['res'][0].abs().max()) > 1e9

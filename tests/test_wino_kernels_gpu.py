@@ -632,4 +632,4 @@ def test_another_slice_count_runs_the_direct_kernel(dev, N):
     assert got.fam[FAM_DIRECT_H2] == 1 and sum(got.fam) == 1 and abs(got.exec_flops - direct) <= 1e-9 * direct
     r64, _ = R.wino_refs(c, i, 'F')
     hold_k('p2l_conv_fwd:y / den_d', 'direct-h2-' + R.wino_id(c), got.y, r64['y'],
-           r64['den_d'] + R.direct_h2_floor(i['x'], i['w']), R.direct_h2_k(c, 4))
+           r64['den_d'] + R.direct_h2_floor(i['x'], i['w']), R.direct_k(c, 'H'))
