@@ -50,7 +50,9 @@ extern "C" {
  *   p2l_sg2_pixelnorm_fwd/_bwd, p2l_sg2_bias_lrelu_fwd, p2l_sg2_lrelu_bwd, p2l_sg2_demod_fwd/_bwd,
  *   p2l_sg2_styled_act_bwd(_amax), p2l_sg2_rgb_up_fwd/_bwd, p2l_sg2_clamp16_fwd/_bwd, p2l_broadcast_rows,
  *   p2l_add_inplace, p2l_sg2_noise_relayout, p2l_area_pool3_to_nhwc16, p2l_area_pool_nchw,
- *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd, p2l_l2_loss_fwd/_bwd, p2l_adam_step_sched.
+ *   p2l_area_unpool16_add_nchw3, p2l_latent_prior_fwd/_bwd, p2l_l2_loss_fwd/_bwd, p2l_adam_step_sched,
+ *   p2l_nhwc_to_nchw, p2l_nchw_to_nhwc, p2l_feature_anchor_fwd/_bwd, p2l_sg2_synthesis_from_fwd/_bwd,
+ *   p2l_sg2_capture.
  * The conv launches -- p2l_conv_fwd(_ex), p2l_conv_dgrad_arb(_ws) -- refuse in the same way, for the operands that
  * are PRESENT, a pitch below the row it pitches: x_ld < Cin; y_ld, yp_ld, res_ld, mask_ld, P2LArb.x_ld < n_store;
  * pro_bstride, P2LArb.st_bstride, P2LConvExtra.oscale_bstride in 1 .. row - 1 (0 = shared by the images);
@@ -1117,6 +1119,41 @@ int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent, const floa
 int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent, const float* noise, int Bn,
                           void* ws, size_t ws_bytes, const float* dimg16, float* dlatent,
                           float* dnoise, void* stream);
+/* Feature-space (F/W+) inversion: the synthesis from a chosen resolution on (csrc/p2l_plan_sg2.hip, DESIGN.md section
+ * 15).  res is a power of two with 4 <= res <= size / 2.  With k = log2 res, l0 = 2 (k - 2) + 1 is the first styled
+ * conv that runs (the up conv to 2 res) and j0 = k - 2 the last ToRGB that does NOT run.  The run reads
+ *   feat_nchw  [Bn][C][res][res], C = conv[l0].cin: y[l0 - 1], the post-activation output of the plain conv at res;
+ *   skip_nchw3 [Bn][3][res][res]: skip[j0], the unclamped partial RGB at res;
+ * the W+ rows conv[l >= l0].latent_idx and rgb[j > j0].latent_idx of latent [Bn][n_latent][512], and the noise of
+ * conv[l >= l0] (noise is the layer-major vector of the full run; the slices in front of Bn * conv[l0].noise_off are
+ * not read).  _from_fwd transposes feat and skip into the workspace slots of y[l0 - 1] and skip[j0], computes styles
+ * and demodulation of the layers that run and then runs the layer loop of p2l_sg2_synthesis_fwd from l0 / j0 + 1
+ * (conv[l0] reduces the maxima of its input itself, as conv[0] of the full run does) and the clamp.  The workspace
+ * is the one of the full run (p2l_sg2_ws_bytes), and p2l_sg2_ws_lookup describes it for the layers >= l0.
+ * _from_bwd takes the workspace as _from_fwd left it: dlatent [Bn][n_latent][512] (the rows that were not read are
+ * written as 0), dnoise layer-major or NULL (the slices that were not read are written as 0), dfeat_nchw (the input
+ * gradient of conv[l0] alone: ToRGB j0 is outside the graph) or NULL, dskip_nchw3 (from the skip up-sampling of
+ * ToRGB j0 + 1) or NULL.
+ * p2l_sg2_capture copies y[l0 - 1] and skip[j0] out of the workspace of a finished p2l_sg2_synthesis_fwd on Bn
+ * candidates, in the layouts _from_fwd takes.
+ * Before anything is launched: P2L_EINVAL for a res that is not such a power of two or does not match the descriptor,
+ * a NULL m or pointer (other than the optional ones above) and Bn < 1; P2L_EWS for a NULL or short workspace. */
+int p2l_sg2_synthesis_from_fwd(const P2LStyleGAN2* m, int res, const float* feat_nchw, const float* skip_nchw3,
+                               const float* latent, const float* noise, int Bn, void* ws, size_t ws_bytes,
+                               float* img16, void* stream);
+int p2l_sg2_synthesis_from_bwd(const P2LStyleGAN2* m, int res, const float* latent, const float* noise, int Bn,
+                               void* ws, size_t ws_bytes, const float* dimg16, float* dlatent, float* dnoise,
+                               float* dfeat_nchw, float* dskip_nchw3, void* stream);
+int p2l_sg2_capture(const P2LStyleGAN2* m, int res, int Bn, const void* ws, size_t ws_bytes, float* feat_nchw,
+                    float* skip_nchw3, void* stream);
+/* Batched layout transposes through LDS (csrc/p2l_sg2_feat.hip): src [Bn][H][W][C] -> dst [Bn][C][H][W] and back,
+ * dense, any C, H, W >= 1 (Bn <= 65535; the SOURCE has at most 65535 * 64 rows per image: H W for the first, C for
+ * the second; H W < 2^31).  64 x 64 tiles; loads and stores
+ * are coalesced, 16 bytes per lane on a side whose row length (C or H W) is a multiple of 4 and whose pointer is
+ * 16-byte aligned, 4 bytes otherwise.  No workspace; src and dst must not overlap.  P2L_EINVAL (NULL src / dst, a
+ * size < 1 or above the limits) before the launch. */
+int p2l_nhwc_to_nchw(const float* src, float* dst, int Bn, int C, int H, int W, void* stream);
+int p2l_nchw_to_nhwc(const float* src, float* dst, int Bn, int C, int H, int W, void* stream);
 /* mapping network: z [B,512] -> w [B,512]; acts: 9*B*512 floats kept for the backward */
 int p2l_sg2_mapping_fwd(const P2LStyleGAN2* m, const float* z, float* w, float* acts, int Bn,
                         void* stream);
@@ -1167,6 +1204,23 @@ int p2l_latent_prior_fwd(const float* w, const double* basis_t, const double* me
                          int D, int K, int p_space, float* loss, void* ws, size_t ws_bytes, void* stream);
 int p2l_latent_prior_bwd(const float* w, const double* basis, const double* layer_w, const float* gloss, int B, int L,
                          int D, int K, int p_space, const void* ws, size_t ws_bytes, float* dw, void* stream);
+
+/* FeatureAnchor: keeps an optimised activation near its start (csrc/p2l_sg2_feat.hip).
+ * f [Bn][n] fp32, anchor [n] (anchor_bstride = 0: shared by the candidates) or [Bn][n] (anchor_bstride = n; any
+ * stride >= n), on the device:   loss[b] = weight (1 / n) sum_i (f[b,i] - anchor[b,i])^2
+ * with f - anchor exact in fp64, squares and sums in fp64 in an order that follows from n alone (4096-element chunks),
+ * weight * (sum / n) rounded once to fp32.  _bwd: df[b,i] = gloss[b] (NULL = 1) * (2 weight / n) * (f - anchor), fp64,
+ * rounded once; gloss is applied last, so gloss = 2 or -1 scale the result bit for bit.  A candidate's loss and df do
+ * not depend on Bn, on its row, on the stream or on the call.  Launches: forward 2, backward 1, whatever Bn is; no
+ * atomics, no memset.  The forward's workspace holds Bn * ceil(n / 4096) fp64 partial sums; the backward needs none.
+ * P2L_EINVAL (NULL f / anchor / loss / df, Bn < 1 or > 65535, n < 1 or >= 2^31, a stride in 1 .. n - 1) and P2L_EWS
+ * (NULL, not 8-byte aligned or short workspace) are returned before any launch; p2l_feature_anchor_ws_bytes is
+ * host-only and 0 for sizes the launches refuse. */
+size_t p2l_feature_anchor_ws_bytes(int Bn, int64_t n);
+int p2l_feature_anchor_fwd(const float* f, const float* anchor, int64_t anchor_bstride, int Bn, int64_t n,
+                           double weight, float* loss, void* ws, size_t ws_bytes, void* stream);
+int p2l_feature_anchor_bwd(const float* f, const float* anchor, int64_t anchor_bstride, const float* gloss, int Bn,
+                           int64_t n, double weight, float* df, void* stream);
 
 
 #ifdef __cplusplus

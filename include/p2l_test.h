@@ -42,7 +42,11 @@ int p2l_projloss_ws_lookup(int Bn, int H, int W, int idx, size_t* float_off, int
 int p2l_sqzloss_ws_lookup(int Bn, int H, int W, int idx, size_t* float_off, int32_t shape[4]);
 
 /* debug/test hook: float offset + shape [B,res,res,cout] of the post-activation output of styled conv l
- * (0 .. n_conv-1) inside ws after p2l_sg2_synthesis_fwd: the signs are the run's leaky-ReLU decisions */
+ * (0 .. n_conv-1) inside ws after p2l_sg2_synthesis_fwd: the signs are the run's leaky-ReLU decisions.
+ * l = P2L_SG2_WS_SKIP + j (j = 0 .. n_rgb-1): the unclamped partial RGB behind ToRGB j, [B,res,res,16] (3 real
+ * channels).  After p2l_sg2_synthesis_from_fwd the layers >= l0 and the ToRGBs > j0 are those of that run, y[l0-1]
+ * and skip[j0] what it was given. */
+#define P2L_SG2_WS_SKIP 1000
 int p2l_sg2_ws_lookup(const P2LStyleGAN2* m, int Bn, int l, size_t* float_off, int32_t shape[4]);
 
 /* MFMA layout self-test: C[32x32] = A[32xK] * B[Kx32] via one wave. */

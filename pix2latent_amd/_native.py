@@ -316,6 +316,8 @@ EXPORTS = [
     'p2l_area_pool3_to_nhwc16', 'p2l_area_pool_nchw', 'p2l_area_unpool16_add_nchw3',
     'p2l_latent_prior_ws_bytes', 'p2l_latent_prior_fwd', 'p2l_latent_prior_bwd',
     'p2l_l2_loss_nblk', 'p2l_l2_loss_fwd', 'p2l_l2_loss_bwd', 'p2l_adam_step_sched',
+    'p2l_sg2_synthesis_from_fwd', 'p2l_sg2_synthesis_from_bwd', 'p2l_sg2_capture', 'p2l_nhwc_to_nchw', 'p2l_nchw_to_nhwc',
+    'p2l_feature_anchor_ws_bytes', 'p2l_feature_anchor_fwd', 'p2l_feature_anchor_bwd',
 ]
 
 _lib = None
@@ -402,6 +404,21 @@ def lib():
         _lib.p2l_latent_prior_ws_bytes.argtypes = [i32, i32, i32]
         _lib.p2l_latent_prior_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
         _lib.p2l_latent_prior_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp]
+        # (a library of version 101 built before these entry points existed still loads -- P2L_LIB_PATH, the A/B
+        #  runs of tools/plan_bits.py -- and fails at the call that needs one; __graft_entry__.build() checks EXPORTS)
+        for name, types in (
+                ('p2l_sg2_synthesis_from_fwd', [vp, i32, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp]),
+                ('p2l_sg2_synthesis_from_bwd', [vp, i32, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+                ('p2l_sg2_capture', [vp, i32, i32, vp, C.c_size_t, vp, vp, vp]),
+                ('p2l_nhwc_to_nchw', [vp, vp, i32, i32, i32, i32, vp]),
+                ('p2l_nchw_to_nhwc', [vp, vp, i32, i32, i32, i32, vp]),
+                ('p2l_feature_anchor_ws_bytes', [i32, i64_]),
+                ('p2l_feature_anchor_fwd', [vp, vp, i64_, i32, i64_, C.c_double, vp, vp, C.c_size_t, vp]),
+                ('p2l_feature_anchor_bwd', [vp, vp, i64_, vp, i32, i64_, C.c_double, vp, vp])):
+            if hasattr(_lib, name):
+                getattr(_lib, name).argtypes = types
+                if name.endswith('_ws_bytes'):
+                    getattr(_lib, name).restype = C.c_size_t
     return _lib
 
 

@@ -181,10 +181,17 @@ extern "C" size_t p2l_sg2_ws_bytes(const P2LStyleGAN2* m, int Bn) {
 
 // test hook (include/p2l_test.h): where the post-activation output of styled conv l lives in ws after
 // p2l_sg2_synthesis_fwd, NHWC [B, res, res, cout] -- its signs are the leaky-ReLU decisions of the run
-// (oracle/replay.py replays them in the CPU oracle)
+// (oracle/replay.py replays them in the CPU oracle); l = P2L_SG2_WS_SKIP + j: the partial RGB behind ToRGB j, NHWC16
 extern "C" int p2l_sg2_ws_lookup(const P2LStyleGAN2* m, int Bn, int l, size_t* float_off, int32_t shape[4]) {
   SgLayout L;
-  if (!m || !float_off || !shape || sg_layout(m, Bn, L) || l < 0 || l >= m->n_conv) return P2L_EINVAL;
+  if (!m || !float_off || !shape || sg_layout(m, Bn, L)) return P2L_EINVAL;
+  if (l >= P2L_SG2_WS_SKIP && l < P2L_SG2_WS_SKIP + m->n_rgb) {
+    const int j = l - P2L_SG2_WS_SKIP;
+    *float_off = L.skip[j];
+    shape[0] = Bn; shape[1] = m->rgb[j].res; shape[2] = m->rgb[j].res; shape[3] = 16;
+    return P2L_OK;
+  }
+  if (l < 0 || l >= m->n_conv) return P2L_EINVAL;
   *float_off = L.y[l];
   shape[0] = Bn; shape[1] = m->conv[l].res; shape[2] = m->conv[l].res; shape[3] = m->conv[l].cout;
   return P2L_OK;
@@ -222,24 +229,41 @@ extern "C" int p2l_sg2_mapping_bwd(const P2LStyleGAN2* m, const float* z, const 
   return p2l_sg2_pixelnorm_bwd(z, g, dz, B, D, st);
 }
 
-extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
-                                     const float* noise, int B, void* ws, size_t ws_bytes,
-                                     float* img16, void* st) {
-  SgLayout L;
-  RET_IF(sg_layout(m, B, L));
-  if (!ws || ws_bytes < L.total * sizeof(float) || !latent || !noise || !img16) return P2L_EWS;
-  float* W = (float*)ws;
+namespace {
+
+// The cut of the feature-space run: conv[l0] is the first styled conv that runs, rgb[j0] the
+// last ToRGB that does not.  l0 = 0, j0 = -1 is the full run.
+struct SgCut { int l0, j0; };
+
+// res -> cut, checked against the descriptor (host only)
+int sg_cut(const P2LStyleGAN2* m, int res, SgCut& c) {
+  if (!m || !is_pow2(res) || res < 4 || res > m->size / 2) return P2L_EINVAL;
+  c.j0 = ilog2(res) - 2;
+  c.l0 = 2 * c.j0 + 1;
+  if (c.l0 >= m->n_conv || c.j0 + 1 >= m->n_rgb || m->n_conv > P2L_SG2_MAX_CONVS || m->n_rgb > P2L_SG2_MAX_RGBS)
+    return P2L_EINVAL;
+  if (!m->conv[c.l0].up || m->conv[c.l0 - 1].res != res || m->conv[c.l0 - 1].cout != m->conv[c.l0].cin ||
+      m->rgb[c.j0].res != res || m->rgb[c.j0].after_conv != c.l0 - 1 || m->rgb[c.j0 + 1].after_conv <= c.l0)
+    return P2L_EINVAL;
+  return P2L_OK;
+}
+
+// styles, demodulation and the layer loop from conv[l0] / rgb[j0 + 1] to the clamp.  The input of conv[l0] is the
+// constant (l0 = 0) or what the caller left in the slot of y[l0 - 1]; rgb[j0 + 1] adds the up-sampled skip[j0].
+int sg_forward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* latent, const float* noise, int B,
+               SgCut cut, float* img16, void* st) {
+  const int l0 = cut.l0, j0 = cut.j0;
   const int D = m->style_dim, lat_ld = m->n_latent * D;
   if (hipMemsetAsync(W + L.zeros, 0, (L.ubuf - L.zeros) * sizeof(float), (hipStream_t)st) != hipSuccess)
     return P2L_ELAUNCH;
-  RET_IF(p2l_broadcast_rows(m->const_input, W + L.x0, (int64_t)16 * m->conv[0].cin, B, st));
-  const float* x = W + L.x0;
+  if (l0 == 0) RET_IF(p2l_broadcast_rows(m->const_input, W + L.x0, (int64_t)16 * m->conv[0].cin, B, st));
+  const float* x = l0 == 0 ? W + L.x0 : W + L.y[l0 - 1];
   {
     // every layer's style s = latent . mod_w + mod_b and demodulation scale
     // d = rsqrt(s^2 . wsq + eps) depend only on the latents: two grouped launches
     p2lsg2::GLinFwdK gs{}, gd{};
     gs.Bn = gd.Bn = B; gs.mode = 0; gd.mode = 1;
-    for (int l = 0; l < m->n_conv; ++l) {
+    for (int l = l0; l < m->n_conv; ++l) {
       const P2LSg2Conv& c = m->conv[l];
       p2lsg2::GLinItem& a = gs.g[gs.n++];
       a.W = c.mod_w; a.bias = c.mod_b; a.x = latent + (size_t)c.latent_idx * D; a.x_ld = lat_ld;
@@ -248,7 +272,7 @@ extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
       e.W = c.wsq; e.bias = nullptr; e.x = W + L.s[l]; e.x_ld = c.cin;
       e.y = W + L.d[l]; e.y_ld = c.cout; e.K = c.cin; e.N = c.cout;
     }
-    for (int j = 0; j < m->n_rgb; ++j) {
+    for (int j = j0 + 1; j < m->n_rgb; ++j) {
       const P2LSg2Rgb& r = m->rgb[j];
       p2lsg2::GLinItem& a = gs.g[gs.n++];
       a.W = r.mod_w; a.bias = r.mod_b; a.x = latent + (size_t)r.latent_idx * D; a.x_ld = lat_ld;
@@ -266,8 +290,8 @@ extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
     return P2L_ELAUNCH;
   const float* am_in = nullptr;          // maxima of x with s[l] applied, [B][am_n]
   int am_n = 0;
-  int rj = 0;
-  for (int l = 0; l < m->n_conv; ++l) {
+  int rj = j0 + 1;
+  for (int l = l0; l < m->n_conv; ++l) {
     const P2LSg2Conv& c = m->conv[l];
     const float* nz = noise + (size_t)B * c.noise_off;
     P2LConv d = mk(m->wfmt, B, c.res, c.cin, c.cout, 9);
@@ -327,16 +351,14 @@ extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
   return p2l_sg2_clamp16_fwd(W + L.skip[m->n_rgb - 1], img16, (int64_t)B * m->size * m->size, st);
 }
 
-extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
-                                     const float* noise, int B, void* ws, size_t ws_bytes,
-                                     const float* dimg16, float* dlatent, float* dnoise,
-                                     void* st) {
-  SgLayout L;
-  RET_IF(sg_layout(m, B, L));
-  if (!ws || ws_bytes < L.total * sizeof(float) || !dimg16 || !dlatent) return P2L_EWS;
-  float* W = (float*)ws;
+// The backward of sg_forward: from the clamp down to conv[l0].  dlatent is zero-filled as a whole and receives the
+// rows of the layers that ran.  *gx_out: the gradient with respect to the input of conv[l0], NHWC, and *gskip_out:
+// the gradient with respect to skip[j0], NHWC16 (j0 >= 0), both inside the workspace.
+int sg_backward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* noise, int B, SgCut cut,
+                const float* dimg16, float* dlatent, float* dnoise, const float** gx_out, const float** gskip_out,
+                void* st) {
+  const int l0 = cut.l0, j0 = cut.j0;
   const int D = m->style_dim, lat_ld = m->n_latent * D;
-  (void)latent;
   if (hipMemsetAsync(dlatent, 0, (size_t)B * lat_ld * sizeof(float), (hipStream_t)st) != hipSuccess)
     return P2L_ELAUNCH;
   const bool hand = !(m->wfmt & P2L_WFMT_FLAG_NO_AMAX);
@@ -360,13 +382,13 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
   } defer;
   bool have_next = false;    // gx holds a gradient for the current layer's output
   int rj = m->n_rgb - 1;
-  for (int l = m->n_conv - 1; l >= 0; --l) {
+  for (int l = m->n_conv - 1; l >= l0; --l) {
     const P2LSg2Conv& c = m->conv[l];
     const float* x_in = (l == 0) ? W + L.x0 : W + L.y[l - 1];
     const int res_in = c.up ? c.res / 2 : c.res;
     // ---- ToRGB reading y_l -------------------------------------------------
     bool gy_ready = false;
-    while (rj >= 0 && m->rgb[rj].after_conv == l) {
+    while (rj > j0 && m->rgb[rj].after_conv == l) {
       const P2LSg2Rgb& r = m->rgb[rj];
       P2LConv t = mk(m->wfmt, B, r.res, 16, r.cin, 1);
       t.algo_flops = 2.0 * B * r.res * r.res * (double)r.cin * 3;
@@ -414,7 +436,7 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
   // latent row at most once, and the two launches are ordered -> deterministic)
   p2lsg2::GLinBwdK gm{}, gc{}, gr{};
   gm.Bn = gc.Bn = gr.Bn = B; gm.mode = 1;
-  for (int l = 0; l < m->n_conv; ++l) {
+  for (int l = l0; l < m->n_conv; ++l) {
     const P2LSg2Conv& c = m->conv[l];
     p2lsg2::GLinBwdItem& a = gm.g[gm.n++];
     a.W = c.wsq; a.dy = W + L.dd[l]; a.d = W + L.d[l]; a.x = W + L.s[l]; a.dx = W + L.ds[l];
@@ -423,7 +445,7 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
     e.W = c.mod_w; e.dy = W + L.ds[l]; e.dx = dlatent + (size_t)c.latent_idx * D;
     e.K = D; e.N = c.cin; e.dx_ld = lat_ld; e.accumulate = 1;
   }
-  for (int j = 0; j < m->n_rgb; ++j) {
+  for (int j = j0 + 1; j < m->n_rgb; ++j) {
     const P2LSg2Rgb& r = m->rgb[j];
     p2lsg2::GLinBwdItem& e = gr.g[gr.n++];
     e.W = r.mod_w; e.dy = W + L.rds[j]; e.dx = dlatent + (size_t)r.latent_idx * D;
@@ -434,5 +456,73 @@ extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
   RET_IF(p2lsg2::grouped_linear_bwd(gm, st));
   RET_IF(p2lsg2::grouped_linear_bwd(gc, st));
   RET_IF(p2lsg2::grouped_linear_bwd(gr, st));
+  if (gx_out) *gx_out = gx;
+  if (gskip_out) *gskip_out = gs_cur;
   return P2L_OK;
+}
+
+}  // namespace
+
+extern "C" int p2l_sg2_synthesis_fwd(const P2LStyleGAN2* m, const float* latent,
+                                     const float* noise, int B, void* ws, size_t ws_bytes,
+                                     float* img16, void* st) {
+  SgLayout L;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float) || !latent || !noise || !img16) return P2L_EWS;
+  return sg_forward(m, L, (float*)ws, latent, noise, B, SgCut{0, -1}, img16, st);
+}
+
+extern "C" int p2l_sg2_synthesis_bwd(const P2LStyleGAN2* m, const float* latent,
+                                     const float* noise, int B, void* ws, size_t ws_bytes,
+                                     const float* dimg16, float* dlatent, float* dnoise,
+                                     void* st) {
+  SgLayout L;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float) || !dimg16 || !dlatent) return P2L_EWS;
+  (void)latent;
+  return sg_backward(m, L, (float*)ws, noise, B, SgCut{0, -1}, dimg16, dlatent, dnoise, nullptr, nullptr, st);
+}
+
+extern "C" int p2l_sg2_synthesis_from_fwd(const P2LStyleGAN2* m, int res, const float* feat_nchw,
+                                          const float* skip_nchw3, const float* latent, const float* noise, int B,
+                                          void* ws, size_t ws_bytes, float* img16, void* st) {
+  SgCut cut;
+  SgLayout L;
+  if (B < 1 || sg_cut(m, res, cut) || !feat_nchw || !skip_nchw3 || !latent || !noise || !img16) return P2L_EINVAL;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float)) return P2L_EWS;
+  float* W = (float*)ws;
+  RET_IF(p2l_nchw_to_nhwc(feat_nchw, W + L.y[cut.l0 - 1], B, m->conv[cut.l0].cin, res, res, st));
+  RET_IF(p2l_nchw3_to_nhwc16(skip_nchw3, W + L.skip[cut.j0], B, res, res, st));
+  return sg_forward(m, L, W, latent, noise, B, cut, img16, st);
+}
+
+extern "C" int p2l_sg2_synthesis_from_bwd(const P2LStyleGAN2* m, int res, const float* latent, const float* noise,
+                                          int B, void* ws, size_t ws_bytes, const float* dimg16, float* dlatent,
+                                          float* dnoise, float* dfeat_nchw, float* dskip_nchw3, void* st) {
+  SgCut cut;
+  SgLayout L;
+  if (B < 1 || sg_cut(m, res, cut) || !latent || !noise || !dimg16 || !dlatent) return P2L_EINVAL;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float)) return P2L_EWS;
+  // (layer-major noise: the layers below the cut are the front of the vector)
+  const size_t below = (size_t)B * m->conv[cut.l0].noise_off;
+  if (dnoise && hipMemsetAsync(dnoise, 0, below * sizeof(float), (hipStream_t)st) != hipSuccess) return P2L_ELAUNCH;
+  const float *gx = nullptr, *gskip = nullptr;
+  RET_IF(sg_backward(m, L, (float*)ws, noise, B, cut, dimg16, dlatent, dnoise, &gx, &gskip, st));
+  if (dfeat_nchw) RET_IF(p2l_nhwc_to_nchw(gx, dfeat_nchw, B, m->conv[cut.l0].cin, res, res, st));
+  if (dskip_nchw3) RET_IF(p2l_nhwc16_to_nchw3(gskip, dskip_nchw3, B, res, res, st));
+  return P2L_OK;
+}
+
+extern "C" int p2l_sg2_capture(const P2LStyleGAN2* m, int res, int B, const void* ws, size_t ws_bytes,
+                               float* feat_nchw, float* skip_nchw3, void* st) {
+  SgCut cut;
+  SgLayout L;
+  if (B < 1 || sg_cut(m, res, cut) || !feat_nchw || !skip_nchw3) return P2L_EINVAL;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float)) return P2L_EWS;
+  const float* W = (const float*)ws;
+  RET_IF(p2l_nhwc_to_nchw(W + L.y[cut.l0 - 1], feat_nchw, B, m->conv[cut.l0].cin, res, res, st));
+  return p2l_nhwc16_to_nchw3(W + L.skip[cut.j0], skip_nchw3, B, res, res, st);
 }

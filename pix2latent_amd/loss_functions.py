@@ -389,6 +389,95 @@ class LatentPrior(object):
 
 
 # ---------------------------------------------------------------------------
+# Anchor of an optimised activation: the F of F/W+ inversion
+# ---------------------------------------------------------------------------
+def _anchor_shape_ok(f, anchor):
+    return tuple(anchor.shape) in (tuple(f.shape[1:]), tuple(f.shape))
+
+
+def feature_anchor_torch(f, anchor, weight=1.0):
+    """The definition in torch ops, on any device.  f [B, ...], anchor of the shape of f[0] (shared by the candidates)
+    or of f:   loss[b] = weight * (1 / n) * sum_i (f[b, i] - anchor[i])^2,  n = the elements of one candidate,
+    in fp64, rounded once to fp32; differentiable in f.  The CPU path of `feature_anchor`."""
+    anchor = torch.as_tensor(anchor).to(f.device)
+    if not _anchor_shape_ok(f, anchor):
+        raise ValueError('feature_anchor: f %s under an anchor %s' % (tuple(f.shape), tuple(anchor.shape)))
+    d = (f.double() - anchor.double()).reshape(f.size(0), -1)
+    return (float(weight) * ((d * d).sum(1) / d.size(1))).float()
+
+
+class _FeatureAnchorFn(torch.autograd.Function):
+    """loss [B] of f through p2l_feature_anchor_fwd / _bwd: the backward reads f and the anchor again, nothing is
+    shared between lanes or with a captured graph, nothing waits for the host."""
+
+    @staticmethod
+    def forward(ctx, f, anchor, weight):
+        from . import ops
+        x = f.detach()
+        ctx.save_for_backward(x, anchor)
+        ctx.weight = weight
+        return ops.feature_anchor_fwd(x, anchor, weight)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        from . import ops
+        x, anchor = ctx.saved_tensors
+        return ops.feature_anchor_bwd(x, anchor, ctx.weight, gloss.float().contiguous()), None, None
+
+
+def feature_anchor(f, anchor, weight=1.0):
+    """loss [B] fp32 = weight * mean_i (f[b, i] - anchor[i])^2, differentiable in f ([B, ...]; anchor of the shape
+    of f[0] or of f, fp32, on the device of f).  Device tensors run the HIP kernels, CPU tensors
+    `feature_anchor_torch`."""
+    if not f.is_cuda:
+        return feature_anchor_torch(f, anchor, weight)
+    if not _anchor_shape_ok(f, anchor):
+        raise ValueError('feature_anchor: f %s under an anchor %s' % (tuple(f.shape), tuple(anchor.shape)))
+    if anchor.device != f.device or anchor.dtype != torch.float32 or not anchor.is_contiguous():
+        raise ValueError('feature_anchor: the anchor is a contiguous fp32 tensor on %s' % f.device)
+    if f.dtype != torch.float32 or not f.is_contiguous():
+        f = f.float().contiguous()
+    return _FeatureAnchorFn.apply(f, anchor, float(weight))
+
+
+class FeatureAnchor(object):
+    """`weight * mean((F - anchor)^2)` per candidate: the `regularizer=` of an optimised activation
+    (`var_manager.register('feat', ..., regularizer=LF.FeatureAnchor(feat0))`) -- the term ||F - F_init||^2 of the
+    F/W+ space of BDInvert (Kang et al. 2021) and the FS space of Barbershop (Zhu et al. 2021), which keeps F near
+    the activations of the W+ solution it started from.  `anchor` has the shape of one candidate ([C, r, r], shared)
+    or of all of them ([B, C, r, r]).  A contiguous fp32 device tensor is read in place (no copy is made: writing to
+    it changes the term, and its version is part of the graph key); anything else is copied to the device of F at
+    its first use there, which therefore must not happen inside a graph capture."""
+
+    def __init__(self, anchor, weight=1.0):
+        self.anchor = torch.as_tensor(anchor).detach()
+        self.weight = float(weight)
+        self._on_device = {}
+
+    def _device_anchor(self, device):
+        a = self.anchor
+        if a.device == device and a.dtype == torch.float32 and a.is_contiguous():
+            return a
+        key = (str(device), a.data_ptr(), a._version)
+        if key not in self._on_device:
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('FeatureAnchor: first use on %s inside a graph capture; call it once eagerly'
+                                   % device)
+            self._on_device = {key: a.to(device, torch.float32).contiguous()}
+        return self._on_device[key]
+
+    def graph_key(self):
+        """what a captured step bakes in of this term (optimizer/base_optimizer.py `_graph_key`): the anchor's
+        address and version, the weight and the shape"""
+        a = self.anchor
+        return ('FeatureAnchor', a.data_ptr(), a._version, self.weight, tuple(a.shape))
+
+    def __call__(self, f):
+        return feature_anchor(f, self._device_anchor(f.device), self.weight)
+
+
+# ---------------------------------------------------------------------------
 # `lpips_size`: the LPIPS term on an area-pooled image (the StyleGAN2 projector's 256^2; DESIGN.md section 12)
 # ---------------------------------------------------------------------------
 POOL_FACTORS = (1, 2, 4, 8, 16)

@@ -9,11 +9,17 @@ search), `im_res`.  The arithmetic is libp2l_hip (`p2l_sg2_mapping_*`,
 extensions.  Generator parameters are frozen: gradients go to the latents and, in w+
 search, to the noise inputs.
 
+Not in the reference: `search='f'` (feature-space / F/W+ inversion) optimises the activation at
+`f_res` -- `feat`, with the partial RGB `skip` -- next to the W+ rows and noise maps of the layers above it:
+`features(z, noises)` captures both out of a W+ forward, `forward_f` / `__call__(z, noises, feat=, skip=)` run the
+synthesis from there (`p2l_sg2_synthesis_from_*`), `feature_cut` is the arithmetic of the cut.
+
 Weights: `$P2L_STYLEGAN2_<MODEL>_WEIGHTS` (a torch-loadable rosinality checkpoint with a
 'g_ema' entry) if set, else seeded random-init tensors of the same architecture (no
 network access here).  As in the reference, z-search draws fresh per-layer noise on
 every forward unless `noises` is given.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -75,6 +81,89 @@ class _SynthFn(torch.autograd.Function):
         return dlatent, dnoise, None, None
 
 
+class _SynthFromFn(torch.autograd.Function):
+    """(latent [B, n_latent, 512], layer-major noise, feat [B,C,r,r], skip [B,3,r,r]) -> image [B,3,S,S]: the
+    synthesis from the cut at resolution r on (p2l_sg2_synthesis_from_fwd / _bwd), in the lane workspace of _SynthFn
+    and under its stamp / stale check.  Each input gets a gradient only when autograd asks for it."""
+
+    @staticmethod
+    def forward(ctx, latent, noise_lm, feat, skip, model, res):
+        B = latent.shape[0]
+        latent = latent.contiguous().float()
+        noise_lm = noise_lm.contiguous().float()
+        feat = feat.contiguous().float()
+        skip = skip.contiguous().float()
+        lib, S = model._lib, model.im_res
+        s = model._ensure_ws(B)
+        N.check(lib.p2l_sg2_synthesis_from_fwd(C.byref(model._desc), res, N.ptr(feat), N.ptr(skip), N.ptr(latent),
+                                               N.ptr(noise_lm), B, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                                               N.ptr(s.img16), N.stream()), 'p2l_sg2_synthesis_from_fwd')
+        out = torch.empty(B, 3, S, S, device=latent.device, dtype=torch.float32)
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.img16), N.ptr(out), B, S, S, N.stream()),
+                'p2l_nhwc16_to_nchw3')
+        ctx.model, ctx.stamp, ctx.res = model, model._scratch.stamp(), res
+        ctx.shapes = (feat.shape, skip.shape)
+        ctx.save_for_backward(latent, noise_lm)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        with lanes.use(ctx.stamp[0]):    # (the saved activations live in the forward's lane)
+            return _SynthFromFn._backward(ctx, dout)
+
+    @staticmethod
+    def _backward(ctx, dout):
+        model = ctx.model
+        latent, noise_lm = ctx.saved_tensors
+        if model._scratch.stale(ctx.stamp):
+            raise N.NativeError('StyleGAN2 workspace was reused by a later forward before '
+                                'backward(); use one model object per in-flight graph')
+        s = model._scratch.here()
+        B, S, lib = latent.shape[0], model.im_res, model._lib
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(dout.contiguous().float()), N.ptr(s.dimg16), B, S,
+                                        S, N.stream()), 'p2l_nchw3_to_nhwc16')
+        need = ctx.needs_input_grad
+        # (the library always writes dlatent: the style gradients are what the pass reduces into)
+        dlatent = torch.empty_like(latent)
+        dnoise = torch.empty_like(noise_lm) if need[1] else None
+        dfeat = torch.empty(ctx.shapes[0], device=latent.device, dtype=torch.float32) if need[2] else None
+        dskip = torch.empty(ctx.shapes[1], device=latent.device, dtype=torch.float32) if need[3] else None
+        N.check(lib.p2l_sg2_synthesis_from_bwd(C.byref(model._desc), ctx.res, N.ptr(latent), N.ptr(noise_lm), B,
+                                               N.ptr(s.ws), C.c_size_t(s.ws_bytes), N.ptr(s.dimg16),
+                                               N.ptr(dlatent), N.ptr(dnoise), N.ptr(dfeat), N.ptr(dskip),
+                                               N.stream()), 'p2l_sg2_synthesis_from_bwd')
+        return (dlatent if need[0] else None), dnoise, dfeat, dskip, None, None
+
+
+FeatureCut = collections.namedtuple('FeatureCut', 'l0 j0 C rows noise_off')
+
+
+def feature_cut(size, res, channels=None):
+    """The cut of the feature-space (F/W+) run of a generator of size `size` at resolution `res` (a power of two,
+    4 <= res <= size / 2; ValueError otherwise) -- host arithmetic, no device:
+        l0        the first styled conv that still runs, 2 (log2 res - 2) + 1: the up conv to 2 res
+        j0        the last ToRGB that no longer runs, log2 res - 2
+        C         channels of the activation at res (`channels`: {resolution: width}, default the width table
+                  of the released models)
+        rows      the W+ rows the run reads (conv l reads row l, ToRGB j row 2 j + 1)
+        noise_off the first element of a candidate's flat noise vector the run reads (sum of h w of conv[0 .. l0-1])
+    The run reads feat = y[l0 - 1] and skip = skip[j0]; the W+ rows outside `rows` and the noise in front of
+    `noise_off` are not read and get zero gradients."""
+    size, r = int(size), int(res)
+    if r != res or r < 4 or r & (r - 1) or size < 8 or size & (size - 1) or r > size // 2:
+        raise ValueError('feature cut of a %s^2 generator at %s: the resolution is a power of two in 4 .. %d'
+                         % (size, res, size // 2))
+    k, log_size = r.bit_length() - 1, size.bit_length() - 1
+    j0 = k - 2
+    l0 = 2 * j0 + 1
+    n_conv, n_rgb = 2 * (log_size - 2) + 1, log_size - 1
+    rows = sorted(set(range(l0, n_conv)) | set(2 * j + 1 for j in range(j0 + 1, n_rgb)))
+    noise_off = sum((4 if l == 0 else 2 ** ((l + 1) // 2 + 2)) ** 2 for l in range(l0))
+    widths = dict(synthetic.sg2_channels())
+    widths.update(channels or {})
+    return FeatureCut(l0, j0, int(widths[r]), rows, noise_off)
+
+
 class _NoiseLayoutFn(torch.autograd.Function):
     """noises [B, noise_total] (the reference's variable, model/stylegan2.py:128-138 slices it per layer) ->
     layer-major flat vector for the synthesis entry points; one launch each way (p2l_sg2_noise_relayout)
@@ -128,8 +217,10 @@ class _MappingFn(torch.autograd.Function):
 
 class StyleGAN2(nn.Module):
     def __init__(self, model='cars', search='z', weights=None, size=None, device='cuda', seed=0,
-                 wfmt=None):
+                 wfmt=None, f_res=32):
         super(StyleGAN2, self).__init__()
+        if search == 'f':
+            feature_cut(size if size is not None else IM_DIM[model], f_res)      # (ValueError for a bad f_res)
         self._dev = torch.device(device)
         if self._dev.type != 'cuda':
             raise N.NativeError('StyleGAN2 needs a ROCm device: the generator only exists as HIP '
@@ -153,6 +244,7 @@ class StyleGAN2(nn.Module):
         self._scratch = lanes.Scratch()      # arena + image staging per lane (one per stream)
         self._pack(weights)
         self.search = search
+        self.f_res = int(f_res) if search == 'f' else None
         with torch.no_grad():
             n_mean_latent = 4096
             g = torch.Generator(device='cpu').manual_seed(seed + 1)
@@ -160,7 +252,7 @@ class StyleGAN2(nn.Module):
             latent_out = self.mapping(zs)
             if search == 'z':
                 self.mean_latent = latent_out.mean(0, keepdim=True)
-            elif search == 'w+':
+            elif search in ('w+', 'f'):
                 self.latent_mean = latent_out.mean(0)
                 latent_std = (latent_out - self.latent_mean).pow(2).sum()
                 self.latent_std = (latent_std / n_mean_latent) ** 0.5
@@ -192,6 +284,7 @@ class StyleGAN2(nn.Module):
         d.const_input = self._t(W['input.input'][0].permute(1, 2, 0))
         names = ['conv1'] + ['convs.%d' % i for i in range(2 * (log_size - 2))]
         self.noise_shape = []
+        self._widths = {}
         noise_off = 0
         for l, nm in enumerate(names):
             c = d.conv[l]
@@ -201,6 +294,7 @@ class StyleGAN2(nn.Module):
             res = 4 if l == 0 else 2 ** ((l + 1) // 2 + 2)
             ws = w / math.sqrt(cin * 9)
             c.cin, c.cout, c.up, c.res = cin, cout, int(up), res
+            self._widths[res] = cout
             c.w = self._pack_w(ws, 9, cout, cin, False, subpix=up)
             c.wt = self._pack_w(ws, 9, cin, cout, True, subpix=up)
             c.wsq = self._t((ws ** 2).sum((2, 3)).t())            # [cin][cout]
@@ -256,6 +350,11 @@ class StyleGAN2(nn.Module):
         n = shape[0] * shape[1] * shape[2] * shape[3]
         return self._scratch.here().ws[off.value:off.value + n].view(*list(shape))
 
+    def saved_skip(self, j, B):
+        """test hook: view of the unclamped partial RGB behind ToRGB `j` inside the workspace of the last synthesis
+        forward on B candidates, NHWC16 (3 real channels)"""
+        return self.saved_activation(1000 + j, B)          # (P2L_SG2_WS_SKIP, include/p2l_test.h)
+
     # -------------------------------------------------------------- pieces
     def mapping(self, z):
         """PixelNorm + 8 EqualLinear/fused-lrelu layers: z [B,512] -> w [B,512]"""
@@ -276,10 +375,73 @@ class StyleGAN2(nn.Module):
         return _SynthFn.apply(latent, noise_lm, self, want_dnoise)
 
     # ------------------------------------------------------------- public API
-    def __call__(self, z, noises=None, truncation=1.0):
+    def __call__(self, z, noises=None, truncation=1.0, feat=None, skip=None):
+        if self.search == 'f':
+            return self.forward_f(z, noises, feat, skip)
+        if feat is not None or skip is not None:
+            raise ValueError("feat / skip are the inputs of search='f'; this model searches %r" % (self.search,))
         if self.search == 'w+':
             return self.forward_w(z, noises)
         return self.forward_z(z, noises=noises)
+
+    class _CutMethod(object):
+        """`model.feature_cut(res)`: the cut of THIS generator (C, the W+ rows and the noise offset come from its
+        descriptor); `StyleGAN2.feature_cut(size, res, channels=None)`: the same arithmetic without a model or a
+        device (the module's `feature_cut`)."""
+
+        def __get__(self, obj, cls):
+            return feature_cut if obj is None else obj._feature_cut
+
+    feature_cut = _CutMethod()
+
+    def _feature_cut(self, res):
+        cut = feature_cut(self.im_res, res, self._widths)
+        d = self._desc
+        rows = sorted(set(d.conv[l].latent_idx for l in range(cut.l0, d.n_conv)) |
+                      set(d.rgb[j].latent_idx for j in range(cut.j0 + 1, d.n_rgb)))
+        return FeatureCut(cut.l0, cut.j0, d.conv[cut.l0].cin, rows, d.conv[cut.l0].noise_off)
+
+    def _feat_shapes(self, B, res):
+        return (B, self._feature_cut(res).C, res, res), (B, 3, res, res)
+
+    def features(self, z, noises, res=None):
+        """(feat [B,C,r,r], skip [B,3,r,r]) of the W+ latents z and the flat noises at resolution `res` (default
+        `f_res`): the activation behind the plain styled conv at r and the unclamped partial RGB there, as
+        `forward_f` takes them.  One full forward under no_grad, then p2l_sg2_capture: the results are copies,
+        not views of the workspace."""
+        res = self.f_res if res is None else res
+        if res is None:
+            raise ValueError('features: give res (the model was not built with search=\'f\')')
+        B = z.shape[0]
+        fs, ss = self._feat_shapes(B, res)
+        with torch.no_grad():
+            self.forward_w(z.detach().to(self._dev), noises.detach())
+            s = self._scratch.here()
+            feat = torch.empty(fs, device=self._dev, dtype=torch.float32)
+            skip = torch.empty(ss, device=self._dev, dtype=torch.float32)
+            N.check(self._lib.p2l_sg2_capture(C.byref(self._desc), int(res), B, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
+                                              N.ptr(feat), N.ptr(skip), N.stream()), 'p2l_sg2_capture')
+        return feat, skip
+
+    def forward_f(self, z, noises, feat, skip, res=None):
+        """the synthesis from resolution r = `f_res` on: z [B, n_latent, 512] (or [B,512]) W+ latents, of which the
+        rows `feature_cut(r).rows` are read; noises [B, sum(h*w)] flat, read from `feature_cut(r).noise_off` on;
+        feat [B,C,r,r] the activation at r and skip [B,3,r,r] the partial RGB there (`features`).  Gradients go to
+        all four; what is not read gets zeros."""
+        res = self.f_res if res is None else res
+        if res is None:
+            raise ValueError('forward_f: give res (the model was not built with search=\'f\')')
+        B = z.shape[0]
+        fs, ss = self._feat_shapes(B, res)
+        if feat is None or skip is None or tuple(feat.shape) != fs or tuple(skip.shape) != ss:
+            raise ValueError("search='f' at resolution %d takes feat %s and skip %s, got %s and %s"
+                             % (res, list(fs), list(ss), None if feat is None else list(feat.shape),
+                                None if skip is None else list(skip.shape)))
+        if noises is None:
+            raise ValueError("search='f' takes the flat noises [B, %d]" % self._desc.noise_total)
+        latent = z if z.dim() == 3 else z.unsqueeze(1).expand(-1, self._desc.n_latent, -1)
+        noise_lm = _NoiseLayoutFn.apply(noises.to(self._dev), self)
+        return _SynthFromFn.apply(latent, noise_lm, feat.to(self._dev), skip.to(self._dev), self, int(res))
 
     def forward_z(self, z, truncation=1.0, noises=None):
         """generator([z], truncation=1.0).clamp_(-1, 1); `noises` (list of [B,1,h,w]) makes

@@ -535,3 +535,48 @@ def latent_prior_bwd(w, basis, layer_w, p_space, ws, gloss=None):
                                         N.ptr(gloss), B, L, D, K, int(bool(p_space)), C.c_void_p(ws.data_ptr()),
                                         ws.numel() * 8, N.ptr(dw), N.stream()), 'p2l_latent_prior_bwd')
     return dw
+
+
+# ---- feature-space inversion: layout transposes and the anchor term (csrc/p2l_sg2_feat.hip) ----
+def nhwc_to_nchw(x):
+    """[B, H, W, C] fp32 device tensor -> a new [B, C, H, W] one (p2l_nhwc_to_nchw)"""
+    B, H, W, Cn = x.shape
+    out = torch.empty(B, Cn, H, W, device=x.device, dtype=torch.float32)
+    N.check(_lib().p2l_nhwc_to_nchw(N.ptr(x), N.ptr(out), B, Cn, H, W, N.stream()), 'p2l_nhwc_to_nchw')
+    return out
+
+
+def nchw_to_nhwc(x):
+    """[B, C, H, W] fp32 device tensor -> a new [B, H, W, C] one (p2l_nchw_to_nhwc)"""
+    B, Cn, H, W = x.shape
+    out = torch.empty(B, H, W, Cn, device=x.device, dtype=torch.float32)
+    N.check(_lib().p2l_nchw_to_nhwc(N.ptr(x), N.ptr(out), B, Cn, H, W, N.stream()), 'p2l_nchw_to_nhwc')
+    return out
+
+
+def _anchor_stride(f, anchor):
+    n = f[0].numel()
+    if anchor.numel() == n:
+        return 0
+    assert anchor.numel() == f.numel(), 'the anchor has the shape of one candidate or of all of them'
+    return n
+
+
+def feature_anchor_fwd(f, anchor, weight):
+    """f [B, ...] fp32 device, anchor of the shape of f[0] (shared) or of f -> loss [B] fp32"""
+    B, n = f.size(0), f[0].numel()
+    ws = torch.empty(max(_lib().p2l_feature_anchor_ws_bytes(B, n) // 8, 1), dtype=torch.float64, device=f.device)
+    loss = torch.empty(B, dtype=torch.float32, device=f.device)
+    N.check(_lib().p2l_feature_anchor_fwd(N.ptr(f), N.ptr(anchor), _anchor_stride(f, anchor), B, n, float(weight),
+                                          N.ptr(loss), C.c_void_p(ws.data_ptr()), ws.numel() * 8, N.stream()),
+            'p2l_feature_anchor_fwd')
+    return loss
+
+
+def feature_anchor_bwd(f, anchor, weight, gloss=None):
+    """gloss [B] (None = ones) times d loss / d f, of the shape of f"""
+    B, n = f.size(0), f[0].numel()
+    df = torch.empty_like(f)
+    N.check(_lib().p2l_feature_anchor_bwd(N.ptr(f), N.ptr(anchor), _anchor_stride(f, anchor), N.ptr(gloss), B, n,
+                                          float(weight), N.ptr(df), N.stream()), 'p2l_feature_anchor_bwd')
+    return df
