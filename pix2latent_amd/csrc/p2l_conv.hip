@@ -1021,6 +1021,11 @@ int choose_tile(const P2LConv* d, ConvK& k) {
   int TH = 128 / TW;
   if (TH > npow2(gH)) TH = npow2(gH);
   int TB = 128 / (TW * TH);
+  // The staging loops of the 3x3 / sub-pixel kernels cover 5 x 64 patch rows (A_ITERS = 5).  The 2-wide and 2-high
+  // grids of the sub-pixel forms (H or W = 4) asked for more -- 32 images x 16 rows on the 2x2 grid -- and the rows
+  // behind the 320th were never staged: the images from the 21st of a tile on read whatever the LDS held.  Taller
+  // tiles with fewer images instead (partial in y); no stride-1 shape and no larger grid comes near the limit.
+  while (TB > 1 && TB * (TH + 2) * (TW + 2) > 320) { TH <<= 1; TB >>= 1; }
   k.tw_log = ilog2(TW);
   k.th_log = ilog2(TH);
   k.tb_log = ilog2(TB);
@@ -1481,6 +1486,18 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
         (arb->x_ld % 4 || (arb->skip && arb->skip_ld % 4)))
       return P2L_EINVAL;
   }
+  // sub-pixel launches: what the form does not take is refused HERE -- a launch refused behind the profiler's slot
+  // left its event pair half recorded, and p2l_prof_totals then failed for the whole profiled section
+  const int sk3 = (d->ups >= 2 && d->taps == 9 && d->splitk > 1) ? ((d->ups == 3 && d->ext) ? effective_splitk(d) : 1) : 1;
+  // a 3x3 / sub-pixel block stages at most A_ITERS x 64 = 320 patch rows: choose_tile keeps every tile inside that, and
+  // a tiling that did not would read unstaged LDS without any sign of it -- refused, loudly
+  if (d->taps == 9 && (1 << k.tb_log) * ((1 << k.th_log) + 2) * ((1 << k.tw_log) + 2) > 5 * 64) return P2L_EUNSUP;
+  if (d->ups >= 2) {
+    if (sk3 > 1 && !(use_h2 && direct_h2(d))) return P2L_EWS;
+    if (d->taps != 9 || (k.splitk != 1 && sk3 == 1) || d->Cin % 16 || d->pool != P2L_POOL_NONE ||
+        (arb && k.tb_log != 0 && sk3 == 1) || (d->ups == 2 && (res || mask)))
+      return P2L_EUNSUP;
+  }
   hipStream_t st = (hipStream_t)stream;
 
   int prof_slot = -1;
@@ -1619,11 +1636,7 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     // K slices: the input-gradient form of a transposed conv in the fp16 x 2 kernel only (subpix_bwd_split);
     // the fused modulation / activation backward of a sliced launch runs in the finish kernel, per quad,
     // so multi-image tiles are no obstacle there
-    const int sk3 = (d->taps == 9 && d->splitk > 1) ? ((d->ups == 3 && d->ext) ? effective_splitk(d) : 1) : 1;
-    if (sk3 > 1 && !(use_h2 && direct_h2(d))) return P2L_EWS;
-    if (d->taps != 9 || (k.splitk != 1 && sk3 == 1) || d->Cin % 16 || d->pool != P2L_POOL_NONE ||
-        (arb && k.tb_log != 0 && sk3 == 1) || (d->ups == 2 && (res || mask)))
-      return P2L_EUNSUP;
+    // (what this form does not take was refused above, in front of the profiler's slot)
     {
       int gH, gW;
       grid_dims(d, gH, gW);

@@ -20,7 +20,8 @@ _RECORDS = []
 # test module -> the environment variable that names its record file (profiles/*_kernels_err.txt)
 _ERR_FILE_ENV = {'test_small_kernels_gpu': 'P2L_SMALL_ERR_FILE', 'test_loss_kernels_gpu': 'P2L_LOSS_ERR_FILE',
                  'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE', 'test_pw_kernels_gpu': 'P2L_PW_ERR_FILE',
-                 'test_wino_kernels_gpu': 'P2L_WINO_ERR_FILE', 'test_direct_kernels_gpu': 'P2L_DIRECT_ERR_FILE'}
+                 'test_wino_kernels_gpu': 'P2L_WINO_ERR_FILE', 'test_direct_kernels_gpu': 'P2L_DIRECT_ERR_FILE',
+                 'test_subpix_kernels_gpu': 'P2L_SUBPIX_ERR_FILE'}
 
 
 class _Native(object):

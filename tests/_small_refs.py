@@ -5,7 +5,9 @@ float64 (`vjp`).  Everything runs on torch-CPU.  tests/test_small_refs.py checks
 independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kernels_gpu.py,
 tests/test_glue_kernels_gpu.py, tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
 restatements, host packers and the case tables) and tests/test_wino_kernels_gpu.py (the Winograd 3x3 routes: the
-same) and tests/test_direct_kernels_gpu.py (the direct 3x3 routes, ups 0 / 1: the same) hold the kernels to them.  (The closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
+same), tests/test_direct_kernels_gpu.py (the direct 3x3 routes, ups 0 / 1: the same) and
+tests/test_subpix_kernels_gpu.py (the sub-pixel routes, ups 2 / 3: the same) hold the kernels to them.  (The
+closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
 Layouts are those of the ABI: activations NHWC, images NHWC16 (3 channels in 16 floats), targets / weights NCHW3.
@@ -1520,7 +1522,10 @@ def direct_tile(H, W):
     rest images"""
     TW = min(npow2(W), 16)
     TH = min(128 // TW, npow2(H))
-    return TW, TH, 128 // (TW * TH)
+    TB = 128 // (TW * TH)
+    while TB > 1 and TB * (TH + 2) * (TW + 2) > 320:      # (the 320 patch rows a block stages: 2-wide / 2-high grids)
+        TH, TB = 2 * TH, TB // 2
+    return TW, TH, TB
 
 
 def direct_cols(a):
@@ -1773,6 +1778,556 @@ def direct_arb_refs(c, i):
     split = len(splitk_slices(9 * c['Cin'], 144, c['splitk'])) > 1
     r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], split)
     return r64, r32
+
+
+# ---- sub-pixel 3x3 convs, ups 2 / 3 (tests/test_subpix_kernels_gpu.py) ------------------------------------------------
+# The four modes of a taps = 9 launch with P2LConv.ups >= 2 (include/p2l.h): ups = 2 the forward conv on the low-
+# resolution x [B, H/2, W/2, Cin] -- ext = 0: the 3x3 conv of its nearest x 2 upsample, ext = 1: the stride-2 transposed
+# conv, written into a [B, H+2, W+2, *] frame -- and ups = 3 its input gradient, from the high-resolution gradient (ext =
+# 1: the frame, row / column H+1 zero) to [B, H/2, W/2, Cout].  H, W are the HIGH-resolution dims of the descriptor, Cin
+# -> Cout those of the launch, and a case's weight is always the FORWARD conv's OIHW tensor: [Cout, Cin, 3, 3] for ups
+# = 2, [Cin, Cout, 3, 3] for ups = 3 (packed through transpose_flip).  Routes: F conv_mfma_kernel<4, .., BF3 = false>
+# (P2L_WFMT_F32), B the same kernel in bf16 x 3 (wfmt 'bf3': P2L_WFMT_BF16X3; 'bf3w': P2L_WFMT_BF16X3W with
+# P2L_FORM_WINO_BF3; 'nows': P2L_WFMT_BF16X3W without the 256 B per image of workspace), H conv_h2_kernel<4, ..> (fp16 x
+# 2, P2L_FORM_NO_SP_PAIR on a forward launch), P conv_h2_kernel<8, ..> (ups = 2: P2L_FORM_SP_PAIR, or pair = 'own': by
+# the launcher's own rule, ext = 1 with 64-channel tiles).
+FORM_NO_SP_SKIP, FORM_NO_SP_PAIR, FORM_SP_PAIR = 1024, 2048, 4096
+
+# sp_tapset of csrc/p2l_conv.hip restated: (mode, flip) -> [p: phase | plane parity][i: window tap] -> the original taps
+# (dy, or dx) whose weights the slab sums along that dimension (tests/test_small_refs.py ties it to the definition)
+SP_TAPS = {
+    (0, 0): (((0,), (1, 2)), ((0, 1), (2,))),
+    (0, 1): (((1, 2), (0,)), ((2,), (0, 1))),
+    (1, 0): (((2,), (0,)), ((1,), ())),
+    (1, 1): (((0,), (2,)), ((), (1,))),
+}
+
+
+def subpix_slabs(w, mode, flip):
+    """the 16 (phase | plane, window tap) weight slabs of pack_subpix_kernel from the forward conv's OIHW w, in the
+    dtype of w: slab 4 p + t with p = 2 py + px, t = 2 i + j sums w[.., dy, dx] over SP_TAPS[py][i] x SP_TAPS[px][j]
+    onto 0 in the kernel's dy-outer / dx-inner order (fp32: its pack-time roundings) -> [16, N, K]; flip (the input
+    gradient): N, K = I, O"""
+    src = w.permute(1, 0, 2, 3) if flip else w
+    T = SP_TAPS[(mode, int(bool(flip)))]
+    out = []
+    for ph in range(4):
+        for tap in range(4):
+            v = torch.zeros(src.shape[:2], dtype=w.dtype)
+            for dy in range(3):
+                for dx in range(3):
+                    if dy in T[ph >> 1][tap >> 1] and dx in T[ph & 1][tap & 1]:
+                        v = v + src[:, :, dy, dx]
+            out.append(v)
+    return torch.stack(out)
+
+
+def subpix_windows(a, ups, ext):
+    """the 2x2 windows the kernels read, per phase (ups = 2: a the low-resolution [B, h, w, K] after the prologue,
+    zero outside) or phase plane (ups = 3: a the high-resolution gradient [B, H + 2 ext, W + 2 ext, K]) -> four
+    [B, gh, gw, 4, K].  Read off the staging and the fragment addressing of conv_mfma_kernel<4, ..> / conv_h2_kernel:
+    a patch line holds low-resolution rows y0 - 1 .., window tap (i, j) of grid point (p, q) reads patch row p + oy + i:
+    phase (py, px) pixel (p - 1 + py + i, q - 1 + px + j) of x; plane (cy, cx) -- oy = 1 - cy -- pixel (p - cy + i, q -
+    cx + j) of the plane, i.e. row 2 (p - cy + i) + cy of the frame"""
+    out = []
+    if ups == 2:
+        h, w = a.shape[1:3]
+        gh, gw = h + ext, w + ext
+        ap = F.pad(a, (0, 0, 1, 1 + ext, 1, 1 + ext))
+        for ph in range(4):
+            py, px = ph >> 1, ph & 1
+            out.append(torch.stack([ap[:, py + i:py + i + gh, px + j:px + j + gw] for i in (0, 1) for j in (0, 1)], dim=3))
+        return out
+    for cls in range(4):
+        cy, cx = cls >> 1, cls & 1
+        pl = a[:, cy::2, cx::2]
+        h, w = pl.shape[1] - ext, pl.shape[2] - ext
+        ap = F.pad(pl, (0, 0, 1, 1, 1, 1))
+        out.append(torch.stack([ap[:, 1 - cy + i:1 - cy + i + h, 1 - cx + j:1 - cx + j + w]
+                                for i in (0, 1) for j in (0, 1)], dim=3))
+    return out
+
+
+def subpix_cols(win):
+    """[B, gh, gw, 4, K] -> [B, gh, gw, 4 K] in the kernels' K order: 16-channel chunk, window tap, channel"""
+    B, gh, gw, _, K = win.shape
+    return win.reshape(B, gh, gw, 4, K // 16, 16).permute(0, 1, 2, 4, 3, 5).reshape(B, gh, gw, 4 * K)
+
+
+def subpix_wmat(slabs4):
+    """the four slabs [4, N, K] of one phase | plane -> [N, 4 K] in subpix_cols' order"""
+    _, N, K = slabs4.shape
+    return slabs4.reshape(4, N, K // 16, 16).permute(1, 2, 0, 3).reshape(N, 4 * K)
+
+
+def subpix_map(a, w, ups, ext):
+    """the plain linear map of the four modes in the dtype of a, from the definitions alone -- nothing here knows
+    phases, planes or slabs.  w: the forward conv's [O, I, 3, 3].  ups = 2, ext = 0: zero pad and 3x3 of the nearest
+    x 2 of a [B, h, w, I]; ext = 1: conv_transpose2d(stride 2) -- out[2 p + k] += a[p] w[k] -- in rows / columns 0 .. H
+    of a [B, H + 2, W + 2, O] frame, row / column H + 1 zero.  ups = 3: the vjp of that forward at the gradient a [B,
+    H + 2 ext, W + 2 ext, O] -> [B, h, w, I]"""
+    nchw = lambda v: v.permute(0, 3, 1, 2)
+    if ups == 2:
+        if not ext:
+            return F.conv2d(nchw(up2(a)), w, padding=1).permute(0, 2, 3, 1)
+        u = F.conv_transpose2d(nchw(a), w.transpose(0, 1), stride=2).permute(0, 2, 3, 1)
+        return F.pad(u, (0, 0, 0, 1, 0, 1))
+    B, Hf, Wf, _ = a.shape
+    z = torch.zeros(B, (Hf - 2 * ext) // 2, (Wf - 2 * ext) // 2, w.shape[1], dtype=a.dtype)
+    return vjp(lambda z_: subpix_map(z_, w, 2, ext), [z], a)
+
+
+def subpix_h2_wmax(w):
+    """what p2l_pack_conv_weight_subpix_h2 records in its tail and scales every slab by: 4 max |w| over the OIHW
+    tensor (h2_tail_x4_kernel: a slab sums up to four taps) -- a bound of the slabs, not their maximum"""
+    return 4.0 * w.abs().max()
+
+
+def subpix_h2_floor(aabs, w, ups, ext, amax, wmax):
+    """direct_h2_floor for the sub-pixel forms, fp64 at the output's shape: 2^-13 (amax_b sum |w| + wmax sum |a|), both
+    sums over the original taps and channels that reach the output from a real input position (subpix_map of ones).
+    aabs: the prologue's absolute values (ups = 3: |gradient|), amax [B] the maxima the kernel scales by, wmax the pack
+    tail (subpix_h2_wmax)"""
+    xa, wa = aabs.double(), w.double().abs()
+    one_a = torch.ones_like(xa[:1])
+    if ups == 3 and ext:
+        one_a[:, -1], one_a[:, :, -1] = 0.0, 0.0
+    one_w = torch.ones_like(wa[:1]) if ups == 2 else torch.ones_like(wa[:, :1])
+    return 2.0 ** -13 * (amax.double().view(-1, 1, 1, 1) * subpix_map(one_a, wa, ups, ext) +
+                         float(wmax) * subpix_map(xa, one_w, ups, ext))
+
+
+def subpix_acc32(c, i, route=None):
+    """the fp32 restatement of a route's accumulator in front of alpha and the epilogue, read off the loops of
+    conv_mfma_kernel<4, ..> (csrc/p2l_conv.hip) and conv_h2_kernel<4 | 8, ..> (csrc/p2l_h2.hip).  Weights: the fp32 slab
+    sums of pack_subpix_kernel / h2_pack_kernel (subpix_slabs).  Forward (blockIdx.y = the phase; TAPS = 8: two phases,
+    two accumulator sets, the same order per output): `for c in chunks` of 16 channels outside, the unrolled window taps
+    u / NT (0 .. 3) inside, 16 channels per MFMA group -- per phase the columns (chunk, tap, channel) of subpix_cols,
+    written to pixels (2 p + py, 2 q + px) of the [2 gh, 2 gw] buffer.  Gradient: chunk c = (plane cls = c / sp_ncc,
+    channel chunk c % sp_ncc) -- `geom` -- with wslab = 4 cls: plane, chunk, tap, channel; K slices cut that chunk
+    sequence by chunks_per_split = cdiv(4 Cin / 16, sk) (splitk_slices on chunks of 64 columns) and meet in the finish
+    kernels' order (combine_slices).  The skipped taps of ext = 1 are zero slabs: their products add +0.  Accumulators:
+    acc_fp32 / acc_bf3 / acc_h2 with chunks of 4 x 16 columns; fp16 x 2 scales by the per-image maxima of pw_amax and
+    by the pack tail subpix_h2_wmax"""
+    route = route or c['route']
+    ups, ext = c['ups'], c['ext']
+    a = pw_prologue(i['x'], c['pro'], i.get('s'), i.get('t'))[0] if ups == 2 else i['x']
+    slabs = subpix_slabs(i['w'], ext, ups == 3)
+    wins = subpix_windows(a, ups, ext)
+
+    def acc(cols, wm, sk):
+        if route == 'F':
+            return acc_fp32(cols, wm, sk, 64)
+        if route == 'B':
+            return acc_bf3(cols, wm, sk, 64)
+        return acc_h2(cols, wm, pw_amax(c, i)[1], subpix_h2_wmax(i['w']), sk, 64)
+    if ups == 2:
+        B, gh, gw = wins[0].shape[:3]
+        out = torch.zeros(B, 2 * gh, 2 * gw, slabs.shape[1])
+        for ph in range(4):
+            out[:, ph >> 1::2, ph & 1::2] = acc(subpix_cols(wins[ph]), subpix_wmat(slabs[4 * ph:4 * ph + 4]), 1)
+        return out
+    cols = torch.cat([subpix_cols(wn) for wn in wins], dim=-1)
+    wm = torch.cat([subpix_wmat(slabs[4 * cls:4 * cls + 4]) for cls in range(4)], dim=-1)
+    return acc(cols, wm, c['splitk'])
+
+
+def subpix_slices(c):
+    """the (plane, chunk) slices of a ups = 3 launch as column ranges of the 16 Cin columns"""
+    return splitk_slices(16 * c['Cin'], 64, c['splitk']) if c['ups'] == 3 else [(0, 4 * c['Cin'])]
+
+
+def subpix_k(c, route=None, pooled=False):
+    """the bar's k of a sub-pixel case, counted like direct_k.  Columns onto one accumulator: forward 4 window taps x
+    Cin per phase, gradient 4 planes x 4 taps x Cin, the deepest K slice of it (whole (plane, chunk) chunks of 64
+    columns) -- F a product and an addition (2), B six cross terms, H / P three per column; the slices in the finish
+    kernels' order (slices - 1); B: pieces 2 + dropped terms 2; H / P: pieces 8 + dropped term 4 + the floor in the
+    denominator 1.  The pack-time roundings of a summed slab, relative to sum |w_tap|: mode 0 (ext = 0) sums up to 2 x 2
+    taps in ONE chain of fp32 additions -- 3 roundings, forward and gradient alike (the first addition onto 0 is exact);
+    mode 1 (ext = 1) slabs are single taps: 0.  Then direct_k's prologue and epilogue terms"""
+    route = route or c['route']
+    sl = subpix_slices(c)
+    deep = max(hi - lo for lo, hi in sl)
+    k = {'F': 2, 'B': 6, 'H': 3, 'P': 3}[route] * deep + (len(sl) - 1) + {'F': 0, 'B': 4, 'H': 13, 'P': 13}[route]
+    k += 0 if c['ext'] else 3
+    k += (2 if c['pro'] != PRO_NONE else 0) + 1 + c['oscale'] + c['bias'] + 2 * c['noise'] + (c['res'] is not None)
+    if c['act'] == ACT_TANH:
+        k += 2
+    if c['act'] == ACT_LRELU_SQRT2:
+        k = 1.5 * k + 1
+    return k
+
+
+def subpix_bwd_split(H, W, Cin, Cout):
+    """subpix_bwd_split of csrc/p2l_conv.hip for a ups = 3, ext = 1 fp16 x 2 launch on whole tiles (H, W the high-
+    resolution dims, Cin the gradient's channels): 1 = unsliced"""
+    p2f = lambda v: 1 if v < 2 else 2 ** (int(v).bit_length() - 1)
+    hw = (H // 2) * (W // 2)
+    s = min(p2f(Cin * 16 // 128), p2f(524288 // (hw * Cout)), 4 if hw >= 256 else 8)
+    nchunks = 4 * (Cin // 16)
+    while s > 1 and nchunks // s < 8:
+        s //= 2
+    return 1 if s <= 2 else s
+
+
+def subpix_grid(c):
+    """(gh, gw) of the low-resolution grid the kernel tiles, and direct_tile of it"""
+    e = 1 if (c['ups'] == 2 and c['ext']) else 0
+    gh, gw = c['H'] // 2 + e, c['W'] // 2 + e
+    return (gh, gw), direct_tile(gh, gw)
+
+
+def _sc(route, ups, ext, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, ups=ups, ext=ext, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, pro=PRO_NONE, pro_b=1, alpha=1.0,
+             bias=False, res=None, mask=False, act=ACT_NONE, pool=POOL_NONE, want_y=True, oscale=False, noise=False,
+             n_store=Cout, splitk=1, amax=None, wfmt='bf3', pair='form', skip=True, finish='v4', t0=False,
+             cancel=False, relu_like=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def subpix_id(c):
+    d = _sc(c['route'], c['ups'], c['ext'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-u%de%d-%dx%dx%d-%dto%d' % (c['route'], c['ups'], c['ext'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + \
+        ''.join('-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+def subpix_form(c, route=None):
+    """-> (P2LConv.wfmt, P2LConv.form, with the fp16 x 2 share of the workspace) of a case on `route`"""
+    route = route or c['route']
+    noskip = 0 if c['skip'] else FORM_NO_SP_SKIP
+    if route == 'F':
+        return 0, 0, True
+    if route == 'B':
+        return {'bf3': (WFMT_BF16X3, 0, True), 'bf3w': (WFMT_BF16X3W, FORM_WINO_BF3, True),
+                'nows': (WFMT_BF16X3W, 0, False)}[c['wfmt']]
+    if route == 'H':
+        return WFMT_BF16X3W, noskip | (FORM_NO_SP_PAIR if c['ups'] == 2 else 0), True
+    assert c['ups'] == 2
+    return WFMT_BF16X3W, noskip | (FORM_SP_PAIR if c['pair'] == 'form' else 0), True
+
+
+# hi-res H x W, B, Cin, Cout of the launch: the smallest shapes that reach each path of choose_tile on the low-
+# resolution grid (ext = 1 forward: H/2 + 1 points, every tile partial)
+SUBPIX_SHAPES = {
+    '16x32': ((16, 32), 1, 16, 32),        # grid 8x16: one whole tile, A_ITERS = 3 | ext forward 9x17: four partial tiles
+    '32x32': ((32, 32), 2, 48, 64),        # grid 16x16: a seam in y | 17x17: four tiles, all partial
+    '16x64': ((16, 64), 1, 16, 96),        # grid 8x32: a seam in x
+    '8x8': ((8, 8), 3, 64, 32),            # grid 4x4: eight images per tile, A_ITERS = 5 | 5x5: two per tile, partial
+    '8x8b9': ((8, 8), 9, 16, 64),          # ... a second tile
+    '4x4': ((4, 4), 3, 16, 32),            # grid 2x2: the minimum choose_tile accepts | 3x3
+    '4x4b9': ((4, 4), 9, 16, 32),          # ... nine images: a second tile of eight
+    '16x16': ((16, 16), 2, 48, 96),        # grid 8x8: two images per tile | 9x9: TW = 16, two partial tile rows
+    'bn64': ((16, 32), 16, 16, 256),       # ups = 2: n64 = 16 tiles x 4 channel tiles x 4 phases = 256 -> BN = 64
+    'bn64e': ((16, 16), 8, 16, 256),       # ... ext = 1: grid 9x9, 2 tiles x 8 images x 4 x 4 = 256 -> BN = 64 unforced
+    '4x4b32': ((4, 4), 32, 16, 32),        # grid 2x2: 32 images -- one tile of 512 patch rows by the 128-pixel rule
+    's4': ((16, 16), 3, 128, 64),          # ups = 3, ext = 1: 4 K slices, two images per tile
+    's8': ((16, 16), 1, 256, 32),          # ... 8 slices
+    's4w': ((32, 32), 1, 256, 32),         # ... 4 slices (hw >= 256)
+    'bn64g': ((16, 32), 64, 16, 256),      # ups = 3: 64 tiles x 4 channel tiles = 256 -> BN = 64 (slots query only: 4.7 s)
+}
+
+
+def _ssh(route, ups, ext, name, **kw):
+    HW, B, Cin, Cout = SUBPIX_SHAPES[name]
+    return _sc(route, ups, ext, HW, B, Cin, Cout, **kw)
+
+
+# the epilogue terms of each mode (the issue's list): ups = 2, ext = 0 (BigGAN's conv_1) / ext = 1 (StyleGAN2's up conv)
+SP_EPI_E0 = [dict(bias=True, alpha=0.5), dict(pro=PRO_AFFINE_RELU), dict(pro=PRO_AFFINE_RELU, pro_b=0, act=ACT_RELU),
+             dict(pro=PRO_AFFINE, bias=True), dict(act=ACT_TANH)]
+SP_EPI_E1 = [dict(pro=PRO_AFFINE, t0=True), dict(pro=PRO_AFFINE), dict(pro=PRO_AFFINE_RELU, bias=True),
+             dict(pro=PRO_AFFINE, oscale=True, noise=True, bias=True, act=ACT_LRELU_SQRT2), dict(bias=True, alpha=0.5)]
+SP_EPI_G = [dict(), dict(res='same', mask=True), dict(act=ACT_TANH), dict(res='same', alpha=0.5), dict(act=ACT_RELU)]
+
+
+def _subpix_fwd(r, **rk):
+    e0, e1 = SP_EPI_E0, SP_EPI_E1
+    return [
+        _ssh(r, 2, 0, '16x32', **dict(rk, **e0[0])), _ssh(r, 2, 0, '32x32', **dict(rk, **e0[1])),
+        _ssh(r, 2, 0, '16x64', **dict(rk, **e0[2])), _ssh(r, 2, 0, '8x8', **dict(rk, **e0[3])),
+        _ssh(r, 2, 0, '8x8b9', **dict(rk, **e0[4])), _ssh(r, 2, 0, '4x4', **dict(rk, **e0[0])),
+        _ssh(r, 2, 0, '16x16', n_store=48, **dict(rk, **e0[1])), _ssh(r, 2, 0, '32x32', cancel=True, **rk),
+        _ssh(r, 2, 1, '8x8', **dict(rk, **e1[0])), _ssh(r, 2, 1, '16x16', **dict(rk, **e1[1])),
+        _ssh(r, 2, 1, '32x32', **dict(rk, **e1[2])), _ssh(r, 2, 1, '16x32', **dict(rk, **e1[3])),
+        _ssh(r, 2, 1, '8x8b9', **dict(rk, **e1[4])), _ssh(r, 2, 1, '4x4', **dict(rk, **e1[1])),
+        _ssh(r, 2, 1, '16x16', n_store=48, **dict(rk, **e1[2])),
+    ]
+
+
+def _subpix_bwd(r, **rk):
+    g = SP_EPI_G
+    return [
+        _ssh(r, 3, 0, '16x32', **dict(rk, **g[0])), _ssh(r, 3, 0, '32x32', n_store=48, **dict(rk, **g[1])),
+        _ssh(r, 3, 0, '16x64', **dict(rk, **g[2])), _ssh(r, 3, 0, '8x8', **dict(rk, **g[3])),
+        _ssh(r, 3, 0, '4x4', **dict(rk, **g[4])), _ssh(r, 3, 0, '32x32', cancel=True, **rk),
+        _ssh(r, 3, 1, '16x32', **dict(rk, **g[1])), _ssh(r, 3, 1, '32x32', **dict(rk, **g[0])),
+        _ssh(r, 3, 1, '8x8b9', **dict(rk, **g[2])), _ssh(r, 3, 1, '4x4', **dict(rk, **g[3])),
+        _ssh(r, 3, 1, '16x16', n_store=48, **dict(rk, **g[4])), _ssh(r, 3, 1, '16x64', **dict(rk, **g[0])),
+    ]
+
+
+SUBPIX_FWD_CASES = _subpix_fwd('F') + _subpix_fwd('B') + [
+    _ssh('B', 2, 0, '16x32', wfmt='bf3w', bias=True), _ssh('B', 2, 1, '16x16', wfmt='nows', pro=PRO_AFFINE),
+    # H: maxima from the pass in front (None), handed over (true / raw under a prologue), in_applied
+    _ssh('H', 2, 0, '16x32', amax='true', **SP_EPI_E0[0]), _ssh('H', 2, 0, '32x32', amax='raw', **SP_EPI_E0[1]),
+    _ssh('H', 2, 0, '16x64', amax='applied', **SP_EPI_E0[2]), _ssh('H', 2, 0, '8x8', **SP_EPI_E0[3]),
+    _ssh('H', 2, 0, '8x8b9', amax='true', **SP_EPI_E0[4]), _ssh('H', 2, 0, '4x4', **SP_EPI_E0[0]),
+    _ssh('H', 2, 0, '16x16', n_store=48, **SP_EPI_E0[1]), _ssh('H', 2, 0, '32x32', cancel=True),
+    _ssh('H', 2, 1, '8x8', **SP_EPI_E1[0]), _ssh('H', 2, 1, '16x16', amax='raw', **SP_EPI_E1[1]),
+    _ssh('H', 2, 1, '32x32', amax='applied', **SP_EPI_E1[2]), _ssh('H', 2, 1, '16x32', **SP_EPI_E1[3]),
+    _ssh('H', 2, 1, '8x8b9', amax='true', **SP_EPI_E1[4]), _ssh('H', 2, 1, '4x4', **SP_EPI_E1[1]),
+    _ssh('H', 2, 1, '16x16', n_store=48, skip=False, **SP_EPI_E1[2]),
+    # P: two phases per block by the form bit, and by the launcher's own rule (ext = 1, 64-channel tiles)
+    _ssh('P', 2, 0, '16x32', **SP_EPI_E0[0]), _ssh('P', 2, 0, '32x32', amax='raw', **SP_EPI_E0[1]),
+    _ssh('P', 2, 0, '8x8', **SP_EPI_E0[3]), _ssh('P', 2, 0, '4x4', **SP_EPI_E0[4]),
+    _ssh('P', 2, 0, 'bn64', bias=True),
+    _ssh('P', 2, 1, '8x8', **SP_EPI_E1[0]), _ssh('P', 2, 1, '16x16', **SP_EPI_E1[1]),
+    _ssh('P', 2, 1, '32x32', amax='applied', **SP_EPI_E1[2]), _ssh('P', 2, 1, '16x32', **SP_EPI_E1[3]),
+    _ssh('P', 2, 1, 'bn64e', pair='own', **SP_EPI_E1[0]),
+    # the 2x2 grid with 32 images: one 128-pixel tile would stage 32 x 16 = 512 patch rows, a block stages 320
+    _ssh('F', 2, 0, '4x4b32', bias=True), _ssh('H', 2, 0, '4x4b32', bias=True),
+]
+SUBPIX_BWD_CASES = _subpix_bwd('F') + _subpix_bwd('B') + [
+    _ssh('B', 3, 0, '16x32', wfmt='bf3w'), _ssh('B', 3, 1, '16x32', wfmt='nows'),
+    _ssh('H', 3, 0, '16x32', amax='true'), _ssh('H', 3, 0, '32x32', n_store=48, **SP_EPI_G[1]),
+    _ssh('H', 3, 0, '16x64', amax='true', **SP_EPI_G[2]), _ssh('H', 3, 0, '8x8', **SP_EPI_G[3]),
+    _ssh('H', 3, 0, '4x4', **SP_EPI_G[4]), _ssh('H', 3, 0, '32x32', cancel=True),
+    _ssh('H', 3, 1, '16x32', **SP_EPI_G[1]), _ssh('H', 3, 1, '32x32', amax='true', **SP_EPI_G[0]),
+    _ssh('H', 3, 1, '8x8b9', **SP_EPI_G[2]), _ssh('H', 3, 1, '4x4', **SP_EPI_G[3]),
+    _ssh('H', 3, 1, '16x16', n_store=48, skip=False, **SP_EPI_G[4]), _ssh('H', 3, 1, '16x64', **SP_EPI_G[0]),
+    _ssh('H', 3, 0, '4x4b9', **SP_EPI_G[2]), _ssh('H', 3, 1, '8x8', **SP_EPI_G[3]),
+    # K slices (ups = 3, ext = 1, fp16 x 2 only) through both finish kernels; s4: two images per tile
+    _ssh('H', 3, 1, 's4', splitk=4, **SP_EPI_G[1]), _ssh('H', 3, 1, 's8', splitk=8, **SP_EPI_G[0]),
+    _ssh('H', 3, 1, 's4w', splitk=4, amax='true', **SP_EPI_G[2]),
+    _ssh('H', 3, 1, 's4', splitk=4, finish='scalar', **SP_EPI_G[3]),
+    _ssh('H', 3, 1, 's8', splitk=8, skip=False, **SP_EPI_G[4]),
+    _ssh('F', 3, 0, '4x4b32'), _ssh('H', 3, 1, '4x4b32'),
+]
+
+
+def subpix_inputs(g, c):
+    """the operands of a case on the host, dense fp32: pw_inputs' draws (every image at a magnitude of its own; H, P:
+    the all-zero image of a batch of three, the quad 2^-20 below the maximum, the heavy channel under a prologue) with
+    direct_inputs' spread on top -- the first image x 1e-6, the last x 3e4: the images of one launch up to 3e14
+    apart.  ups = 2: x the low-resolution tensor, w [Cout, Cin, 3, 3]; PRO_AFFINE: |t| of 2 .. 5 units of the image
+    (t0: exactly 0, the launch the StyleGAN2 plan makes), so that a t at a padding position of the grid is far off;
+    noise on the frame the launch writes.  ups = 3: x the high-resolution gradient (ext: the [H+2, W+2] frame, row /
+    column H+1 zero), w the forward's [Cin, Cout, 3, 3], residual and mask at the low resolution.  cancel: weights
+    whose taps cancel inside the 2 x 2 slab {1, 2} x {1, 2} of mode 0 (phase (0, 0), window tap (1, 1); the gradient's
+    plane (0, 0), tap (0, 0)) the way fp32 cannot follow -- w[1][1] = b, w[2][1] = -b, w[1][2] and w[2][2] 2^-18 of b:
+    the chain b + w12 rounds w12 to ulp(b) before -b takes b away again, so the packed slab is off by 2^-6 of |sum
+    w_tap| and by 2^-24 of sum |w_tap| (two nearly opposite taps alone cancel exactly) -- on isolated input pixels, so
+    that outputs exist which that slab alone feeds"""
+    ups, ext, B, H, W, Cin, Cout = c['ups'], c['ext'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    h, w_ = H // 2, W // 2
+    rt = 'C' if c['route'] in 'HP' else 'A'
+    rn = lambda *sh: torch.randn(*sh, generator=g)
+    if ups == 2:
+        i = pw_inputs(g, dict(c, route=rt, H=h, W=w_, res=None, mask=False, noise=False))
+        i['w'] = rn(Cout, Cin, 3, 3) / math.sqrt(9 * Cin)
+    else:
+        Hf, Wf = H + 2 * ext, W + 2 * ext
+        i = pw_inputs(g, dict(c, route=rt, H=Hf, W=Wf, res=None, mask=False, noise=False))
+        if ext:
+            i['x'][:, Hf - 1], i['x'][:, :, Wf - 1] = 0.0, 0.0
+        i['w'] = rn(Cin, Cout, 3, 3) / math.sqrt(9 * Cin)
+    if c['relu_like']:
+        i['x'] = torch.relu(i['x'])
+    xmax = i['x'].abs().amax(dim=(1, 2, 3))
+    out_mag = torch.where(xmax > 0, mags(B), torch.ones(B)).view(B, 1, 1, 1)
+    if c['pro'] == PRO_AFFINE:
+        sign = torch.where(torch.rand(i['t'].shape, generator=g) < 0.5, -1.0, 1.0)
+        unit = xmax[:i['t'].shape[0]].view(-1, 1) if c['pro_b'] else xmax[xmax > 0].min()
+        i['t'] = sign * (2.0 + 3.0 * torch.rand(i['t'].shape, generator=g)) * 0.3 * unit
+        if c['t0']:
+            i['t'] = torch.zeros_like(i['t'])
+    if c['cancel']:
+        b = i['w'][:, :, 1, 1].clone()
+        i['w'][:, :, 2, 1] = -b
+        i['w'][:, :, 1, 2] = 2.0 ** -18 * b.abs() * rn(*b.shape)
+        i['w'][:, :, 2, 2] = 2.0 ** -18 * b.abs() * rn(*b.shape)
+        keep = torch.zeros_like(i['x'])
+        if ups == 2:
+            keep[:, 1::3, 1::3] = 1.0
+        else:
+            keep[:, 2::6, 2::6] = 1.0
+        i['x'] = i['x'] * keep
+    if c['noise']:
+        fr = (H + 2, W + 2) if (ups == 2 and ext) else ((H, W) if ups == 2 else (h, w_))
+        i['noise'], i['noise_w'] = rn(B, *fr) * out_mag[..., 0], 0.3
+    if c['res']:
+        i['res'] = rn(B, h, w_, Cout) * out_mag
+    if c['mask']:
+        i['mask'] = rn(B, h, w_, Cout)
+    if B >= 2 and (c['pro'] == PRO_NONE or c['pro_b']):
+        f = torch.ones(B)
+        f[0], f[B - 1] = 1e-6, 3e4
+        i['x'] = i['x'] * f.view(B, 1, 1, 1)
+        for name in ('t', 'res', 'noise'):
+            if name in i and torch.is_tensor(i[name]):
+                i[name] = i[name] * f.view([B] + [1] * (i[name].dim() - 1))
+    return i
+
+
+def subpix_launch(x, w, ups, ext, pro=PRO_NONE, s=None, t=None, alpha=1.0, acc=None, floor=None, **epi):
+    """a sub-pixel launch of include/p2l.h in the dtype of x: a = prologue(x) on the input tensor itself -- before any
+    upsampling or padding (ups = 3: no prologue) --, v = alpha subpix_map(a, w), then conv_epilogue(**epi) on the whole
+    output (ext = 1 forward: the frame; its row / column H+1 holds the epilogue of 0).  `acc` replaces the map (a
+    restatement's accumulator), `floor` is added to the denominator.  den = subpix_map(|a|, |w|): sum |a| |w| over the
+    ORIGINAL 3x3 taps that reach the output -- a slab whose taps cancel keeps its denominator.
+    -> conv_epilogue's dict, and a, aabs"""
+    dt = x.dtype
+    w = w.to(dt)
+    a, aabs = pw_prologue(x, pro, s, t) if ups == 2 else (x, x.abs())
+    v = subpix_map(a, w, ups, ext) if acc is None else acc.to(dt)
+    den = subpix_map(aabs, w.abs(), ups, ext)
+    den = den if floor is None else den + floor.to(dt)
+    out = conv_epilogue(v * alpha, den * abs(alpha), **epi)
+    out.update(a=a, aabs=aabs)
+    return out
+
+
+def subpix_refs(c, i, route=None, restate=True):
+    """-> subpix_launch's dict in fp64 (H, P: with subpix_h2_floor) and the route's fp32 restatement's (restate =
+    False: None)"""
+    route = route or c['route']
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    kw64, kw32 = pw_kwargs(c, i, torch.float64), pw_kwargs(c, i, torch.float32)
+    floor = None
+    if route in 'HP':
+        aabs = pw_prologue(i64['x'], c['pro'], i64.get('s'), i64.get('t'))[1] if c['ups'] == 2 else i64['x'].abs()
+        floor = subpix_h2_floor(aabs, i['w'], c['ups'], c['ext'], pw_amax(c, i)[1], subpix_h2_wmax(i['w']))
+    r64 = subpix_launch(i64['x'], i64['w'], c['ups'], c['ext'], floor=floor, **kw64)
+    if not restate:
+        return r64, None
+    return r64, subpix_launch(i['x'], i['w'], c['ups'], c['ext'], acc=subpix_acc32(c, i, route), **kw32)
+
+
+def subpix_spots(c):
+    """(image, y, x) of the one-hot pixels on the INPUT tensor of a case: its corners, both sides of every seam of
+    choose_tile's tiles of the low-resolution grid (ups = 3: the four high-resolution rows / columns around it), the
+    last row / column -- of an ext = 1 forward the input pixel H/2 - 1 that alone reaches grid row H/2, of an ext = 1
+    gradient row H of the frame --, the interior, and the first and last pixel of the second image"""
+    ups, ext, B = c['ups'], c['ext'], c['B']
+    (gh, gw), (TW, TH, TB) = subpix_grid(c)
+    if ups == 2:
+        ih, iw = c['H'] // 2, c['W'] // 2
+        ys = [y for s in range(TH, gh, TH) for y in (s - 1, s)]
+        xs = [x for s in range(TW, gw, TW) for x in (s - 1, s)]
+    else:
+        ih, iw = c['H'] + ext, c['W'] + ext                     # (the real rows / columns of the frame)
+        ys = [y for s in range(TH, gh, TH) for y in (2 * s - 2, 2 * s - 1, 2 * s, 2 * s + 1)]
+        xs = [x for s in range(TW, gw, TW) for x in (2 * s - 2, 2 * s - 1, 2 * s, 2 * s + 1)]
+    sp = [(0, 0, 0), (0, 0, iw - 1), (0, ih - 1, 0), (0, ih - 1, iw - 1), (0, ih // 2, iw // 2), (0, 1, 1),
+          (0, ih - 2, iw - 2), (0, 0, iw // 2), (0, ih // 2, 0)]
+    sp += [(0, y, iw // 3) for y in ys if y < ih] + [(0, y, iw - 1) for y in ys if y < ih]
+    sp += [(0, ih // 3, x) for x in xs if x < iw] + [(0, ih - 1, x) for x in xs if x < iw]
+    if B > 1:
+        sp += [(1, 0, 0), (1, ih - 1, iw - 1), (B - 1, 0, iw - 1), (B - 1, ih - 1, 0)]
+    if ups == 3:        # all four phase planes at every spot: one tap of a transposed conv reaches one parity only
+        sp = [(b, yy, xx) for b, y, x in sp for yy in (y, y ^ 1) for xx in (x, x ^ 1) if yy < ih and xx < iw]
+    out = []
+    for s in sp:
+        if s not in out:
+            out.append(s)
+    return out
+
+
+def subpix_onehot(c, tap, seed=0):
+    """exact inputs: x with single power-of-two pixels at subpix_spots, one per channel in turn; the forward's w with
+    single power-of-two entries on ORIGINAL tap (dy, dx) = (tap / 3, tap % 3) at the channels the pixels sit in.  A
+    slab then holds one tap or none, every output is a sum of a few powers of two within a few binades: exact in fp32,
+    in three bf16 and in two fp16 pieces, in any K slices"""
+    ups, ext, B, H, W, Cin, Cout = c['ups'], c['ext'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    shape = (B, H // 2, W // 2, Cin) if ups == 2 else (B, H + 2 * ext, W + 2 * ext, Cin)
+    x = torch.zeros(*shape)
+    w = torch.zeros(Cout, Cin, 3, 3) if ups == 2 else torch.zeros(Cin, Cout, 3, 3)
+    spots = subpix_spots(c)
+    for n, (b, py, px) in enumerate(spots):
+        x[b, py, px, (5 * (n + seed)) % Cin] = 2.0 ** ((n + seed) % 5 - 2)
+    for n in range(min(len(spots), Cin)):
+        ci, co = (5 * (n + seed)) % Cin, (37 * n + seed) % Cout
+        v = 2.0 ** (n % 3 - 1) * (-1.0) ** n
+        if ups == 2:
+            w[co, ci, tap // 3, tap % 3] = v
+        else:
+            w[ci, co, tap // 3, tap % 3] = v
+    return dict(x=x, w=w)
+
+
+def _sac(route, ext, HW, B, Cin, Cout, **kw):
+    c = dict(route=route, ups=3, ext=ext, H=HW[0], W=HW[1], B=B, Cin=Cin, Cout=Cout, splitk=1, skip_g=None,
+             pool_sum=False, nomask=False, amax=None, pro=PRO_NONE, alpha=1.0, wfmt='bf3', pair='form', skip=True,
+             finish='v4', amax_out=False, cancel=False, relu_like=False, t0=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def subpix_arb_id(c):
+    d = _sac(c['route'], c['ext'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-u3e%d-%dx%dx%d-%dto%d' % (c['route'], c['ext'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+# the variants the launcher accepts for ups = 3 (it drops the pool: no pool_sum); skips live at the low resolution
+SP_ARB_VARIANTS = [dict(), dict(skip_g='same'), dict(skip_g='ups'), dict(nomask=True)]
+# unsplit: one image per whole tile of the low-resolution grid (8x16 and up); sliced: the finish kernel, per quad --
+# multi-image tiles allowed
+SUBPIX_ARB_CASES = [_sac(*base, **dict(kw, **v)) for base, kw in [
+    (('F', 0, (16, 32), 2, 32, 64), {}), (('B', 0, (32, 32), 2, 16, 32), {}), (('B', 1, (16, 32), 2, 32, 64), dict(wfmt='bf3w')),
+    (('H', 0, (16, 32), 2, 32, 64), dict(amax_out=True)), (('H', 0, (32, 32), 2, 16, 96), dict(amax='true')),
+    (('H', 1, (16, 32), 2, 32, 64), {}), (('F', 1, (16, 64), 2, 16, 32), {}),
+    (('H', 1, (16, 16), 3, 128, 64), dict(splitk=4)), (('H', 1, (16, 16), 2, 256, 32), dict(splitk=8, amax='true')),
+    (('H', 1, (16, 16), 3, 128, 64), dict(splitk=4, finish='scalar')), (('H', 1, (32, 32), 2, 256, 32), dict(splitk=4))]
+    for v in SP_ARB_VARIANTS]
+
+
+def subpix_arb_inputs(g, c):
+    """arb_inputs' consumer operands (ax, as, at, the shortcut gradient) at the low resolution of dx, the high-
+    resolution gradient x (ext: the frame, row / column H+1 zero) and the forward's w [Cin, Cout, 3, 3]"""
+    B, H, W, Cin, Cout, ext = c['B'], c['H'], c['W'], c['Cin'], c['Cout'], c['ext']
+    rt = 'C' if c['route'] in 'HP' else 'A'
+    i = arb_inputs(g, dict(c, route=rt, H=H // 2, W=W // 2, skip=c['skip_g'], pool_sum=False))
+    mg = mags(B).view(B, 1, 1, 1)
+    x = torch.randn(B, H + 2 * ext, W + 2 * ext, Cin, generator=g) * mg
+    if rt == 'C':
+        x[1] = 0.0
+        x[0, 0:2, 0:2] *= 2.0 ** -20
+    if ext:
+        x[:, -1], x[:, :, -1] = 0.0, 0.0
+    i['x'] = x
+    i['w'] = torch.randn(Cin, Cout, 3, 3, generator=g) / math.sqrt(9 * Cin)
+    return i
+
+
+def subpix_arb_refs(c, i):
+    """-> arb_epilogue's dict on da = subpix_map of the gradient in fp64 (H: with subpix_h2_floor) and the route's fp32
+    restatement's, ds and dt in the kernels' two stages on the LOW-resolution grid (arb_sums32: an unsplit launch
+    leaves one partial per 128-pixel tile, a K-sliced one one per quad)"""
+    kw = dict(pool_sum=False, nomask=c['nomask'], skip=i.get('skip'), skip_C=c['Cout'] // 2 if c['skip_g'] else 0,
+              skip_ups=c['skip_g'] == 'ups')
+    x64, w64 = i['x'].double(), i['w'].double()
+    dend = subpix_map(x64.abs(), w64.abs(), 3, c['ext'])
+    if c['route'] in 'HP':
+        dend = dend + subpix_h2_floor(x64.abs(), i['w'], 3, c['ext'], pw_amax(c, i)[1], subpix_h2_wmax(i['w']))
+    r64 = arb_epilogue(subpix_map(x64, w64, 3, c['ext']), dend, i['ax'].double(), i['as'].double(), i['at'].double(), **kw)
+    r32 = arb_epilogue(subpix_acc32(c, i), dend.float(), i['ax'], i['as'], i['at'], **kw)
+    r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'] // 2, c['W'] // 2, False, len(subpix_slices(c)) > 1)
+    return r64, r32
+
+
+def subpix_arb_k(c):
+    """arb_k with the conv's count from subpix_k and the sums' over the low-resolution grid of dx"""
+    return arb_k(dict(c, H=c['H'] // 2, W=c['W'] // 2, skip=c['skip_g'], oscale=False, bias=False, noise=False,
+                      res=None, act=ACT_NONE), subpix_k)
+
+
+def subpix_arb_bound(c, r64, ax):
+    return arb_bound(dict(c, H=c['H'] // 2, W=c['W'] // 2, skip=c['skip_g'], oscale=False, bias=False, noise=False,
+                          res=None, act=ACT_NONE), r64, ax, subpix_k)
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

@@ -1011,3 +1011,255 @@ def test_direct_case_tables():
     i = R.direct_inputs(_g(240), R._dsh('F', '8x8', **R.EPI[0]))
     m = i['x'].abs().amax(dim=(1, 2, 3))
     assert float(m[2] / m[0]) > 1e13 and float(i['res'][2].abs().max() / i['res'][0].abs().max()) > 1e9
+
+
+# ---- sub-pixel 3x3 convs (tests/test_subpix_kernels_gpu.py) --------------------------------------------------------
+def _sp_operands(g, ups, ext, B=2, H=8, W=12, Ci=16, Co=32):
+    """fp64 operands of one mode: the forward's OIHW weight and the launch's input (ups = 3: the gradient frame)"""
+    wf = torch.randn(Co, Ci, 3, 3, generator=g, dtype=D) if ups == 2 else torch.randn(Ci, Co, 3, 3, generator=g, dtype=D)
+    if ups == 2:
+        return torch.randn(B, H // 2, W // 2, Ci, generator=g, dtype=D), wf
+    a = torch.randn(B, H + 2 * ext, W + 2 * ext, Ci, generator=g, dtype=D)
+    if ext:
+        a[:, -1], a[:, :, -1] = 0.0, 0.0
+    return a, wf
+
+
+def test_subpix_references_agree_with_independent_formulations():
+    """ups = 2, ext = 0 == F.interpolate(nearest) + F.conv2d; ext = 1 == F.conv_transpose2d(stride 2) in rows / columns
+    0 .. H of the frame, row / column H + 1 +0; ups = 3 == autograd through those, the frame's last row ignored"""
+    g = _g(300)
+    nchw, nhwc = (lambda v: v.permute(0, 3, 1, 2)), (lambda v: v.permute(0, 2, 3, 1))
+    x, w = _sp_operands(g, 2, 0)
+    want = nhwc(F.conv2d(F.interpolate(nchw(x), scale_factor=2, mode='nearest'), w, padding=1))
+    assert (R.subpix_map(x, w, 2, 0) - want).abs().max().item() < 1e-12
+    dy = torch.randn(want.shape, generator=g, dtype=D)
+    xr = x.clone().requires_grad_(True)
+    nhwc(F.conv2d(F.interpolate(nchw(xr), scale_factor=2, mode='nearest'), w, padding=1)).backward(dy)
+    assert (R.subpix_map(dy, w, 3, 0) - xr.grad).abs().max().item() < 1e-12
+    got = R.subpix_map(x, w, 2, 1)
+    tc = nhwc(F.conv_transpose2d(nchw(x), w.transpose(0, 1), stride=2))
+    assert got.shape[1:3] == (10, 14) and tc.shape[1:3] == (9, 13)
+    assert (got[:, :9, :13] - tc).abs().max().item() < 1e-12
+    assert bool((got[:, 9].view(torch.int64) == 0).all()) and bool((got[:, :, 13].view(torch.int64) == 0).all())
+    du = torch.randn(got.shape, generator=g, dtype=D)                        # (junk in row / column H + 1: ignored)
+    xr = x.clone().requires_grad_(True)
+    (nhwc(F.conv_transpose2d(nchw(xr), w.transpose(0, 1), stride=2)) * du[:, :9, :13]).sum().backward()
+    assert (R.subpix_map(du, w, 3, 1) - xr.grad).abs().max().item() < 1e-12
+    # the out[2 p + k] += x[p] w[k] of the header, element by element on one pixel
+    one = torch.zeros(1, 4, 6, 16, dtype=D)
+    one[0, 2, 3, 5] = 1.0
+    u = R.subpix_map(one, w, 2, 1)
+    assert torch.equal(u[0, 4:7, 6:9], w[:, 5].permute(1, 2, 0)) and float(u.abs().sum()) == float(w[:, 5].abs().sum())
+
+
+@pytest.mark.parametrize('ups,ext', [(2, 0), (2, 1), (3, 0), (3, 1)])
+def test_subpix_slab_table_is_tied_to_its_definition(ups, ext):
+    """SP_TAPS / subpix_slabs / subpix_windows restate the kernels; subpix_map does not know them.  For each of the
+    nine ORIGINAL taps alone, and for a dense weight, the sum over phases (planes) of slab (*) low-resolution window ==
+    the plain reference: every one of the 16 slabs of the mode and flip holds exactly the taps the definition gives
+    it.  Mode 1 leaves 7 of the 16 slabs empty (the taps sp_skip leaves out), mode 0 none; every original tap sits in
+    exactly one slab per phase of mode 0 forward (4 slabs), in 4 of the gradient's, and in one slab of mode 1"""
+    g = _g(310 + 2 * ups + ext)
+    a, w = _sp_operands(g, ups, ext)
+
+    def by_slabs(wt):
+        sl, wins = R.subpix_slabs(wt, ext, ups == 3), R.subpix_windows(a, ups, ext)
+        parts = [R.subpix_cols(wins[p]) @ R.subpix_wmat(sl[4 * p:4 * p + 4]).t() for p in range(4)]
+        if ups == 3:
+            return sum(parts)
+        out = torch.zeros(a.shape[0], 2 * parts[0].shape[1], 2 * parts[0].shape[2], parts[0].shape[3], dtype=D)
+        for p in range(4):
+            out[:, p >> 1::2, p & 1::2] = parts[p]
+        return out
+    assert (by_slabs(w) - R.subpix_map(a, w, ups, ext)).abs().max().item() < 1e-12
+    member = torch.zeros(16, 9, dtype=torch.int64)
+    for tap in range(9):
+        wt = torch.zeros_like(w)
+        wt[:, :, tap // 3, tap % 3] = w[:, :, tap // 3, tap % 3]
+        want = R.subpix_map(a, wt, ups, ext)
+        assert float(want.abs().max()) > 0 and (by_slabs(wt) - want).abs().max().item() < 1e-12, tap
+        member[:, tap] = (R.subpix_slabs(wt, ext, ups == 3).abs().sum(dim=(1, 2)) > 0).long()
+    empty = int((member.sum(1) == 0).sum())
+    assert empty == (7 if ext else 0)
+    per_tap = member.sum(0)
+    assert bool((per_tap == (1 if ext else 4)).all()), per_tap
+    if not ext:
+        assert int(member.sum(1).max()) == 4 and int(member.sum(1).min()) == 1     # 2 x 2 sums down to single taps
+    # the window of every slab, read as a position: tap t of phase | plane p at grid point (1, 1)
+    T = R.SP_TAPS[(ext, int(ups == 3))]
+    for p in range(4):
+        for t in range(4):
+            assert int(member[4 * p + t].sum()) == len(T[p >> 1][t >> 1]) * len(T[p & 1][t & 1])
+
+
+def _sp_wrong_prologue(case, i):
+    """the mistake the plan's t = 0 launch cannot see: the prologue applied AFTER the padding of the H/2 + 1 grid -- the
+    out-of-range window positions p - 1 < 0 and p = H/2 read t (relu(t)) in place of 0 -- in fp64, through the epilogue"""
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    kw = R.pw_kwargs(case, i, D)
+    a, _ = R.pw_prologue(F.pad(i64['x'], (0, 0, 1, 1, 1, 1)), case['pro'], i64['s'], i64['t'])
+    u = F.conv_transpose2d(a.permute(0, 3, 1, 2), i64['w'].transpose(0, 1), stride=2).permute(0, 2, 3, 1)
+    H, W = case['H'], case['W']
+    v = u[:, 2:2 + H + 2, 2:2 + W + 2] * case['alpha']
+    r64 = R.subpix_refs(case, i, restate=False)[0]
+    return R.conv_epilogue(v, torch.zeros_like(v), **{k: x for k, x in kw.items() if k not in ('pro', 's', 't', 'alpha')}), r64
+
+
+@pytest.mark.parametrize('case', R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES, ids=R.subpix_id)
+def test_subpix_restatements_stay_under_a_quarter_of_k(case):
+    """for every case's generator and shape the fp32 restatement of its route is within k / 4 of the fp64 reference on
+    sum |a| |w_tap| (H, P: plus subpix_h2_floor): k and the floor were not set from the kernels.  Two negative
+    controls.  (1) ext = 1 forward under a prologue: with t = 0 -- the only launch the StyleGAN2 plan makes -- a
+    prologue applied after the padding of the H/2 + 1 grid IS the right answer, bit for bit; on the t != 0 draws it
+    misses the bar by more than 100 x in the frame's rows / columns 0 and H (and H + 1, which must hold the epilogue of
+    0).  (2) cancel: on weights whose taps nearly cancel inside a slab the restatement held to a denominator on |sum
+    w_tap| -- sum |a| |slab| -- misses its bar by more than 100 x, and passes on sum |a| |w_tap|"""
+    def body(gen):
+        i = R.subpix_inputs(gen('subpix', R.subpix_id(case)), case)
+        r64, r32 = R.subpix_refs(case, i)
+        f = _fig(r32['y'], r64['y'], r64['den'])
+        k = R.subpix_k(case)
+        assert f <= k / 4.0, (f, k)
+        bar = min(k, 4.0 * f)
+        if case['ups'] == 2 and case['ext'] and case['pro'] != R.PRO_NONE:
+            wrong, _ = _sp_wrong_prologue(case, i)
+            err = (wrong['y'] - r64['y']).abs()
+            if case['t0']:
+                assert float(err.max()) == 0.0
+            else:
+                H, W = case['H'], case['W']
+                edge = torch.zeros(err.shape[1:3], dtype=torch.bool)
+                edge[0], edge[H], edge[:, 0], edge[:, W] = True, True, True, True
+                edge[H + 1], edge[:, W + 1] = False, False
+                rel = err / r64['den'].clamp_min(1e-300) / R.U
+                xmax = i['x'].abs().amax(dim=(1, 2, 3))
+                b0 = int(torch.where(xmax > 0, xmax, xmax.max()).argmin()) if not case['pro_b'] else case['B'] - 1
+                live = (r64['den'][b0] > 0) & edge[..., None]
+                miss = float(rel[b0][live].median()) / bar
+                print('%s: prologue after the padding misses the bar %.3g x' % (R.subpix_id(case), miss))
+                assert miss > 100, miss
+                assert float(err[:, 1:H, 1:W].max()) == 0.0                  # (the interior cannot tell)
+                assert float(err[:, H + 1].max()) > 0                        # t W[1] where the frame must hold +0
+        if case['cancel'] and case['route'] in 'FB':
+            # (H, P: the fp16 x 2 floor, 2^-13 of the maxima, stands above a slab cancelled to 2^-18 in either denominator)
+            a = r64['aabs']
+            sl = R.subpix_slabs(i['w'].double(), case['ext'], case['ups'] == 3).abs()
+            wins = R.subpix_windows(a, case['ups'], case['ext'])
+            parts = [R.subpix_cols(wins[p]) @ R.subpix_wmat(sl[4 * p:4 * p + 4]).t() for p in range(4)]
+            if case['ups'] == 3:
+                den_slab = sum(parts)
+            else:
+                den_slab = torch.zeros_like(r64['den'])
+                for p in range(4):
+                    den_slab[:, p >> 1::2, p & 1::2] = parts[p]
+            miss = _fig(r32['y'], r64['y'], den_slab * abs(case['alpha'])) / bar
+            print('%s: a denominator on |sum w_tap| misses the bar %.3g x' % (R.subpix_id(case), miss))
+            assert miss > 100, miss
+    _draws(body)
+
+
+@pytest.mark.parametrize('case', R.SUBPIX_ARB_CASES, ids=R.subpix_arb_id)
+def test_subpix_dgrad_restatements_stay_under_a_quarter_of_k(case):
+    def body(gen):
+        i = R.subpix_arb_inputs(gen('sarb', R.subpix_arb_id(case)), case)
+        kdx, kds, kdt = R.subpix_arb_k(case)
+        r64, r32 = R.subpix_arb_refs(case, i)
+        f = _fig(r32['dx'], r64['dx'], r64['den_dx'])
+        assert f <= kdx / 4.0, ('dx', f, kdx)
+        for name, bound in zip(('ds', 'dt'), R.subpix_arb_bound(case, r64, i['ax'])):
+            assert bool(((r32[name].double() - r64[name]).abs() <= bound * R.U).all()), name
+        p64, p32 = R.subpix_arb_refs(case, R.arb_positive(i))
+        for name, k in (('ds', kds), ('dt', kdt)):
+            f = _fig(p32[name], p64[name], p64['den_' + name])
+            assert f <= k / 4.0, (name, f, k)
+    _draws(body)
+    # against autograd through relu(x s + t) -> the forward of the mode, once
+    i = R.subpix_arb_inputs(_g(330), case)
+    got = R.subpix_arb_refs(case, i)[0]
+    x64, s64, t64 = i['ax'].double(), i['as'].double(), i['at'].double()
+
+    def fwd(x, s, t):
+        a = x * s[:, None, None, :] + t[:, None, None, :]
+        return R.subpix_map(a if case['nomask'] else torch.relu(a), i['w'].double(), 2, case['ext'])
+    dx, ds, dt = R.vjp(fwd, [x64, s64, t64], i['x'].double())
+    if case['skip_g']:
+        C2 = case['Cout'] // 2
+        sk = i['skip'].double()[..., :C2]
+        dx[..., :C2] += R.quad_sum(sk) if case['skip_g'] == 'ups' else sk
+    for name, want in (('dx', dx), ('ds', ds), ('dt', dt)):
+        assert (got[name] - want).abs().max().item() <= 1e-11 * want.abs().max().item(), name
+
+
+@pytest.mark.parametrize('tap', range(9))
+def test_subpix_one_hot_inputs_are_exact_in_every_restatement(tap):
+    """single power-of-two pixels and a single power-of-two weight on one original tap go through the slab sums, the
+    fp32 chain, the bf16 x 3 and the fp16 x 2 pieces and the slices without a rounding: every restatement gives the
+    fp64 result bit for bit, and it is not all zero"""
+    for c in (R._ssh('F', 2, 0, '32x32'), R._ssh('B', 2, 1, '16x16'), R._ssh('H', 2, 1, '8x8'), R._ssh('P', 2, 0, '4x4'),
+              R._ssh('F', 3, 1, '16x16'), R._ssh('B', 3, 0, '8x8'), R._ssh('H', 3, 0, '16x64'),
+              R._ssh('H', 3, 1, 's4', splitk=4), R._ssh('H', 3, 1, 's8', splitk=8)):
+        for seed in range(2):
+            i = R.subpix_onehot(c, tap, seed)
+            r64, r32 = R.subpix_refs(c, i)
+            assert torch.equal(r32['y'].double(), r64['y']), (R.subpix_id(c), seed)
+            assert torch.equal(r64['y'], R.subpix_map(i['x'].double(), i['w'].double(), c['ups'], c['ext']))
+            assert int((r64['y'] != 0).sum()) >= 3, (R.subpix_id(c), seed)
+
+
+def _choose_bn(c):
+    """choose_bn of csrc/p2l_conv.hip for a sub-pixel case"""
+    (gh, gw), (TW, TH, TB) = R.subpix_grid(c)
+    n_mtiles = R.cdiv(gw, TW) * R.cdiv(gh, TH) * R.cdiv(c['B'], TB)
+    if c['Cout'] % 64:
+        return 32
+    ph = 4 if c['ups'] == 2 else 1
+    n64, n32 = n_mtiles * (c['Cout'] // 64) * ph, n_mtiles * (c['Cout'] // 32) * ph
+    if n64 < 256:
+        return 32
+    return 32 if R.cdiv(n32, 256) * 32.0 * 1.06 < 0.93 * R.cdiv(n64, 256) * 64.0 else 64
+
+
+def test_subpix_case_tables():
+    """the slice counts of the issue against the restatement of subpix_bwd_split; the tiles each shape reaches
+    (choose_tile on the low-resolution grid); 64-channel tiles at the two bn64 shapes only; every route in all four
+    modes with every epilogue term of its mode; H with all sources of its maxima; the images of a launch 3e10 apart"""
+    assert R.subpix_bwd_split(16, 16, 128, 64) == 4 and R.subpix_bwd_split(16, 16, 256, 32) == 8
+    assert R.subpix_bwd_split(32, 32, 256, 32) == 4 and R.subpix_bwd_split(16, 16, 64, 64) == 1
+    for c in R.SUBPIX_BWD_CASES + R.SUBPIX_ARB_CASES:
+        if c['splitk'] > 1:
+            assert c['route'] == 'H' and c['ext'] and R.subpix_bwd_split(c['H'], c['W'], c['Cin'], c['Cout']) == c['splitk']
+            assert len(R.subpix_slices(c)) == c['splitk']
+    assert R.subpix_slices(R._ssh('H', 3, 1, 's4', splitk=4)) == [(z * 512, (z + 1) * 512) for z in range(4)]
+    tiles = {}
+    for c in R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES:
+        tiles.setdefault((c['ups'], c['ext']), set()).add(R.subpix_grid(c))
+    assert tiles[(2, 0)] >= set([((8, 16), (16, 8, 1)), ((16, 16), (16, 8, 1)), ((8, 32), (16, 8, 1)), ((4, 4), (4, 4, 8)),
+                                 ((2, 2), (2, 8, 8)), ((8, 8), (8, 8, 2))])
+    assert tiles[(2, 1)] >= set([((5, 5), (8, 8, 2)), ((9, 9), (16, 8, 1)), ((17, 17), (16, 8, 1)), ((9, 17), (16, 8, 1)),
+                                 ((3, 3), (4, 4, 8))])
+    assert tiles[(3, 1)] >= set([((8, 16), (16, 8, 1)), ((16, 16), (16, 8, 1)), ((4, 4), (4, 4, 8)), ((2, 2), (2, 8, 8))])
+    for c in R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES:
+        name = [n for n, v in R.SUBPIX_SHAPES.items() if v == ((c['H'], c['W']), c['B'], c['Cin'], c['Cout'])][0]
+        assert _choose_bn(c) == (64 if name.startswith('bn64') else 32), R.subpix_id(c)
+    for route in 'FBH':
+        for ups, ext, epi in ((2, 0, R.SP_EPI_E0), (2, 1, R.SP_EPI_E1), (3, 0, R.SP_EPI_G), (3, 1, R.SP_EPI_G)):
+            cs = [c for c in R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES if (c['route'], c['ups'], c['ext']) == (route, ups, ext)]
+            for e in epi:
+                assert any(all(c[k] == v for k, v in e.items()) for c in cs), (route, ups, ext, e)
+            assert any(c['n_store'] < c['Cout'] for c in cs), (route, ups, ext)
+    for ext in (0, 1):
+        assert any((c['route'], c['ext']) == ('P', ext) for c in R.SUBPIX_FWD_CASES)
+    h = [c for c in R.SUBPIX_FWD_CASES if c['route'] in 'HP']
+    assert set(c['amax'] for c in h) == set([None, 'true', 'raw', 'applied'])
+    assert len(set(R.subpix_id(c) for c in R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES)) == \
+        len(R.SUBPIX_FWD_CASES + R.SUBPIX_BWD_CASES)
+    assert len(set(R.subpix_arb_id(c) for c in R.SUBPIX_ARB_CASES)) == len(R.SUBPIX_ARB_CASES)
+    i = R.subpix_inputs(_g(340), R._ssh('H', 2, 1, '8x8', pro=R.PRO_AFFINE))
+    m = i['x'].abs().amax(dim=(1, 2, 3))
+    assert float(m[2] / m[0]) > 1e13 and not bool(i['x'][1].any())
+    w = R.subpix_inputs(_g(341), R._ssh('F', 2, 0, '32x32', cancel=True))['w']
+    sl, big = R.subpix_slabs(w.double(), 0, False), R.subpix_slabs(w.double().abs(), 0, False)
+    assert float((sl[3].abs() / big[3]).median()) < 2.0 ** -16          # phase (0, 0), tap (1, 1): {1, 2} x {1, 2}
+    off = (R.subpix_slabs(w, 0, False)[3].double() - sl[3]).abs()          # ... and fp32 cannot follow the chain
+    assert float((off / sl[3].abs()).median()) > 2.0 ** -10 and float((off / big[3]).max()) <= 3 * R.U
