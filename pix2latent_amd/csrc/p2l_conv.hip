@@ -1012,6 +1012,7 @@ void grid_dims(const P2LConv* d, int& gH, int& gW) {
   gH = d->H >> sh; gW = d->W >> sh;
   if (d->ups == 2 && d->ext) { gH += 1; gW += 1; }
 }
+// the tiling of that grid (the tile fields of k, nothing else)
 int choose_tile(const P2LConv* d, ConvK& k) {
   int gH, gW;
   grid_dims(d, gH, gW);
@@ -1050,6 +1051,57 @@ int halo_pitch(int TW, bool bf3) {
 // ... of the fp16 x 2 kernel's 64-byte rows (tools/h2_banks.py: 16- and 8-wide tiles are conflict
 // free at 24 rows per line, 2.0 LDS cycles per lane group at best for the 4-wide tiles of the 4^2 layers)
 int halo_pitch_h2(int TW) { return TW >= 8 ? 24 : (TW == 4 ? 8 : TW + 2); }
+// rows of a 3x3 / sub-pixel block's staged patch: the tile's pixels + halo
+int patch_rows(const ConvK& k) { return (1 << k.tb_log) * ((1 << k.th_log) + 2) * ((1 << k.tw_log) + 2); }
+
+// Channels per K chunk: 16 for 3x3, 32 for 1x1 where the channel count allows it (the packed fp32 layout is
+// [tap][K / kc][N][kc], so the pack and the launch must agree)
+int conv_kc(int taps, int K) { return (taps != 1) ? 16 : (K % 32 == 0 ? 32 : 16); }
+
+// Where the images of a packed weight buffer start, in floats: the ONE statement of the layout that the size
+// queries, the pack functions and the launcher read.  (taps, sub-pixel or not, N_pad, K_pad, wfmt) decide it:
+//   P2L_WFMT_F32      the fp32 layout alone
+//   P2L_WFMT_PW       fp32 layout | bf16 x 3 image | fp16 x 2 image                      (1x1)
+//   P2L_WFMT_BF16X3   bf16 x 3 tile image alone
+//   P2L_WFMT_BF16X3W  bf16 x 3 | Winograd, Winograd fp16 x 2 (shapes p2l_wino_weight_ok takes) | direct fp16 x 2;
+//                     sub-pixel: bf16 x 3 | fp16 x 2, both of the 16 phase-tap slabs
+//   P2L_WFMT_BF16X3T  bf16 x 3 | thin image (three real channels on one side)
+// Every fp16 x 2 image ends in four tail floats (bits of max |weight|: ConvK::w_tail).  An image the buffer does
+// not hold keeps offset 0 and is never asked for: the formats a route reads are the ones its predicate admits.
+struct WeightImages {
+  size_t direct, wino, wino_h2, h2, pw, pw_h2, thin, total;
+  size_t wino_h2_tail, h2_tail, pw_h2_tail;
+};
+WeightImages weight_images(int taps, bool subpix, int N_pad, int K_pad, int wfmt) {
+  WeightImages o{};
+  const size_t fp32 = (size_t)(subpix ? 16 : taps) * N_pad * K_pad;
+  auto put = [&o](size_t& at, size_t floats) { at = o.total; o.total += floats; };
+  auto put_h2 = [&o, &put](size_t& at, size_t& tail, size_t floats) { put(at, floats); tail = o.total - 4; };
+  if (wfmt == P2L_WFMT_F32) {
+    put(o.direct, fp32);
+  } else if (wfmt == P2L_WFMT_PW && !subpix) {
+    put(o.direct, fp32);
+    put(o.pw, fp32 * 3 / 2);
+    put_h2(o.pw_h2, o.pw_h2_tail, p2l_pw_h2_weight_floats(N_pad, K_pad));
+  } else {
+    put(o.direct, fp32 * 3 / 2);
+    if (subpix) {
+      if (wfmt == P2L_WFMT_BF16X3W) put_h2(o.h2, o.h2_tail, p2l_h2_weight_floats(N_pad, K_pad, 1));
+    } else if (taps == 9 && wfmt == P2L_WFMT_BF16X3W) {
+      if (p2l_wino_weight_ok(N_pad, K_pad)) {
+        put(o.wino, p2l_wino_weight_floats(N_pad, K_pad));
+        put_h2(o.wino_h2, o.wino_h2_tail, p2l_wino_h2_weight_floats(N_pad, K_pad));
+      }
+      put_h2(o.h2, o.h2_tail, p2l_h2_weight_floats(N_pad, K_pad, 0));   // behind everything else
+    } else if (taps == 9 && wfmt == P2L_WFMT_BF16X3T) {
+      put(o.thin, p2l_thin_weight_floats(N_pad, K_pad));
+    }
+  }
+  return o;
+}
+
+// ---- The routing rules.  Each predicate below is the ONE place its rule is stated; conv_route calls each once
+// ---- and everything else -- the launcher and the size queries -- reads the ConvRoute it fills.
 
 // Winograd form (p2l_wino.hip).  Which launches take it is a function of the LAYER SHAPE only,
 // never of the batch: a candidate's result must not depend on how many others share its chunk
@@ -1063,12 +1115,12 @@ int halo_pitch_h2(int TW) { return TW >= 8 ? 24 : (TW == 4 ? 8 : TW + 2); }
 // P2LConv.form: P2L_FORM_NO_WINO keeps the direct kernel, P2L_FORM_WINO_ANY takes every eligible
 // shape (tests: small grids too).
 // K slices of a small-grid Winograd layer (shape only; 1 = none)
-static int wino_split(const P2LConv* d) {
+int wino_split(const P2LConv* d) {
   if (d->wfmt != P2L_WFMT_BF16X3W || d->taps != 9 || d->ups != 0 || (d->form & P2L_FORM_NO_WINO)) return 1;
   if (d->x_ld % 4 || !p2l_wino_weight_ok(d->Cout, d->Cin) || (d->form & P2L_FORM_WINO_8X16)) return 1;
   return p2l_wino_split_factor(d->H, d->W, d->Cin, d->Cout);
 }
-static bool wino_shape(const P2LConv* d) {
+bool wino_shape(const P2LConv* d, int slices /* wino_split(d) */) {
   if (d->wfmt != P2L_WFMT_BF16X3W || d->taps != 9 || d->ups != 0 || (d->form & P2L_FORM_NO_WINO)) return false;
   if (d->H % 8 || d->W % 16 || d->x_ld % 4 || !p2l_wino_weight_ok(d->Cout, d->Cin)) return false;
   // 64 input channels = 4 chunks per block: the 16x16 kernel's prologue + epilogue (16.5 k cycles, one
@@ -1083,8 +1135,12 @@ static bool wino_shape(const P2LConv* d) {
   // p2l_conv_suggest_splitk gives for the shape (with it a 48-block launch at 2-3 candidates per
   // GPU becomes 96-192 short blocks; unsliced, a threshold of 32 measured +1 % at 18 candidates
   // and -2...-4 % at 2-3)
-  const int s = wino_split(d);
-  return s > 1 && d->splitk == s;
+  return slices > 1 && d->splitk == slices;
+}
+// the 16x16 Winograd kernel in the fp16 x 2 arithmetic: 64 partial maxima per image in front of
+// the split-K slices
+bool wino_h2(const P2LConv* d, bool wino) {
+  return wino && d->H % 16 == 0 && d->W % 16 == 0 && !(d->form & (P2L_FORM_WINO_8X16 | P2L_FORM_WINO_BF3));
 }
 
 // full-tile form of the 1x1 conv on the 16-bit pipe (p2l_pw.hip: bf16 x 3, or fp16 x 2 when the
@@ -1092,7 +1148,7 @@ static bool wino_shape(const P2LConv* d) {
 // image, 64-channel tiles.  Like the Winograd form a function of the layer shape only; the 4^2 ..
 // 16^2 layers take the small-grid fp16 x 2 form of the same kernel (pw_small_h2 below: multi-image
 // tiles, split-K slices).  P2L_FORM_NO_PW keeps the exact-fp32 kernel.
-static bool pw_shape(const P2LConv* d) {
+bool pw_shape(const P2LConv* d) {
   if ((d->form & P2L_FORM_NO_PW) || d->wfmt != P2L_WFMT_PW || d->taps != 1 || d->ups != 0) return false;
   if (d->Cin % 64 || d->Cout % 64 || d->x_ld % 4 || d->H % 8 || d->W % 16) return false;
   // measured per layer inside the bench step: 1.2-1.9x the exact-fp32 kernel from 256 input
@@ -1102,40 +1158,38 @@ static bool pw_shape(const P2LConv* d) {
 
 // 3-channel image convs (p2l_thin.hip): 0 thin output, 1 thin input, -1 the generic kernel.
 // Shape + format only (the epilogue conditions are checked at the launch).
-static int thin_shape(const P2LConv* d) {
+// (Either bf16x3 pointwise kernel -- pw_shape or this -- never splits K.)
+int thin_shape(const P2LConv* d) {
   if ((d->form & P2L_FORM_NO_THIN) || d->wfmt != P2L_WFMT_BF16X3T || d->taps != 9 || d->ups != 0) return -1;
   if (d->H % 8 || d->W % 16 || d->x_ld % 4 || d->Cin % 16) return -1;
   return p2l_thin_mode(d->Cout, d->Cin);
 }
-// either bf16x3 pointwise kernel: no split-K
-static bool pw_any(const P2LConv* d) { return pw_shape(d) || thin_shape(d) >= 0; }
 
 // fp16 x 2 form of the direct 3x3 / sub-pixel kernel (p2l_h2.hip): every P2L_WFMT_BF16X3W launch that
 // the Winograd kernel does not take (sub-pixel up-convs, the 4^2 ... 16^2 layers in split-K slices,
 // H / W not multiples of 16) -- a function of the layer shape and the format; P2L_FORM_WINO_BF3
 // ("bf16 x 3 instead of fp16 x 2") keeps the bf16 x 3 kernel.  The launch also needs the 256 B per
 // image of workspace p2l_conv_workspace_bytes asks for.
-static bool direct_h2(const P2LConv* d) {
+bool direct_h2(const P2LConv* d, bool wino) {
 #ifdef P2L_AB_NO_DIRECT_H2      // A/B builds (tools/ab_build.sh): bisecting an arithmetic difference by kernel family
   return false;
 #endif
   if (d->wfmt != P2L_WFMT_BF16X3W || d->taps != 9 || (d->form & P2L_FORM_WINO_BF3)) return false;
   if (d->ups == 1 || d->x_ld % 4 || d->Cin % 16 || d->Cout % 32) return false;
-  return !wino_shape(d);
+  return !wino;
 }
 
 // ... and of the 1x1 kernel's small-grid form (p2l_pw.hip, pw_h2_kernel<.., SM>): the 4^2 ... 16^2
 // layers of P2L_WFMT_PW weights that the full-tile pointwise kernels do not take (multi-image tiles,
 // split-K slices).  Shape and format only.
-static bool pw_small_h2(const P2LConv* d) {
+bool pw_small_h2(const P2LConv* d, bool pw, bool whole_tiles) {
 #ifdef P2L_AB_NO_PWSMALL_H2
   return false;
 #endif
-  if (d->wfmt != P2L_WFMT_PW || d->taps != 1 || d->ups != 0 || pw_shape(d)) return false;
+  if (d->wfmt != P2L_WFMT_PW || d->taps != 1 || d->ups != 0 || pw) return false;
   if (d->form & (P2L_FORM_NO_PW | P2L_FORM_WINO_BF3)) return false;
   if (d->Cin % 32 || d->Cout % 64 || d->x_ld % 4) return false;
-  ConvK k{};
-  return choose_tile(d, k) == P2L_OK && !k.partial;
+  return whole_tiles;
 }
 
 // Output-channel tile: 64 unless the grid then leaves CUs idle in its last
@@ -1152,44 +1206,6 @@ int choose_bn(const P2LConv* d, int n_mtiles) {
   return (t32 < 0.93 * t64) ? 32 : 64;
 }
 
-// (A tap-row pipelined, double-buffered variant of the bf16x3 kernel - one barrier per 3 taps
-// instead of two per chunk - measured slower, 149-166 vs 158-188 TFLOP/s, and was removed;
-// see DESIGN.md 4.1 and the repository history.)
-template <int TAPS, int BN, int KC, int A_ITERS, int PRO, bool UPS, bool BF3>
-constexpr auto pick_kernel() {
-  return conv_mfma_kernel<TAPS, BN, KC, A_ITERS, PRO, UPS, BF3>;
-}
-
-template <int TAPS, int BN, int KC, int A_ITERS, bool BF3 = false>
-int launch_conv(const ConvK& k, int pro, int ups, size_t lds, hipStream_t st) {
-  dim3 grid(k.n_mtiles * k.n_ntiles, k.splitk), block(256);
-#define P2L_LAUNCH(PRO, UPS)                                                     \
-  do {                                                                           \
-    auto kfn = pick_kernel<TAPS, BN, KC, A_ITERS, PRO, UPS, BF3>();             \
-    static std::atomic<bool> attr_set{false};                                                \
-    if (!attr_set) {                                                             \
-      (void)hipFuncSetAttribute((const void*)kfn,                                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                160 * 1024);                                     \
-      attr_set = true;                                                           \
-    }                                                                            \
-    hipLaunchKernelGGL(kfn, grid, block, lds, st, k);                            \
-  } while (0)
-  if (ups) {
-    if (pro == P2L_PRO_NONE) P2L_LAUNCH(P2L_PRO_NONE, true);
-    else if (pro == P2L_PRO_AFFINE_RELU) P2L_LAUNCH(P2L_PRO_AFFINE_RELU, true);
-    else P2L_LAUNCH(P2L_PRO_AFFINE, true);
-  } else {
-    if (pro == P2L_PRO_NONE) P2L_LAUNCH(P2L_PRO_NONE, false);
-    else if (pro == P2L_PRO_AFFINE_RELU) P2L_LAUNCH(P2L_PRO_AFFINE_RELU, false);
-    else P2L_LAUNCH(P2L_PRO_AFFINE, false);
-  }
-#undef P2L_LAUNCH
-  return p2l_check_launch();
-}
-
-}  // namespace
-
 // K slices of a launch of the direct / pointwise kernels: a function of the LAYER SHAPE only (round 5).
 // Until round 4 the factor followed the grid (cdiv(512, blocks), blocks ~ batch), so the fp32 summation
 // order of the 4^2 ... 16^2 layers -- and with it a candidate's low bits -- depended on how many others
@@ -1203,77 +1219,42 @@ int launch_conv(const ConvK& k, int pro, int ups, size_t lds, hipStream_t st) {
 //   work term:  Cin * taps / 128   (>= 4 pointwise stages, >= 1.8 3x3 chunks per slice)
 //   grid term:  64 blocks per image:  64 / (H W / 128 * Cout / 64)
 //   at most 8 slices, 4 where an image has several tiles (H W >= 256); 2 slices never pay: 1
-static int p2f(long v) { int p = 1; while (2L * p <= v) p <<= 1; return p; }
-static int direct_split(const P2LConv* d) {
-  const int kc = (d->taps == 9) ? 16 : (d->Cin % 32 == 0 ? 32 : 16);
-  const int nchunks = d->Cin / kc;
-  const long hw = (long)d->H * d->W;
-  int s = p2f((long)d->Cin * d->taps / 128);
-  const int g = p2f(524288L / (hw * d->Cout > 0 ? hw * d->Cout : 1));
+int p2f(long v) { int p = 1; while (2L * p <= v) p <<= 1; return p; }
+// (the terms the stride-1 rule and the sub-pixel gradient's share: work, grid, cap, chunks a slice must keep)
+int shape_split(long work, long hw, int Cout, int nchunks, int min_chunks) {
+  int s = p2f(work / 128);
+  const int g = p2f(524288L / (hw * Cout > 0 ? hw * Cout : 1));
   if (g < s) s = g;
   const int cap = hw >= 256 ? 4 : 8;
   if (s > cap) s = cap;
-  // keep >= 2 chunks of work per slice for 3x3 (18 tap-chunks), >= 4 for 1x1
-  const int min_chunks = (d->taps == 9) ? 2 : 4;
   while (s > 1 && nchunks / s < min_chunks) s >>= 1;
   return s <= 2 ? 1 : s;
+}
+int direct_split(const P2LConv* d, int nchunks) {
+  // keep >= 2 chunks of work per slice for 3x3 (18 tap-chunks), >= 4 for 1x1
+  return shape_split((long)d->Cin * d->taps, (long)d->H * d->W, d->Cout, nchunks, (d->taps == 9) ? 2 : 4);
 }
 
 // ... with the weights resident in registers (p2l_h2r.hip: persistent blocks, bit-identical results): the
 // 64 -> 64 channel layers of whole 8x16-pixel tiles that never split K.  Shape and format only.
-static bool direct_h2r(const P2LConv* d) {
-  if ((d->form & P2L_FORM_NO_H2R) || !direct_h2(d)) return false;
+bool direct_h2r(const P2LConv* d, bool h2, int direct_slices) {
+  if ((d->form & P2L_FORM_NO_H2R) || !h2) return false;
   if (!p2l_h2r_shape(d->taps, d->ups, d->H, d->W, d->Cin, d->Cout, d->x_ld)) return false;
-  return d->H * d->W >= 128 && direct_split(d) <= 1;
+  return d->H * d->W >= 128 && direct_slices <= 1;
 }
-
 
 // K slices of the sub-pixel INPUT-GRADIENT form of a stride-2 transposed conv (ups 3, ext 1: StyleGAN2's up
 // convs) in the fp16 x 2 kernel, whose chunk loop walks (phase plane, channel chunk) and takes a slice like the
 // stride-1 kernel does: the 8^2 ... 32^2 layers of a few candidates were 8 - 32 blocks running 128 chunks each
 // (0.20 - 0.23 ms for 5 - 50 us of work, profiles/round6_sg2_1024_layers.txt).  Shape and format only.
-static int subpix_bwd_split(const P2LConv* d) {
-  if (d->ups != 3 || !d->ext || !direct_h2(d)) return 1;
-  ConvK k{};
-  if (choose_tile(d, k) != P2L_OK || k.partial) return 1;
-  const long hw = (long)(d->H >> 1) * (d->W >> 1);
-  int s = p2f((long)d->Cin * 16 / 128);
-  const int g = p2f(524288L / (hw * d->Cout > 0 ? hw * d->Cout : 1));
-  if (g < s) s = g;
-  const int cap = hw >= 256 ? 4 : 8;
-  if (s > cap) s = cap;
-  const int nchunks = 4 * (d->Cin / 16);
-  while (s > 1 && nchunks / s < 8) s >>= 1;
-  return s <= 2 ? 1 : s;
+int subpix_bwd_split(const P2LConv* d, bool h2, bool whole_tiles) {
+  if (d->ups != 3 || !d->ext || !h2 || !whole_tiles) return 1;
+  return shape_split((long)d->Cin * 16, (long)(d->H >> 1) * (d->W >> 1), d->Cout, 4 * (d->Cin / 16), 8);
 }
 
-extern "C" int p2l_conv_suggest_splitk(const P2LConv* d) {
-  ConvK k{};
-  if (d && d->ups == 3 && d->ext) return subpix_bwd_split(d);
-  if (!d || d->ups >= 2) return 1;       // the other sub-pixel modes never split K
-  if (choose_tile(d, k) == P2L_OK && wino_split(d) > 1 && !(d->form & P2L_FORM_WINO_ANY) &&
-      (d->H / 8) * (d->W / 16) * (d->Cout / 64) < 64)
-    return wino_split(d);                // small-grid Winograd layer: a function of the shape only
-  if (choose_tile(d, k) != P2L_OK || k.partial || wino_shape(d) || pw_any(d)) return 1;
-  return direct_split(d);
-}
-
-// the 16x16 Winograd kernel in the fp16 x 2 arithmetic: 64 partial maxima per image in front of
-// the split-K slices
-static bool wino_h2(const P2LConv* d) {
-  return wino_shape(d) && d->H % 16 == 0 && d->W % 16 == 0 &&
-         !(d->form & (P2L_FORM_WINO_8X16 | P2L_FORM_WINO_BF3));
-}
-// P2LAmax producers: launches whose blocks each cover one tile of ONE image and end in the shared
-// epilogue -- the unsplit 16x16 Winograd kernel (16x16 pixels x 64 channels) and the kernels that
-// go through epilogue_vec (direct 3x3, sub-pixel forward: 4 phases, 1x1 in both arithmetics:
-// 128 pixels x 32 / 64 channels); every WAVE of a block writes its own partial.  Split-K launches leave
-// theirs through the finish kernel (one per 64 items).  The 8x16 Winograd kernel, the thin-output
-// image kernel and unsplit tiles that span images write none.
-static int effective_splitk(const P2LConv* d);
 // the 16-byte finish kernel of a split-K launch: every pitch it touches a multiple of four floats
 // (descriptor only: p2l_conv_amax_slots and the launch must agree)
-static bool finish_v4_ok(const P2LConv* d) {
+bool finish_v4_ok(const P2LConv* d) {
 #ifdef P2L_AB_SCALAR_FINISH           // (A/B build: the 4-byte finish kernel for every split-K launch.  That kernel has no
                                       //  oscale / noise / leaky-ReLU term: such a launch -- StyleGAN2's styled convs -- is
                                       //  refused with P2L_EUNSUP in this build, which therefore serves BigGAN only)
@@ -1282,11 +1263,96 @@ static bool finish_v4_ok(const P2LConv* d) {
   return d->n_store % 4 == 0 && d->Cout % 4 == 0 && d->y_ld % 4 == 0 && d->yp_ld % 4 == 0 &&
          d->res_ld % 4 == 0 && d->mask_ld % 4 == 0;
 }
-extern "C" int p2l_conv_amax_slots(const P2LConv* d) {
-  if (!d) return 0;
-  if (wino_shape(d)) {
+
+// `nchunks` chunks in at most `want` slices: the slice length first, then the count that length leaves
+void cut(int nchunks, int want, int& splitk, int& per) {
+  if (want > nchunks) want = nchunks;
+  per = cdiv(nchunks, want);
+  splitk = cdiv(nchunks, per);
+}
+// floats of `slices` partial outputs [B, H, W, Cout] in the workspace, behind the maxima of an fp16 x 2 launch
+size_t slice_bytes(const P2LConv* d, int slices) {
+  return slices > 1 ? (size_t)slices * d->B * d->H * d->W * d->Cout * sizeof(float) : 0;
+}
+
+// Everything about a launch that is a function of its descriptor alone.  What depends on the ARGUMENTS of the
+// launch -- a workspace that is there and large enough (use_h2), maxima handed over, StyleGAN2 terms that send a
+// thin shape to the generic kernel, a fused activation backward -- is resolved by the launcher from this.
+enum { FAM_WINO, FAM_PW, FAM_THIN /* candidate: the launch has the last word */, FAM_SUBPIX, FAM_DIRECT,
+       FAM_PW_SMALL, FAM_1X1 };
+enum { FIN_NONE, FIN_V4, FIN_SCALAR, FIN_WINO4 };       // the finish kernel of a sliced launch
+struct ConvRoute {
+  int tile_rc;                  // choose_tile's answer; `tile` means nothing unless P2L_OK
+  ConvK tile;                   // the tile fields alone: the launcher's ConvK starts as a copy
+  int family;
+  int thin;                     // thin_shape
+  bool wino, wino_sliced, pw;
+  bool h2;                      // the family's fp16 x 2 form is eligible (wino_h2 | direct_h2 | pw_small_h2)
+  bool h2r;                     // direct_h2r
+  int kc, bn, nchunks;          // nchunks: of the launch's own chunk loop (sub-pixel gradient: 4 planes x Cin / 16)
+  int wino_slices, direct_slices, subpix_slices;   // what each slicing rule suggests for the shape (1 = none)
+  int splitk, chunks_per_split; // what the launch runs with, under whichever rule takes the descriptor
+  int splitk_ws;                // slices the workspace is checked for: the stride-1 rule's answer to d->splitk,
+                                // also where the sub-pixel rule decides the launch (the route of a launch)
+  int finish;
+  size_t amax_bytes, slice_bytes;   // workspace: maxima of an fp16 x 2 launch, then splitk_ws slices
+};
+int conv_route(const P2LConv* d, ConvRoute& r) {
+  r = ConvRoute{};
+  r.tile_rc = choose_tile(d, r.tile);
+  const bool whole = r.tile_rc == P2L_OK && !r.tile.partial;
+  r.kc = conv_kc(d->taps, d->Cin);
+  const int nc = d->Cin / r.kc;
+  r.wino_slices = wino_split(d);
+  r.wino = wino_shape(d, r.wino_slices);
+  r.wino_sliced = r.wino && d->splitk > 1 && r.wino_slices == d->splitk;
+  r.pw = pw_shape(d);
+  r.thin = thin_shape(d);
+  const bool dh2 = direct_h2(d, r.wino), pws = pw_small_h2(d, r.pw, whole);
+  r.h2 = wino_h2(d, r.wino) || dh2 || pws;
+  r.direct_slices = direct_split(d, nc);
+  r.subpix_slices = subpix_bwd_split(d, dh2, whole);
+  r.h2r = direct_h2r(d, dh2, r.direct_slices);
+  // (an h2r-shaped layer keeps 64-channel tiles in the chunked kernel too: its launches may take either kernel,
+  //  by their epilogue, and both must fill the same maxima slots)
+  r.bn = r.h2r ? 64 : choose_bn(d, r.tile.n_mtiles);
+  r.family = r.wino ? FAM_WINO : r.pw ? FAM_PW : r.thin >= 0 ? FAM_THIN : d->ups >= 2 ? FAM_SUBPIX
+           : d->taps == 9 ? FAM_DIRECT : pws ? FAM_PW_SMALL : FAM_1X1;
+  // the stride-1 rule: any count up to the chunks there are; the Winograd and the full-tile / thin pointwise
+  // kernels never take one (the K-sliced Winograd form: exactly its own)
+  r.splitk_ws = 1;
+  int per = nc;
+  const bool unsliced = d->splitk < 1 || (r.wino && !r.wino_sliced) || r.pw || r.thin >= 0;
+  if (!unsliced && nc > 0) cut(nc, d->splitk, r.splitk_ws, per);
+  r.nchunks = nc;
+  r.splitk = r.splitk_ws;
+  r.chunks_per_split = per;
+  if (r.wino_sliced) {
+    r.splitk = d->splitk;
+    r.chunks_per_split = nc / r.splitk;                  // (the factor divides the chunk count)
+  } else if (d->ups >= 2) {
+    // the sub-pixel forms: slices only for the input gradient of a transposed conv in the fp16 x 2 kernel
+    r.nchunks = (d->ups == 3) ? 4 * (d->Cin / 16) : d->Cin / 16;
+    r.splitk = 1;
+    if (d->splitk > 1 && r.subpix_slices > 1) cut(r.nchunks, d->splitk, r.splitk, per);
+    r.chunks_per_split = cdiv(r.nchunks, r.splitk);
+  }
+  r.finish = r.splitk <= 1 ? FIN_NONE : r.wino_sliced ? FIN_WINO4 : finish_v4_ok(d) ? FIN_V4 : FIN_SCALAR;
+  r.amax_bytes = r.h2 ? (size_t)d->B * 64 * sizeof(float) : 0;
+  r.slice_bytes = slice_bytes(d, r.splitk_ws);
+  return r.tile_rc;
+}
+
+// P2LAmax producers: launches whose blocks each cover one tile of ONE image and end in the shared
+// epilogue -- the unsplit 16x16 Winograd kernel (16x16 pixels x 64 channels) and the kernels that
+// go through epilogue_vec (direct 3x3, sub-pixel forward: 4 phases, 1x1 in both arithmetics:
+// 128 pixels x 32 / 64 channels); every WAVE of a block writes its own partial.  Split-K launches leave
+// theirs through the finish kernel (one per 64 items).  The 8x16 Winograd kernel, the thin-output
+// image kernel and unsplit tiles that span images write none.
+int amax_slots(const P2LConv* d, const ConvRoute& r) {
+  if (r.wino) {
     if (d->H % 16 || d->W % 16 || (d->form & P2L_FORM_WINO_8X16)) return 0;
-    if (d->splitk > 1 && wino_split(d) == d->splitk) {
+    if (r.wino_sliced) {
       // K-sliced launch: the float4 finish kernel writes the tensor, one partial per wave of 64
       // (quad, 4 channels) items -- when a wave never straddles two images
       const int per_image = (d->H / 2) * (d->W / 2) * (d->n_store / 4);
@@ -1294,67 +1360,184 @@ extern "C" int p2l_conv_amax_slots(const P2LConv* d) {
     }
     return (d->H / 16) * (d->W / 16) * (d->Cout / 64) * 8;     // (one partial per wave)
   }
-  if (d->ups == 3 && effective_splitk(d) > 1) return 0;   // (the finish kernel runs on the low-res grid: no slots)
-  if (effective_splitk(d) > 1) {
+  if (r.splitk > 1) {
+    if (d->ups == 3) return 0;                    // (the finish kernel runs on the low-res grid: no slots)
     // split-K launch of the direct kernels: a finish kernel writes the tensor, one partial per block of
     // 64 items -- (quad, 4 channels) for the 16-byte kernel, (quad, channel) for the scalar one -- when
     // a block never straddles two images.  (The hand-over thereby follows the LAYER, not the split-K
     // choice a batch size brings with it.)
-    const int per_image = (d->H / 2) * (d->W / 2) * (finish_v4_ok(d) ? d->n_store / 4 : d->n_store);
+    const int per_image = (d->H / 2) * (d->W / 2) * (r.finish == FIN_V4 ? d->n_store / 4 : d->n_store);
     return (per_image % 64 == 0) ? per_image / 64 : 0;
   }
-  ConvK k{};
-  if (choose_tile(d, k) != P2L_OK || k.tb_log != 0 || k.partial) return 0;
-  const int tm = thin_shape(d);
-  if (tm >= 0) {                                       // three-channel image convs: the thin-input kernel only
-    const bool geom = k.tw_log == 4 && k.th_log == 3;
-    return (tm == 1 && geom) ? k.tiles_x * k.tiles_y * 4 : 0;
-  }
+  const ConvK& t = r.tile;
+  if (r.tile_rc != P2L_OK || t.tb_log != 0 || t.partial) return 0;
+  if (r.thin >= 0)                                     // three-channel image convs: the thin-input kernel only
+    return (r.thin == 1 && t.tw_log == 4 && t.th_log == 3) ? t.tiles_x * t.tiles_y * 4 : 0;
   // (both pointwise forms tile 64 output channels whatever choose_bn says for the grid.  Until round 5
   //  the small-grid form was counted with choose_bn's 32 where the grid made it say so -- 16^2 256->1024 at
   //  9 and 18 candidates: twice the slots its blocks write, the reader took the maximum over stale ring
   //  contents as well and an image's power of two followed what had used the ring set before.)
 #ifdef P2L_AB_PW_SLOTS_R4             // (A/B build: the round-4 count, for the test that has to fail on it)
-  const int nnt = pw_shape(d) ? d->Cout / 64 : d->Cout / choose_bn(d, k.n_mtiles);
+  const int nnt = r.pw ? d->Cout / 64 : d->Cout / choose_bn(d, t.n_mtiles);
 #else
   // (the register-resident 64-channel kernel writes all 64 channels of a tile from one block)
-  const int nnt = (pw_shape(d) || pw_small_h2(d)) ? d->Cout / 64 : direct_h2r(d) ? 1 : d->Cout / choose_bn(d, k.n_mtiles);
+  const int nnt = (r.pw || r.family == FAM_PW_SMALL) ? d->Cout / 64 : r.h2r ? 1 : d->Cout / r.bn;
 #endif
-  return k.tiles_x * k.tiles_y * nnt * (d->ups == 2 ? 4 : 1) * 4;
+  return t.tiles_x * t.tiles_y * nnt * (d->ups == 2 ? 4 : 1) * 4;
 }
-extern "C" size_t p2l_conv_workspace_bytes(const P2LConv* d) {
-  const size_t h2 = (wino_h2(d) || direct_h2(d) || pw_small_h2(d)) ? (size_t)d->B * 64 * sizeof(float) : 0;
-  if (d->splitk <= 1) return h2;
-  return h2 + (size_t)d->splitk * d->B * d->H * d->W * d->Cout * sizeof(float);
+// per-image partial sums of a fused activation backward: one per tile in the kernel, one per quad of the grid the
+// finish kernel walks (low-res for ups 3) on a sliced launch
+int arb_nblk(const P2LConv* d, const ConvRoute& r, bool sliced) {
+  const int sh = d->ups == 3 ? 2 : 1;
+  if (sliced) return (d->H >> sh) * (d->W >> sh);
+  return r.tile_rc == P2L_OK ? r.tile.n_mtiles / d->B : 0;
 }
 
-// the split-K factor conv_launch_impl ends up with for d->splitk
-static int effective_splitk(const P2LConv* d) {
-  if (d->splitk > 1 && d->ups == 3 && d->ext && subpix_bwd_split(d) > 1) {
-    const int nchunks = 4 * (d->Cin / 16);
-    const int sk = d->splitk > nchunks ? nchunks : d->splitk;
-    return cdiv(nchunks, cdiv(nchunks, sk));
+// (A tap-row pipelined, double-buffered variant of the bf16x3 kernel - one barrier per 3 taps
+// instead of two per chunk - measured slower, 149-166 vs 158-188 TFLOP/s, and was removed;
+// see DESIGN.md 4.1 and the repository history.)
+// One instance of conv_mfma_kernel: its LDS attribute once, then the launch.
+template <int TAPS, int BN, int KC, int A_ITERS, int PRO, bool UPS, bool BF3>
+void launch_instance(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
+  auto kfn = conv_mfma_kernel<TAPS, BN, KC, A_ITERS, PRO, UPS, BF3>;
+  static std::atomic<bool> attr_set{false};
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
   }
-  if (d->splitk > 1 && d->ups == 0 && wino_split(d) == d->splitk && wino_shape(d)) return d->splitk;
-  if (d->splitk <= 1 || d->ups >= 2 || wino_shape(d) || pw_any(d)) return 1;
-  const int kc = (d->taps == 9) ? 16 : (d->Cin % 32 == 0 ? 32 : 16);
-  const int nchunks = d->Cin / kc;
-  int sk = d->splitk > nchunks ? nchunks : d->splitk;
-  const int per = cdiv(nchunks, sk);
-  return cdiv(nchunks, per);
+  hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, k);
+}
+// ... by prologue and fused nearest upsample (the sub-pixel kernel, TAPS = 4, has no upsampling instance)
+template <int TAPS, int BN, int KC, int A_ITERS, bool BF3 = false>
+int launch_conv(const ConvK& k, int pro, int ups, dim3 grid, size_t lds, hipStream_t st) {
+  auto by_pro = [&](auto ups_c) {
+    constexpr bool UPS = decltype(ups_c)::value;
+    if (pro == P2L_PRO_NONE) launch_instance<TAPS, BN, KC, A_ITERS, P2L_PRO_NONE, UPS, BF3>(k, grid, lds, st);
+    else if (pro == P2L_PRO_AFFINE_RELU) launch_instance<TAPS, BN, KC, A_ITERS, P2L_PRO_AFFINE_RELU, UPS, BF3>(k, grid, lds, st);
+    else launch_instance<TAPS, BN, KC, A_ITERS, P2L_PRO_AFFINE, UPS, BF3>(k, grid, lds, st);
+    return p2l_check_launch();
+  };
+  if constexpr (TAPS != 4)
+    if (ups) return by_pro(std::true_type{});
+  return by_pro(std::false_type{});
+}
+// ... by channel tile, patch size (small: three staging rounds instead of five) and arithmetic: the 3x3 (TAPS = 9)
+// and sub-pixel (TAPS = 4) launches
+template <int TAPS>
+int launch_tiled(const ConvK& k, int bn, bool small, bool bf3, int pro, int ups, dim3 grid, size_t lds, hipStream_t st) {
+  if (bf3) {
+    if (bn == 64) return small ? launch_conv<TAPS, 64, 16, 3, true>(k, pro, ups, grid, lds, st)
+                               : launch_conv<TAPS, 64, 16, 5, true>(k, pro, ups, grid, lds, st);
+    return small ? launch_conv<TAPS, 32, 16, 3, true>(k, pro, ups, grid, lds, st)
+                 : launch_conv<TAPS, 32, 16, 5, true>(k, pro, ups, grid, lds, st);
+  }
+  if (bn == 64) return small ? launch_conv<TAPS, 64, 16, 3>(k, pro, ups, grid, lds, st)
+                             : launch_conv<TAPS, 64, 16, 5>(k, pro, ups, grid, lds, st);
+  return small ? launch_conv<TAPS, 32, 16, 3>(k, pro, ups, grid, lds, st)
+               : launch_conv<TAPS, 32, 16, 5>(k, pro, ups, grid, lds, st);
+}
+// dynamic LDS of conv_mfma_kernel: the staged patch + the weight tile, `pitch` floats per row; the vectorised
+// epilogue re-uses it for 4 wave tiles of 32 x (bn+4)
+size_t conv_lds(int a_rows_lds, int taps, int bn, int pitch) {
+  const size_t lds = (size_t)(a_rows_lds + taps * bn) * pitch * sizeof(float);
+  const size_t lds_epi = (size_t)4 * 32 * (bn + 4) * sizeof(float);
+  return lds_epi > lds ? lds_epi : lds;
+}
+// The slices of a launch meet in a deterministic finish kernel: fixed-order sum, then the whole epilogue (bias /
+// residual / activation / fused activation backward), on the grid k tiles (low-res for the sub-pixel gradient).
+int launch_finish(const ConvK& k, int kind, hipStream_t st) {
+  const size_t quads = (size_t)k.B * (k.H >> 1) * (k.W >> 1);
+  if (kind == FIN_WINO4)
+    hipLaunchKernelGGL(conv_splitk_finish4, dim3(cdiv(quads * (k.n_store >> 2), 256)), dim3(256), 0, st, k);
+  else if (kind == FIN_V4)
+    hipLaunchKernelGGL(conv_splitk_finish_v4, dim3(cdiv(quads * (k.n_store >> 2), 64)), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL(conv_splitk_finish, dim3(cdiv(quads * k.n_store, 64)), dim3(256), 0, st, k);
+  return p2l_check_launch();
 }
 
-static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvExtra* ex,
-                            const float* x, const float* w,
-                            const float* bias, const float* pro_s,
-                            const float* pro_t, const float* res,
-                            const float* mask, float* y, float* yp,
-                            void* workspace, size_t ws_bytes, void* stream, int* dry_class = nullptr) {
-  // dry_class: nothing is launched; *dry_class = the epilogue class the launch would run (p2l_conv_epilogue_class)
+// The profiler's slot of one launch.  It is taken behind every refusal and its destructor records the end event,
+// so no path -- a failed launch, a route added later -- can leave an event pair half recorded (p2l_prof_totals
+// would then fail for the whole profiled section).  took(): the family's corrections to what the slot assumed.
+struct ProfSlot {
+  int slot = -1;
+  hipStream_t st;
+  ProfSlot(const P2LConv* d, const ConvRoute& r, const P2LArb* arb, bool y, bool yp, bool res, bool mask,
+           hipStream_t st_, bool dry) : st(st_) {
+    bool ok = g_prof.on && !dry;
+    if (ok) {
+      // an event pair recorded during stream capture becomes graph nodes and can never be read
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) ok = false;
+    }
+    if (ok) {
+      std::lock_guard<std::mutex> lk(g_prof.mu);
+      if (g_prof.on && g_prof.n < (int)g_prof.flops.size() && (g_prof.seq++ % g_prof.period) == g_prof.phase)
+        slot = g_prof.n++;
+    }
+    if (slot < 0) return;
+    g_prof.flops[slot] = d->algo_flops > 0.0 ? d->algo_flops
+                                             : 2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * d->taps;
+    // what the MFMAs actually multiply: padded channel counts, and for the sub-pixel forms 4
+    // phase-taps per high-resolution output pixel instead of 9
+    g_prof.xflops[slot] = 2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * (d->ups >= 2 ? 4 : d->taps);
+    g_prof.kind[slot] = d->taps == 9 ? 0 : 1;
+    g_prof.fam[slot] = P2L_PROF_FAM_OTHER;
+    g_prof.nprod[slot] = (d->wfmt == P2L_WFMT_F32 || (d->taps == 1 && !r.pw)) ? 16 : 6;
+    g_prof.shape[slot] = {d->taps, d->B, d->H, d->W, d->Cin, d->Cout, d->ups, d->pro,
+                          arb ? (arb->skip ? 2 : 1) : 0, d->splitk};
+    // algorithmic bytes: every operand tensor once (input at ITS resolution, outputs,
+    // residual / mask, the fused activation-backward operands) + the packed weights
+    const double opx = (double)d->B * d->H * d->W;
+    const double ipx = d->ups == 1 || d->ups == 2 ? opx / 4 : (d->ups == 3 ? opx * 4 : opx);
+    double by = ipx * d->Cin + (double)d->taps * d->Cin * d->Cout;
+    if (y) by += opx * d->n_store;
+    if (yp) by += opx / 4 * d->n_store;
+    if (res) by += (d->res_ups ? opx / 4 : opx) * d->n_store;
+    if (mask) by += opx * d->n_store;
+    if (arb) by += opx * d->n_store * (arb->skip ? 2.0 : 1.0);
+    g_prof.bytes[slot] = 4.0 * by;
+    g_prof.wbytes[slot] = 4.0 * ((y ? opx * d->n_store : 0.0) + (yp ? opx / 4 * d->n_store : 0.0));
+    (void)hipEventRecord(g_prof.ev[2 * slot], st);
+  }
+  ProfSlot(const ProfSlot&) = delete;
+  ~ProfSlot() { if (slot >= 0) (void)hipEventRecord(g_prof.ev[2 * slot + 1], st); }
+  void took(int fam, int nprod = 0, double xflops = 0.0) {
+    if (slot < 0) return;
+    g_prof.fam[slot] = fam;
+    if (nprod) g_prof.nprod[slot] = nprod;
+    if (xflops > 0.0) g_prof.xflops[slot] = xflops;
+  }
+};
+
+// One launch on its way: the descriptor, its route, the kernel arguments and what the call's arguments decided.
+struct Launch {
+  const P2LConv* d;
+  const P2LArb* arb;
+  const P2LConvExtra* ex;
+  const float* w;
+  const float* res;
+  const float* mask;
+  ConvRoute r;
+  WeightImages wi;
+  ConvK k;
+  bool use_h2;          // the fp16 x 2 form: eligible (r.h2) and the workspace holds its maxima
+  hipStream_t st;
+  int* dry_class;       // nothing is launched; *dry_class = the epilogue class the launch would run
+  ProfSlot* prof;
+  const unsigned* tail(size_t at) const { return reinterpret_cast<const unsigned*>(w + at); }
+};
+
+// ---- part 1: every check and refusal, and the kernel arguments that follow from the call ----
+int conv_prepare(Launch& L, const float* x, const float* bias, const float* pro_s, const float* pro_t, float* y,
+                 float* yp, void* workspace, size_t ws_bytes) {
+  const P2LConv* d = L.d;
+  const P2LArb* arb = L.arb;
+  const P2LConvExtra* ex = L.ex;
+  const float *w = L.w, *res = L.res, *mask = L.mask;
   if (!d || !x || !w) return P2L_EINVAL;
   if (d->taps != 1 && d->taps != 9) return P2L_EINVAL;
-  const int kc = (d->taps == 9) ? 16 : (d->Cin % 32 == 0 ? 32 : 16);
-  if (d->Cin % kc || d->Cout % 32 || d->B < 1) return P2L_EINVAL;
+  if (d->Cin % conv_kc(d->taps, d->Cin) || d->Cout % 32 || d->B < 1) return P2L_EINVAL;
   if (d->x_ld % 4 || d->x_ld < d->Cin) return P2L_EINVAL;
   if (d->pro != P2L_PRO_NONE && (!pro_s || !pro_t || d->pro_bstride % 4)) return P2L_EINVAL;
   if (d->pool != P2L_POOL_NONE && !yp) return P2L_EINVAL;
@@ -1365,13 +1548,10 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     return P2L_EUNSUP;
   if (d->taps == 1 && d->wfmt != P2L_WFMT_F32 && d->wfmt != P2L_WFMT_PW) return P2L_EUNSUP;
   if (d->ups < 0 || d->ups > 3) return P2L_EINVAL;
-  if (d->w_floats != 0) {
-    // the packed formats carry no tag: the images a launch of (taps, ups, Cin, Cout, wfmt) may read sit
-    // at fixed offsets of a buffer of exactly this size; a shorter one was packed for something else
-    const size_t need = d->ups >= 2 ? p2l_packed_subpix_weight_floats(d->Cout, d->Cin, d->wfmt)
-                                    : p2l_packed_weight_floats(d->taps, d->Cout, d->Cin, d->wfmt);
-    if (d->w_floats < 0 || (size_t)d->w_floats < need) return P2L_EINVAL;
-  }
+  // the packed formats carry no tag: the images a launch of (taps, ups, Cin, Cout, wfmt) may read sit
+  // at fixed offsets of a buffer of exactly this size; a shorter one was packed for something else
+  L.wi = weight_images(d->taps, d->ups >= 2, d->Cout, d->Cin, d->wfmt);
+  if (d->w_floats != 0 && (d->w_floats < 0 || (size_t)d->w_floats < L.wi.total)) return P2L_EINVAL;
   if (d->n_store < 1 || d->n_store > d->Cout || d->n_store % 4) return P2L_EINVAL;
   if ((y && d->y_ld % 4) || (yp && d->yp_ld % 4) || (res && d->res_ld % 4) ||
       (mask && d->mask_ld % 4))
@@ -1398,7 +1578,10 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     if (px * ldmax >= ((int64_t)1 << 31)) return P2L_EUNSUP;
   }
 
-  ConvK k{};
+  ConvRoute& r = L.r;
+  if (int rc = conv_route(d, r)) return rc;
+  ConvK& k = L.k;
+  k = r.tile;
   k.x = x; k.w = w; k.bias = bias; k.pro_s = pro_s; k.pro_t = pro_t;
   k.res = res; k.mask = mask; k.y = y; k.yp = yp; k.ws = (float*)workspace;
   k.B = d->B; k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Cout = d->Cout;
@@ -1407,11 +1590,12 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   k.alpha = d->alpha; k.act = d->act; k.pool = d->pool; k.res_ups = d->res_ups;
   k.ups = d->ups;
   k.form = d->form;
-  int rc = choose_tile(d, k);
-  if (rc) return rc;
   k.iH = d->H; k.iW = d->W; k.ibH = d->H; k.ibW = d->W; k.obH = d->H; k.obW = d->W;
   k.hp = halo_pitch(1 << k.tw_log, d->wfmt != P2L_WFMT_F32 && d->taps == 9);
-  const bool bf3_3x3 = d->taps == 9 && d->wfmt != P2L_WFMT_F32;
+  k.n_ntiles = d->Cout / r.bn;
+  k.nchunks = r.nchunks;
+  k.splitk = r.splitk;
+  k.chunks_per_split = r.chunks_per_split;
   if (ex) {
     k.oscale = ex->oscale; k.oscale_bstride = ex->oscale_bstride;
     k.noise = ex->noise; k.noise_w = ex->noise_w;
@@ -1419,13 +1603,11 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
   // the scalar finish kernel of a split-K launch (conv_splitk_finish -> epilogue_quad: a pitch field that is no
   // multiple of four, even that of an absent operand) has no demodulation, noise or leaky-ReLU term; the 16-byte
   // one (epi_item) has all three
-  if ((k.oscale || k.noise || d->act == P2L_ACT_LRELU_SQRT2) && !finish_v4_ok(d) && !wino_shape(d) &&
-      effective_splitk(d) > 1)
-    return P2L_EUNSUP;
+  if ((k.oscale || k.noise || d->act == P2L_ACT_LRELU_SQRT2) && r.finish == FIN_SCALAR) return P2L_EUNSUP;
   if (k.partial && (arb || d->pool != P2L_POOL_NONE || d->splitk > 1)) return P2L_EUNSUP;
   if (arb) {
     // one image per tile for the in-kernel form; with split-K the finish kernel does it
-    if ((k.tb_log != 0 && effective_splitk(d) <= 1) || res || mask || d->act != P2L_ACT_NONE ||
+    if ((k.tb_log != 0 && r.splitk <= 1) || res || mask || d->act != P2L_ACT_NONE ||
         d->pool == P2L_POOL_MAX || !arb->x || !arb->s || !arb->t || !arb->partial)
       return P2L_EUNSUP;
     k.arb_x = arb->x; k.arb_s = arb->s; k.arb_t = arb->t; k.arb_skip = arb->skip;
@@ -1434,23 +1616,10 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     k.arb_nblk = k.n_mtiles / d->B;
     k.arb_nomask = arb->nomask;
   }
-  // (an h2r-shaped layer keeps 64-channel tiles in the chunked kernel too: its launches may take either kernel,
-  //  by their epilogue, and both must fill the same maxima slots)
-  const int bn = direct_h2r(d) ? 64 : choose_bn(d, k.n_mtiles);
-  k.n_ntiles = d->Cout / bn;
-  k.nchunks = d->Cin / kc;
-  const bool wino_sliced = wino_shape(d) && d->splitk > 1 && wino_split(d) == d->splitk;
-  k.splitk = (d->splitk < 1 || (wino_shape(d) && !wino_sliced) || pw_any(d)) ? 1 : d->splitk;
-  if (k.splitk > k.nchunks) k.splitk = k.nchunks;
-  k.chunks_per_split = cdiv(k.nchunks, k.splitk);
-  k.splitk = cdiv(k.nchunks, k.chunks_per_split);
-  // fp16 x 2 Winograd: the partial maxima sit at the head of the workspace; a caller that gives
+  // fp16 x 2 forms: the partial maxima sit at the head of the workspace; a caller that gives
   // none gets the bf16 x 3 arithmetic
-  const bool h2_direct = direct_h2(d), h2_pw_small = pw_small_h2(d);
-  const size_t h2_bytes = (wino_h2(d) || h2_direct || h2_pw_small) ? (size_t)d->B * 64 * sizeof(float) : 0;
-  const bool use_h2 = h2_bytes && workspace &&
-                      ws_bytes >= h2_bytes + (k.splitk > 1 ? (size_t)k.splitk * d->B * d->H * d->W * d->Cout * sizeof(float) : 0);
-  if (use_h2) {
+  L.use_h2 = r.amax_bytes && workspace && ws_bytes >= r.amax_bytes + r.slice_bytes;
+  if (L.use_h2) {
     k.amax = (float*)workspace;
     k.ws = (float*)workspace + (size_t)d->B * 64;
   }
@@ -1460,15 +1629,15 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
     // kernel (which takes the fp16 x 2 form only with handed-over maxima)
     // (maxima recorded with a prologue applied say nothing about the raw tensor: not usable without one)
     if (am && am->in && am->in_n > 0 && !(am->in_applied && d->pro == P2L_PRO_NONE) &&
-        (use_h2 || (pw_shape(d) && !(d->form & P2L_FORM_WINO_BF3)))) {
+        (L.use_h2 || (r.pw && !(d->form & P2L_FORM_WINO_BF3)))) {
       k.amax_in = am->in; k.amax_in_n = am->in_n;
       k.amax_in_applied = am->in_applied ? 1 : 0;
     }
-    int nslots = (am && (am->out || am->outp)) ? p2l_conv_amax_slots(d) : 0;
-    if (thin_shape(d) >= 0 && ex && (ex->oscale || ex->noise)) nslots = 0;   // (generic kernel then)
+    int nslots = (am && (am->out || am->outp)) ? amax_slots(d, r) : 0;
+    if (r.thin >= 0 && ex && (ex->oscale || ex->noise)) nslots = 0;   // (generic kernel then)
     // (the slot count was promised for the fp16 x 2 small-grid pointwise kernel: 64-channel tiles)
-    if (nslots > 0 && h2_pw_small && !use_h2 && effective_splitk(d) <= 1) return P2L_EWS;
-    if (nslots > 0 && direct_h2r(d) && !use_h2) return P2L_EWS;   // (... for the register-resident kernel: one block per tile)
+    if (nslots > 0 && r.family == FAM_PW_SMALL && !L.use_h2 && r.splitk <= 1) return P2L_EWS;
+    if (nslots > 0 && r.h2r && !L.use_h2) return P2L_EWS;   // (... for the register-resident kernel: one block per tile)
     if (nslots > 0) { k.amax_out = am->out; k.amax_outp = am->outp; k.amax_out_n = nslots; }
     if (nslots > 0 && am->out && am->next_s && am->next_t && !arb) {
       // the reader's affine is read as [B][next_bstride] rows of n_store floats, like oscale (0 = shared by the images)
@@ -1476,354 +1645,283 @@ static int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvEx
       k.amax_ps = am->next_s; k.amax_pt = am->next_t; k.amax_pbstride = am->next_bstride;
     }
   }
-  if (k.splitk > 1) {
-    const size_t need = (use_h2 ? h2_bytes : 0) + (size_t)k.splitk * d->B * d->H * d->W * d->Cout * sizeof(float);
-    if (!workspace || ws_bytes < need) return P2L_EWS;
-    if (arb) k.arb_nblk = p2l_conv_arb_nblk_ws(d);      // finish kernel: one partial per quad
+  if (r.splitk_ws > 1) {
+    if (!workspace || ws_bytes < (L.use_h2 ? r.amax_bytes : 0) + r.slice_bytes) return P2L_EWS;
+    if (arb) k.arb_nblk = arb_nblk(d, r, r.splitk > 1);      // finish kernel: one partial per quad
     // the 16-byte finish kernel reads the fused backward's operands in 16-byte pieces, and the maxima slots were
     // sized for it: refused here, before the slices are launched
-    if (arb && d->ups < 2 && !wino_shape(d) && finish_v4_ok(d) &&
-        (arb->x_ld % 4 || (arb->skip && arb->skip_ld % 4)))
+    if (arb && d->ups < 2 && r.finish == FIN_V4 && (arb->x_ld % 4 || (arb->skip && arb->skip_ld % 4)))
       return P2L_EINVAL;
   }
-  // sub-pixel launches: what the form does not take is refused HERE -- a launch refused behind the profiler's slot
-  // left its event pair half recorded, and p2l_prof_totals then failed for the whole profiled section
-  const int sk3 = (d->ups >= 2 && d->taps == 9 && d->splitk > 1) ? ((d->ups == 3 && d->ext) ? effective_splitk(d) : 1) : 1;
   // a 3x3 / sub-pixel block stages at most A_ITERS x 64 = 320 patch rows: choose_tile keeps every tile inside that, and
   // a tiling that did not would read unstaged LDS without any sign of it -- refused, loudly
-  if (d->taps == 9 && (1 << k.tb_log) * ((1 << k.th_log) + 2) * ((1 << k.tw_log) + 2) > 5 * 64) return P2L_EUNSUP;
+  if (d->taps == 9 && patch_rows(k) > 5 * 64) return P2L_EUNSUP;
+  // sub-pixel launches: what the form does not take is refused HERE, in front of the profiler's slot.  K slices:
+  // the input-gradient form of a transposed conv in the fp16 x 2 kernel only (subpix_bwd_split)
   if (d->ups >= 2) {
-    if (sk3 > 1 && !(use_h2 && direct_h2(d))) return P2L_EWS;
-    if (d->taps != 9 || (k.splitk != 1 && sk3 == 1) || d->Cin % 16 || d->pool != P2L_POOL_NONE ||
-        (arb && k.tb_log != 0 && sk3 == 1) || (d->ups == 2 && (res || mask)))
+    if (r.splitk > 1 && !L.use_h2) return P2L_EWS;
+    if ((r.splitk_ws != 1 && r.splitk == 1) || d->Cin % 16 || d->pool != P2L_POOL_NONE ||
+        (arb && k.tb_log != 0 && r.splitk == 1) || (d->ups == 2 && (res || mask)))
       return P2L_EUNSUP;
   }
-  hipStream_t st = (hipStream_t)stream;
+  return P2L_OK;
+}
 
-  int prof_slot = -1;
-  bool prof_ok = g_prof.on && !dry_class;
-  if (dry_class) *dry_class = EPI_GENERIC;   // (every route below answers in front of its first launch)
-  if (prof_ok) {
-    // an event pair recorded during stream capture becomes graph nodes and can never be read
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) prof_ok = false;
-  }
-  if (prof_ok) {
-    std::lock_guard<std::mutex> lk(g_prof.mu);
-    if (g_prof.on && g_prof.n < (int)g_prof.flops.size() && (g_prof.seq++ % g_prof.period) == g_prof.phase)
-      prof_slot = g_prof.n++;
-  }
-  if (prof_slot >= 0) {
-    g_prof.flops[prof_slot] = d->algo_flops > 0.0
-        ? d->algo_flops
-        : 2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * d->taps;
-    // what the MFMAs actually multiply: padded channel counts, and for the sub-pixel forms 4
-    // phase-taps per high-resolution output pixel instead of 9
-    g_prof.xflops[prof_slot] =
-        2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * (d->ups >= 2 ? 4 : d->taps);
-    g_prof.kind[prof_slot] = d->taps == 9 ? 0 : 1;
-    g_prof.fam[prof_slot] = P2L_PROF_FAM_OTHER;
-    g_prof.nprod[prof_slot] = (d->wfmt == P2L_WFMT_F32 || (d->taps == 1 && !pw_shape(d))) ? 16 : 6;
-    g_prof.shape[prof_slot] = {d->taps, d->B, d->H, d->W, d->Cin, d->Cout, d->ups, d->pro,
-                               arb ? (arb->skip ? 2 : 1) : 0, d->splitk};
-    {
-      // algorithmic bytes: every operand tensor once (input at ITS resolution, outputs,
-      // residual / mask, the fused activation-backward operands) + the packed weights
-      const double opx = (double)d->B * d->H * d->W;
-      const double ipx = d->ups == 1 || d->ups == 2 ? opx / 4 : (d->ups == 3 ? opx * 4 : opx);
-      double by = ipx * d->Cin + (double)d->taps * d->Cin * d->Cout;
-      if (y) by += opx * d->n_store;
-      if (yp) by += opx / 4 * d->n_store;
-      if (res) by += (d->res_ups ? opx / 4 : opx) * d->n_store;
-      if (mask) by += opx * d->n_store;
-      if (arb) by += opx * d->n_store * (arb->skip ? 2.0 : 1.0);
-      g_prof.bytes[prof_slot] = 4.0 * by;
-      g_prof.wbytes[prof_slot] = 4.0 * ((y ? opx * d->n_store : 0.0) + (yp ? opx / 4 * d->n_store : 0.0));
-    }
-    (void)hipEventRecord(g_prof.ev[2 * prof_slot], st);
-  }
-  // ---- Winograd F(2x2,3x3) form (p2l_wino.hip): stride-1 3x3 layers whose grid fills the
-  //      chip with 8x16-pixel x 64-channel blocks; everything else stays on the direct kernel
-  if (wino_shape(d)) {
-    ConvK kw = k;                    // (arb_nblk keeps the 128-pixel tiling of the caller's buffer)
-    kw.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
-    if (use_h2) {
-      kw.w += p2l_wino_weight_floats(d->Cout, d->Cin);
-      kw.w_tail = reinterpret_cast<const unsigned*>(kw.w + (size_t)d->Cout * d->Cin * 16);
-    }
-    kw.tiles_x = d->W / 16; kw.tiles_y = d->H / 8;
-    kw.n_mtiles = d->B * kw.tiles_x * kw.tiles_y;
-    kw.n_ntiles = d->Cout / 64;
-    kw.nchunks = d->Cin / 16;
-    if (wino_sliced) {
-      kw.splitk = d->splitk;
-      kw.chunks_per_split = kw.nchunks / kw.splitk;     // (the factor divides the chunk count)
-    } else {
-      kw.splitk = 1;
-    }
-    if (dry_class) { *dry_class = p2l_wino_epi_class(kw, d->pro); return P2L_OK; }
-    rc = p2l_wino_launch(kw, d->pro, st);
-    if (rc == P2L_OK && wino_sliced) {
-      // the slices meet in the deterministic finish kernel of the direct path: fixed-order sum,
-      // then the whole epilogue (bias / residual / activation / fused activation backward)
-      const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * (k.n_store >> 2);
-      hipLaunchKernelGGL(conv_splitk_finish4, dim3(cdiv(total, 256)), dim3(256), 0, st, k);
-      rc = p2l_check_launch();
-    }
-    if (prof_slot >= 0) {
-      g_prof.xflops[prof_slot] = 2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * 4;   // 16 per quad
-      if (use_h2) g_prof.nprod[prof_slot] = 3;
-      g_prof.fam[prof_slot] = use_h2 ? P2L_PROF_FAM_WINO_H2 : P2L_PROF_FAM_OTHER;
-      (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-    }
-    return rc;
-  }
-  // ---- 1x1 conv in the bf16x3 arithmetic (p2l_pw.hip): the image follows the fp32 weights ----
-  if (pw_shape(d)) {
-    ConvK kp = k;
-    kp.w = w + (size_t)d->Cout * d->Cin;
-    if (k.amax_in != nullptr) {                          // fp16 x 2 image behind the bf16 x 3 one
-      kp.w += (size_t)d->Cout * d->Cin * 3 / 2;
-      kp.w_tail = reinterpret_cast<const unsigned*>(kp.w + (size_t)d->Cout * d->Cin);
-    }
-    kp.n_ntiles = d->Cout / 64;
-    kp.nchunks = d->Cin / 64;
-    kp.splitk = 1;
-    if (dry_class) { *dry_class = p2l_pw_epi_class(kp, d->pro); return P2L_OK; }
-    rc = p2l_pw_launch(kp, d->pro, st);
-    if (prof_slot >= 0) {
-      if (k.amax_in != nullptr) g_prof.nprod[prof_slot] = 3;
-      g_prof.fam[prof_slot] = P2L_PROF_FAM_PW;
-      (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-    }
-    return rc;
-  }
-  // ---- 3-channel image convs ----
-  {
-    const int tm = thin_shape(d);
-    const bool geom = k.tw_log == 4 && k.th_log == 3 && k.tb_log == 0 && !k.partial && !(ex && (ex->oscale || ex->noise));
-    if (tm == 1 && geom) {
-      if (dry_class) return P2L_OK;
-      ConvK kt = k;
-      kt.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
-      kt.splitk = 1;
-      rc = p2l_thinin_launch(kt, d->pro, st);
-      if (prof_slot >= 0) {
-        g_prof.xflops[prof_slot] = 2.0 * d->B * d->H * d->W * 32.0 * d->Cout;    // K = 27 -> 32
-        g_prof.fam[prof_slot] = P2L_PROF_FAM_THIN;
-        (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-      }
-      return rc;
-    }
-    if (tm == 0 && geom && !arb && !res && !mask && d->pool == P2L_POOL_NONE && y) {
-      if (dry_class) return P2L_OK;
-      ConvK kt = k;
-      kt.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
-      kt.nchunks = d->Cin / 16;
-      kt.splitk = 1;
-      rc = p2l_thinout_launch(kt, d->pro, st);
-      if (prof_slot >= 0) {
-        // pointwise product onto 32 columns for the 8x16 pixels + halo (192 rows per 128)
-        g_prof.xflops[prof_slot] = 2.0 * d->B * d->H * d->W * 1.5 * d->Cin * 32.0;
-        g_prof.fam[prof_slot] = P2L_PROF_FAM_THIN;
-        (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-      }
-      return rc;
-    }
-  }
-  // ---- sub-pixel modes (ups 2 = forward, 3 = input-gradient of an upsampled conv) ----
-  if (d->ups >= 2) {
-    // K slices: the input-gradient form of a transposed conv in the fp16 x 2 kernel only (subpix_bwd_split);
-    // the fused modulation / activation backward of a sliced launch runs in the finish kernel, per quad,
-    // so multi-image tiles are no obstacle there
-    // (what this form does not take was refused above, in front of the profiler's slot)
-    {
-      int gH, gW;
-      grid_dims(d, gH, gW);
-      const int e = d->ext ? 1 : 0, e2 = d->ext ? 2 : 0;
-      k.H = gH; k.W = gW;                    // the kernel tiles the low-res grid
-      if (d->ups == 2) {                     // low-res input -> phases of the high-res buffer
-        k.iH = d->H >> 1; k.iW = d->W >> 1; k.ibH = k.iH; k.ibW = k.iW;
-        k.obH = d->H + e2; k.obW = d->W + e2;
-      } else {                               // phase planes of the high-res buffer -> low-res
-        k.iH = (d->H >> 1) + e; k.iW = (d->W >> 1) + e;
-        k.ibH = d->H + e2; k.ibW = d->W + e2;
-        k.obH = gH; k.obW = gW;
-      }
-    }
-    k.sp_mode = d->ups - 1;
-    k.sp_skip = (d->ext && !(d->form & P2L_FORM_NO_SP_SKIP)) ? 1 : 0;
-    k.sp_ncc = d->Cin / 16;
-    k.nchunks = (d->ups == 3) ? 4 * k.sp_ncc : k.sp_ncc;
-    k.chunks_per_split = cdiv(k.nchunks, sk3);
-    k.splitk = sk3;
-    k.ups = 0;
-    const int a_rows_sp = (1 << k.tb_log) * ((1 << k.th_log) + 2) * ((1 << k.tw_log) + 2);
-    const bool small_sp = (a_rows_sp * 4 <= 3 * 256) && k.tb_log == 0;
-    const bool bf3 = bf3_3x3;
-    if (use_h2 && h2_direct) {
-      // fp16 x 2 form (p2l_h2.hip): its image follows the bf16 x 3 one
-      ConvK kh = k;
-      kh.hp = halo_pitch_h2(1 << k.tw_log);
-      kh.w = w + (size_t)16 * d->Cout * d->Cin * 3 / 2;
-      kh.w_tail = reinterpret_cast<const unsigned*>(kh.w + (size_t)16 * d->Cout * d->Cin);
-      if (dry_class) {                      // (the paired forward kernel, taps = 8, keeps the shared item)
-        *dry_class = d->ups == 3 ? p2l_h2_epi_class(kh, d->pro, 4) : EPI_GENERIC;
-        return P2L_OK;
-      }
-      if (kh.amax_in == nullptr) {
-        ConvK ka = kh;                      // the INPUT tensor: low-res (forward) / high-res frame (gradient)
-        ka.H = k.ibH; ka.W = k.ibW;
-        rc = p2l_amax_launch(ka, d->pro, st);
-        if (rc) return rc;
-      }
-      // Forward: two output phases per block on one staged patch -- for the transposed convs with 64-channel
-      // tiles (tools/bench_subpix.py: 1.10 - 1.18 x per launch; BigGAN's nearest-upsample convs, whose 16 taps are
-      // all live and whose launches are 60 - 100 us, lose 5 - 15 % to the halved grid; 32-channel tiles 3 %), or
-      // wherever P2L_FORM_SP_PAIR asks for it (tests); P2L_FORM_NO_SP_PAIR: never.  Shape and form only.
-#ifdef P2L_AB_NO_SP_PAIR
-      const bool pair = d->ups == 2 && !(d->form & P2L_FORM_NO_SP_PAIR) && (d->form & P2L_FORM_SP_PAIR);
-#else
-      const bool pair = d->ups == 2 && !(d->form & P2L_FORM_NO_SP_PAIR) &&
-                        ((d->ext && bn == 64) || (d->form & P2L_FORM_SP_PAIR));
-#endif
-      rc = p2l_h2_launch(kh, d->pro, pair ? 8 : 4, bn, small_sp, st);
-      if (rc == P2L_OK && k.splitk > 1) {
-        // the slices meet in the finish kernel of the direct path, on the low-res grid this launch tiled
-        const bool arb_al = !arb || (k.arb_x_ld % 4 == 0 && (!k.arb_skip || k.arb_skip_ld % 4 == 0));
-        if (finish_v4_ok(d) && arb_al) {
-          const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * (k.n_store >> 2);
-          hipLaunchKernelGGL(conv_splitk_finish_v4, dim3(cdiv(total, 64)), dim3(256), 0, st, k);
-        } else {
-          const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * k.n_store;
-          hipLaunchKernelGGL(conv_splitk_finish, dim3(cdiv(total, 64)), dim3(256), 0, st, k);
-        }
-        rc = p2l_check_launch();
-      }
-      if (prof_slot >= 0) {
-        g_prof.nprod[prof_slot] = 3;
-        g_prof.fam[prof_slot] = P2L_PROF_FAM_SUBPIX_H2;
-        (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-      }
-      return rc;
-    }
-    const int a_lds_sp = (1 << k.tb_log) * ((1 << k.th_log) + 2) * k.hp;
-    size_t lds_sp = (size_t)(a_lds_sp + 4 * bn) * (bf3 ? 24 : 20) * sizeof(float);
-    const size_t lds_epi = (size_t)4 * 32 * (bn + 4) * sizeof(float);
-    if (lds_epi > lds_sp) lds_sp = lds_epi;
-    if (dry_class) return P2L_OK;
-    dim3 grid(k.n_mtiles * k.n_ntiles, d->ups == 2 ? 4 : 1), block(256);
-#define P2L_LAUNCH_SP(BNV, AIT, PROV)                                                     \
-    do {                                                                                  \
-      if (bf3) { P2L_LAUNCH_SP2(BNV, AIT, PROV, true); } else { P2L_LAUNCH_SP2(BNV, AIT, PROV, false); } \
-    } while (0)
-#define P2L_LAUNCH_SP2(BNV, AIT, PROV, BF3V)                                              \
-    do {                                                                                  \
-      auto kfn = pick_kernel<4, BNV, 16, AIT, PROV, false, BF3V>();                       \
-      static std::atomic<bool> attr_set{false};                                                       \
-      if (!attr_set) {                                                                    \
-        (void)hipFuncSetAttribute((const void*)kfn,                                       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        attr_set = true;                                                                  \
-      }                                                                                   \
-      hipLaunchKernelGGL(kfn, grid, block, lds_sp, st, k);                                \
-    } while (0)
-#define P2L_LAUNCH_SP_PRO(BNV, AIT)                                                       \
-    do {                                                                                  \
-      if (d->pro == P2L_PRO_NONE) P2L_LAUNCH_SP(BNV, AIT, P2L_PRO_NONE);                  \
-      else if (d->pro == P2L_PRO_AFFINE_RELU) P2L_LAUNCH_SP(BNV, AIT, P2L_PRO_AFFINE_RELU); \
-      else P2L_LAUNCH_SP(BNV, AIT, P2L_PRO_AFFINE);                                       \
-    } while (0)
-    if (bn == 64) {
-      if (small_sp) P2L_LAUNCH_SP_PRO(64, 3); else P2L_LAUNCH_SP_PRO(64, 5);
-    } else {
-      if (small_sp) P2L_LAUNCH_SP_PRO(32, 3); else P2L_LAUNCH_SP_PRO(32, 5);
-    }
-#undef P2L_LAUNCH_SP_PRO
-#undef P2L_LAUNCH_SP
-#undef P2L_LAUNCH_SP2
-    rc = p2l_check_launch();
-    if (prof_slot >= 0) (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-    return rc;
-  }
-  const int TW = 1 << k.tw_log, TH = 1 << k.th_log, TB = 1 << k.tb_log;
-  const int a_rows = (d->taps == 9) ? TB * (TH + 2) * (TW + 2) : 128;
-  const bool bf3 = bf3_3x3;
-  const int a_rows_lds = (d->taps == 9) ? TB * (TH + 2) * k.hp : 128;
-  size_t lds = (size_t)(a_rows_lds + d->taps * bn) * (bf3 ? 24 : kc + 4) * sizeof(float);
-  {
-    // the vectorised epilogue re-uses the staging LDS for 4 wave tiles of 32 x (bn+4)
-    const size_t lds_epi = (size_t)4 * 32 * (bn + 4) * sizeof(float);
-    if (lds_epi > lds) lds = lds_epi;
-  }
+// ---- part 3: one launch function per family.  Each answers dry_class in front of its first launch. ----
 
-  if (d->taps == 9 && use_h2 && h2_direct) {
+// Winograd F(2x2,3x3) form (p2l_wino.hip): stride-1 3x3 layers whose grid fills the chip with 8x16-pixel x
+// 64-channel blocks; its image follows the bf16 x 3 one, the fp16 x 2 image follows that
+int launch_wino(Launch& L) {
+  const P2LConv* d = L.d;
+  ConvK kw = L.k;                    // (arb_nblk keeps the 128-pixel tiling of the caller's buffer)
+  kw.w = L.w + (L.use_h2 ? L.wi.wino_h2 : L.wi.wino);
+  if (L.use_h2) kw.w_tail = L.tail(L.wi.wino_h2_tail);
+  kw.tiles_x = d->W / 16; kw.tiles_y = d->H / 8;
+  kw.n_mtiles = d->B * kw.tiles_x * kw.tiles_y;
+  kw.n_ntiles = d->Cout / 64;
+  if (L.dry_class) { *L.dry_class = p2l_wino_epi_class(kw, d->pro); return P2L_OK; }
+  int rc = p2l_wino_launch(kw, d->pro, L.st);
+  if (rc == P2L_OK && L.r.wino_sliced) rc = launch_finish(L.k, FIN_WINO4, L.st);
+  L.prof->took(L.use_h2 ? P2L_PROF_FAM_WINO_H2 : P2L_PROF_FAM_OTHER, L.use_h2 ? 3 : 0,
+               2.0 * d->B * d->H * d->W * (double)d->Cin * d->Cout * 4);   // 16 per quad
+  return rc;
+}
+
+// 1x1 conv on whole tiles in the bf16x3 arithmetic (p2l_pw.hip), or fp16 x 2 with handed-over maxima
+int launch_pw(Launch& L) {
+  const P2LConv* d = L.d;
+  const bool h2 = L.k.amax_in != nullptr;
+  ConvK kp = L.k;
+  kp.w = L.w + (h2 ? L.wi.pw_h2 : L.wi.pw);
+  if (h2) kp.w_tail = L.tail(L.wi.pw_h2_tail);
+  kp.n_ntiles = d->Cout / 64;
+  kp.nchunks = d->Cin / 64;
+  if (L.dry_class) { *L.dry_class = p2l_pw_epi_class(kp, d->pro); return P2L_OK; }
+  const int rc = p2l_pw_launch(kp, d->pro, L.st);
+  L.prof->took(P2L_PROF_FAM_PW, h2 ? 3 : 0);
+  return rc;
+}
+
+// 3-channel image convs (p2l_thin.hip).  thin_takes: the launch-side conditions of a thin shape; what fails
+// them runs on the generic 3x3 kernel.
+bool thin_takes(const Launch& L, float* y) {
+  const ConvK& k = L.k;
+  if (!(k.tw_log == 4 && k.th_log == 3 && k.tb_log == 0 && !k.partial) || (L.ex && (L.ex->oscale || L.ex->noise)))
+    return false;
+  return L.r.thin == 1 || (!L.arb && !L.res && !L.mask && L.d->pool == P2L_POOL_NONE && y);
+}
+int launch_thin(Launch& L) {
+  const P2LConv* d = L.d;
+  if (L.dry_class) return P2L_OK;
+  ConvK kt = L.k;
+  kt.w = L.w + L.wi.thin;
+  const int rc = L.r.thin == 1 ? p2l_thinin_launch(kt, d->pro, L.st) : p2l_thinout_launch(kt, d->pro, L.st);
+  // thin input: K = 27 -> 32; thin output: pointwise product onto 32 columns for the 8x16 pixels + halo (192 rows per 128)
+  L.prof->took(P2L_PROF_FAM_THIN, 0, L.r.thin == 1 ? 2.0 * d->B * d->H * d->W * 32.0 * d->Cout
+                                                   : 2.0 * d->B * d->H * d->W * 1.5 * d->Cin * 32.0);
+  return rc;
+}
+
+// sub-pixel modes (ups 2 = forward, 3 = input-gradient of an upsampled conv).  The fused modulation / activation
+// backward of a sliced launch runs in the finish kernel, per quad, so multi-image tiles are no obstacle there.
+int launch_subpix(Launch& L) {
+  const P2LConv* d = L.d;
+  ConvK& k = L.k;
+  {
+    int gH, gW;
+    grid_dims(d, gH, gW);
+    const int e = d->ext ? 1 : 0, e2 = d->ext ? 2 : 0;
+    k.H = gH; k.W = gW;                    // the kernel tiles the low-res grid
+    if (d->ups == 2) {                     // low-res input -> phases of the high-res buffer
+      k.iH = d->H >> 1; k.iW = d->W >> 1; k.ibH = k.iH; k.ibW = k.iW;
+      k.obH = d->H + e2; k.obW = d->W + e2;
+    } else {                               // phase planes of the high-res buffer -> low-res
+      k.iH = (d->H >> 1) + e; k.iW = (d->W >> 1) + e;
+      k.ibH = d->H + e2; k.ibW = d->W + e2;
+      k.obH = gH; k.obW = gW;
+    }
+  }
+  k.sp_mode = d->ups - 1;
+  k.sp_skip = (d->ext && !(d->form & P2L_FORM_NO_SP_SKIP)) ? 1 : 0;
+  k.sp_ncc = d->Cin / 16;
+  k.ups = 0;
+  const int bn = L.r.bn;
+  const bool small_sp = (patch_rows(k) * 4 <= 3 * 256) && k.tb_log == 0;
+  if (L.use_h2) {
+    // fp16 x 2 form (p2l_h2.hip): its image follows the bf16 x 3 one
     ConvK kh = k;
-    kh.hp = halo_pitch_h2(TW);
-    kh.w = w + (size_t)9 * d->Cout * d->Cin * 3 / 2;
-    if (p2l_wino_weight_ok(d->Cout, d->Cin))
-      kh.w += p2l_wino_weight_floats(d->Cout, d->Cin) + p2l_wino_h2_weight_floats(d->Cout, d->Cin);
-    kh.w_tail = reinterpret_cast<const unsigned*>(kh.w + (size_t)9 * d->Cout * d->Cin);
-    const bool small = (a_rows * 4 <= 3 * 256) && TB == 1;
-    const bool h2r = direct_h2r(d) && k.splitk == 1 && !k.partial && TB == 1 && p2l_h2r_takes(kh);
-    if (dry_class) {                        // (the register-resident kernel has epilogues of its own)
-      *dry_class = h2r ? EPI_GENERIC : p2l_h2_epi_class(kh, d->pro, 9);
+    kh.hp = halo_pitch_h2(1 << k.tw_log);
+    kh.w = L.w + L.wi.h2;
+    kh.w_tail = L.tail(L.wi.h2_tail);
+    if (L.dry_class) {                      // (the paired forward kernel, taps = 8, keeps the shared item)
+      *L.dry_class = d->ups == 3 ? p2l_h2_epi_class(kh, d->pro, 4) : EPI_GENERIC;
       return P2L_OK;
     }
+    L.prof->took(P2L_PROF_FAM_SUBPIX_H2, 3);
     if (kh.amax_in == nullptr) {
-      rc = p2l_amax_launch(kh, d->pro, st);
-      if (rc) return rc;
+      ConvK ka = kh;                      // the INPUT tensor: low-res (forward) / high-res frame (gradient)
+      ka.H = k.ibH; ka.W = k.ibW;
+      if (int rc = p2l_amax_launch(ka, d->pro, L.st)) return rc;
     }
-    rc = h2r ? p2l_h2r_launch(kh, d->pro, st) : p2l_h2_launch(kh, d->pro, 9, bn, small, st);
-    if (prof_slot >= 0) { g_prof.nprod[prof_slot] = 3; g_prof.fam[prof_slot] = h2r ? P2L_PROF_FAM_DIRECT_H2R : P2L_PROF_FAM_DIRECT_H2; }
-  } else if (dry_class) {
-    return P2L_OK;
-  } else
-  if (d->taps == 9) {
-    const bool small = (a_rows * 4 <= 3 * 256) && TB == 1;
-    if (bf3) {
-      if (bn == 64) rc = small ? launch_conv<9, 64, 16, 3, true>(k, d->pro, d->ups, lds, st)
-                               : launch_conv<9, 64, 16, 5, true>(k, d->pro, d->ups, lds, st);
-      else          rc = small ? launch_conv<9, 32, 16, 3, true>(k, d->pro, d->ups, lds, st)
-                               : launch_conv<9, 32, 16, 5, true>(k, d->pro, d->ups, lds, st);
-    } else
-    if (bn == 64) rc = small ? launch_conv<9, 64, 16, 3>(k, d->pro, d->ups, lds, st)
-                             : launch_conv<9, 64, 16, 5>(k, d->pro, d->ups, lds, st);
-    else          rc = small ? launch_conv<9, 32, 16, 3>(k, d->pro, d->ups, lds, st)
-                             : launch_conv<9, 32, 16, 5>(k, d->pro, d->ups, lds, st);
-  } else if (d->taps == 1 && use_h2 && h2_pw_small) {
-    // 1x1 layers of 4^2 ... 16^2 in the fp16 x 2 arithmetic (multi-image tiles, split-K in
-    // blockIdx.y; the slices meet in conv_splitk_finish below)
-    ConvK kp = k;
-    kp.w = w + (size_t)d->Cout * d->Cin + (size_t)d->Cout * d->Cin * 3 / 2;
-    kp.w_tail = reinterpret_cast<const unsigned*>(kp.w + (size_t)d->Cout * d->Cin);
-    kp.n_ntiles = d->Cout / 64;
-    if (kp.amax_in == nullptr) {
-      rc = p2l_amax_launch(kp, d->pro, st);
-      if (rc) return rc;
+    // Forward: two output phases per block on one staged patch -- for the transposed convs with 64-channel
+    // tiles (tools/bench_subpix.py: 1.10 - 1.18 x per launch; BigGAN's nearest-upsample convs, whose 16 taps are
+    // all live and whose launches are 60 - 100 us, lose 5 - 15 % to the halved grid; 32-channel tiles 3 %), or
+    // wherever P2L_FORM_SP_PAIR asks for it (tests); P2L_FORM_NO_SP_PAIR: never.  Shape and form only.
+#ifdef P2L_AB_NO_SP_PAIR
+    const bool pair = d->ups == 2 && !(d->form & P2L_FORM_NO_SP_PAIR) && (d->form & P2L_FORM_SP_PAIR);
+#else
+    const bool pair = d->ups == 2 && !(d->form & P2L_FORM_NO_SP_PAIR) &&
+                      ((d->ext && bn == 64) || (d->form & P2L_FORM_SP_PAIR));
+#endif
+    int rc = p2l_h2_launch(kh, d->pro, pair ? 8 : 4, bn, small_sp, L.st);
+    if (rc == P2L_OK && k.splitk > 1) {
+      // (the 16-byte finish kernel reads the fused backward's operands in 16-byte pieces)
+      const bool arb_al = !L.arb || (k.arb_x_ld % 4 == 0 && (!k.arb_skip || k.arb_skip_ld % 4 == 0));
+      rc = launch_finish(k, (L.r.finish == FIN_V4 && arb_al) ? FIN_V4 : FIN_SCALAR, L.st);
     }
-    rc = p2l_pw_launch(kp, d->pro, st);
-    if (prof_slot >= 0) { g_prof.nprod[prof_slot] = 3; g_prof.fam[prof_slot] = P2L_PROF_FAM_PW; }
-  } else if (kc == 32) {
-    if (bn == 64) rc = launch_conv<1, 64, 32, 4>(k, d->pro, 0, lds, st);
-    else          rc = launch_conv<1, 32, 32, 4>(k, d->pro, 0, lds, st);
-  } else {          // 1x1 with Cin a multiple of 16 only (RGB image gradients)
-    if (bn == 64) rc = launch_conv<1, 64, 16, 2>(k, d->pro, 0, lds, st);
-    else          rc = launch_conv<1, 32, 16, 2>(k, d->pro, 0, lds, st);
+    return rc;
   }
-  if (rc) return rc;
-  if (k.splitk > 1) {
-    if (finish_v4_ok(d)) {                               // (its arb pitches were checked in front of the launch)
-      const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * (k.n_store >> 2);
-      hipLaunchKernelGGL(conv_splitk_finish_v4, dim3(cdiv(total, 64)), dim3(256), 0, st, k);
-    } else {
-      const size_t total = (size_t)k.B * (k.H >> 1) * (k.W >> 1) * k.n_store;
-      hipLaunchKernelGGL(conv_splitk_finish, dim3(cdiv(total, 64)), dim3(256), 0, st, k);
+  if (L.dry_class) return P2L_OK;
+  const bool bf3 = d->wfmt != P2L_WFMT_F32;
+  const size_t lds = conv_lds((1 << k.tb_log) * ((1 << k.th_log) + 2) * k.hp, 4, bn, bf3 ? 24 : 20);
+  return launch_tiled<4>(k, bn, small_sp, bf3, d->pro, 0, dim3(k.n_mtiles * k.n_ntiles, d->ups == 2 ? 4 : 1), lds, L.st);
+}
+
+// the split-K slices of the stride-1 kernels below meet in the finish kernel (its arb pitches were checked in
+// front of the launch)
+int finish_sliced(Launch& L, int rc) {
+  return (rc == P2L_OK && L.k.splitk > 1) ? launch_finish(L.k, L.r.finish, L.st) : rc;
+}
+
+// stride-1 3x3 (and the fused nearest upsample, ups 1): the fp16 x 2 kernel, chunked or with the weights resident
+// in registers, where the workspace holds its maxima; the bf16 x 3 or the exact-fp32 kernel otherwise
+int launch_direct(Launch& L) {
+  const P2LConv* d = L.d;
+  const ConvK& k = L.k;
+  const int TW = 1 << k.tw_log, TH = 1 << k.th_log, TB = 1 << k.tb_log, bn = L.r.bn;
+  const bool small = (patch_rows(k) * 4 <= 3 * 256) && TB == 1;
+  if (L.use_h2) {
+    ConvK kh = k;
+    kh.hp = halo_pitch_h2(TW);
+    kh.w = L.w + L.wi.h2;
+    kh.w_tail = L.tail(L.wi.h2_tail);
+    const bool h2r = L.r.h2r && k.splitk == 1 && !k.partial && TB == 1 && p2l_h2r_takes(kh);
+    if (L.dry_class) {                        // (the register-resident kernel has epilogues of its own)
+      *L.dry_class = h2r ? EPI_GENERIC : p2l_h2_epi_class(kh, d->pro, 9);
+      return P2L_OK;
     }
-    rc = p2l_check_launch();
+    L.prof->took(h2r ? P2L_PROF_FAM_DIRECT_H2R : P2L_PROF_FAM_DIRECT_H2, 3);
+    if (kh.amax_in == nullptr)
+      if (int rc = p2l_amax_launch(kh, d->pro, L.st)) return rc;
+    return finish_sliced(L, h2r ? p2l_h2r_launch(kh, d->pro, L.st) : p2l_h2_launch(kh, d->pro, 9, bn, small, L.st));
   }
-  if (prof_slot >= 0) (void)hipEventRecord(g_prof.ev[2 * prof_slot + 1], st);
-  return rc;
+  if (L.dry_class) return P2L_OK;
+  const bool bf3 = d->wfmt != P2L_WFMT_F32;
+  const size_t lds = conv_lds(TB * (TH + 2) * k.hp, 9, bn, bf3 ? 24 : 20);
+  return finish_sliced(L, launch_tiled<9>(k, bn, small, bf3, d->pro, d->ups, dim3(k.n_mtiles * k.n_ntiles, k.splitk), lds, L.st));
+}
+
+// 1x1 layers of 4^2 ... 16^2 in the fp16 x 2 arithmetic (multi-image tiles, split-K in blockIdx.y); without the
+// workspace for its maxima the launch runs on the exact-fp32 kernel
+int launch_1x1(Launch& L);
+int launch_pw_small(Launch& L) {
+  const P2LConv* d = L.d;
+  if (!L.use_h2) return launch_1x1(L);
+  if (L.dry_class) return P2L_OK;
+  ConvK kp = L.k;
+  kp.w = L.w + L.wi.pw_h2;
+  kp.w_tail = L.tail(L.wi.pw_h2_tail);
+  kp.n_ntiles = d->Cout / 64;
+  L.prof->took(P2L_PROF_FAM_PW, 3);
+  if (kp.amax_in == nullptr)
+    if (int rc = p2l_amax_launch(kp, d->pro, L.st)) return rc;
+  return finish_sliced(L, p2l_pw_launch(kp, d->pro, L.st));
+}
+
+// the exact-fp32 1x1 kernel: 32-channel chunks, or 16 where Cin is a multiple of 16 only (RGB image gradients)
+int launch_1x1(Launch& L) {
+  const ConvK& k = L.k;
+  if (L.dry_class) return P2L_OK;
+  const int bn = L.r.bn, pro = L.d->pro;
+  const dim3 grid(k.n_mtiles * k.n_ntiles, k.splitk);
+  const size_t lds = conv_lds(128, 1, bn, L.r.kc + 4);
+  int rc;
+  if (L.r.kc == 32) rc = bn == 64 ? launch_conv<1, 64, 32, 4>(k, pro, 0, grid, lds, L.st) : launch_conv<1, 32, 32, 4>(k, pro, 0, grid, lds, L.st);
+  else rc = bn == 64 ? launch_conv<1, 64, 16, 2>(k, pro, 0, grid, lds, L.st) : launch_conv<1, 32, 16, 2>(k, pro, 0, grid, lds, L.st);
+  return finish_sliced(L, rc);
+}
+
+// The one launcher: checks, then the profiler's slot, then the family's launch function -- in that order by
+// construction.  dry_class: nothing is launched; *dry_class = the epilogue class the launch would run
+// (p2l_conv_epilogue_class).
+int conv_launch_impl(const P2LConv* d, const P2LArb* arb, const P2LConvExtra* ex,
+                     const float* x, const float* w,
+                     const float* bias, const float* pro_s,
+                     const float* pro_t, const float* res,
+                     const float* mask, float* y, float* yp,
+                     void* workspace, size_t ws_bytes, void* stream, int* dry_class = nullptr) {
+  Launch L{d, arb, ex, w, res, mask};
+  L.st = (hipStream_t)stream;
+  L.dry_class = dry_class;
+  if (int rc = conv_prepare(L, x, bias, pro_s, pro_t, y, yp, workspace, ws_bytes)) return rc;
+  if (dry_class) *dry_class = EPI_GENERIC;   // (every family answers in front of its first launch)
+  ProfSlot prof(d, L.r, arb, y, yp, res, mask, L.st, dry_class != nullptr);
+  L.prof = &prof;
+  switch (L.r.family) {
+    case FAM_WINO: return launch_wino(L);
+    case FAM_PW: return launch_pw(L);
+    case FAM_SUBPIX: return launch_subpix(L);
+    case FAM_PW_SMALL: return launch_pw_small(L);
+    case FAM_1X1: return launch_1x1(L);
+    case FAM_THIN: if (thin_takes(L, y)) return launch_thin(L);   // (else the generic 3x3 kernel)
+  }
+  return launch_direct(L);
+}
+
+// the route of a descriptor for the queries below (NULL: no route, the query's own answer)
+struct Routed {
+  ConvRoute r;
+  bool ok;       // the grid can be tiled
+  explicit Routed(const P2LConv* d) : r{}, ok(d && conv_route(d, r) == P2L_OK) {}
+};
+
+}  // namespace
+
+extern "C" int p2l_conv_suggest_splitk(const P2LConv* d) {
+  if (!d) return 1;
+  const Routed q(d);
+  if (d->ups >= 2) return (d->ups == 3 && d->ext) ? q.r.subpix_slices : 1;   // the other sub-pixel modes never split K
+  // small-grid Winograd layer: a function of the shape only (p2l_wino_split_factor gives 1 from 64 blocks per image up)
+  if (q.ok && q.r.wino_slices > 1 && !(d->form & P2L_FORM_WINO_ANY)) return q.r.wino_slices;
+  if (!q.ok || q.r.tile.partial || q.r.wino || q.r.pw || q.r.thin >= 0) return 1;
+  return q.r.direct_slices;
+}
+extern "C" int p2l_conv_amax_slots(const P2LConv* d) {
+  if (!d) return 0;
+  const Routed q(d);
+  return amax_slots(d, q.r);
+}
+// (the slices are sized for d->splitk as it stands, never fewer than the launch takes: DESIGN.md 4, the route of a launch)
+extern "C" size_t p2l_conv_workspace_bytes(const P2LConv* d) {
+  const Routed q(d);
+  return q.r.amax_bytes + slice_bytes(d, d->splitk);
+}
+extern "C" int p2l_conv_arb_fusable(const P2LConv* d) {
+  const Routed q(d);
+  return q.ok && q.r.tile.tb_log == 0;     // one image per tile; the caller decides about split-K
+}
+extern "C" int p2l_conv_arb_nblk(const P2LConv* d) {
+  const Routed q(d);
+  return q.ok ? arb_nblk(d, q.r, false) : 0;
+}
+extern "C" int p2l_conv_arb_split_fusable(const P2LConv* d) {
+  const Routed q(d);
+  return q.ok && !q.r.tile.partial && q.r.splitk > 1 && d->pool != P2L_POOL_MAX;
+}
+extern "C" int p2l_conv_arb_nblk_ws(const P2LConv* d) {
+  if (!d) return 0;
+  const Routed q(d);
+  return arb_nblk(d, q.r, q.r.splitk > 1);
 }
 
 extern "C" int p2l_conv_fwd(const P2LConv* d, const float* x, const float* w,
@@ -1844,6 +1942,16 @@ extern "C" int p2l_conv_fwd_ex(const P2LConv* d, const P2LConvExtra* ex, const f
                           ws_bytes, stream);
 }
 
+// a fused activation backward as p2l_conv_dgrad_arb_ws hands it to the launcher: no pooling for the sub-pixel
+// gradient, unsliced where d->splitk resolves to one slice
+static P2LConv arb_descriptor(const P2LConv* d, bool& sliced) {
+  P2LConv dd = *d;
+  if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
+  sliced = Routed(&dd).r.splitk > 1;
+  if (!sliced) dd.splitk = 1;
+  return dd;
+}
+
 extern "C" int p2l_conv_epilogue_class(const P2LConv* d, const P2LConvExtra* ex, const P2LArb* arb,
                                        const float* bias, const float* res, const float* mask, const float* y,
                                        const float* yp, const void* workspace, size_t ws_bytes) {
@@ -1851,9 +1959,9 @@ extern "C" int p2l_conv_epilogue_class(const P2LConv* d, const P2LConvExtra* ex,
   // x, w and the prologue vectors only have to be there: nothing is read through any pointer
   const float* some = reinterpret_cast<const float*>(d);
   P2LConv dd = *d;
-  if (arb) {                                             // (as p2l_conv_dgrad_arb_ws hands the launch on)
-    if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
-    if (effective_splitk(&dd) <= 1) dd.splitk = 1;
+  if (arb) {
+    bool sliced;
+    dd = arb_descriptor(d, sliced);
     if (dd.pool == P2L_POOL_SUM) { yp = y; y = nullptr; }
   }
   int ec = 0;
@@ -1863,100 +1971,59 @@ extern "C" int p2l_conv_epilogue_class(const P2LConv* d, const P2LConvExtra* ex,
   return rc == P2L_OK ? ec : 0;
 }
 
-extern "C" int p2l_conv_arb_fusable(const P2LConv* d) {
-  ConvK k{};
-  if (!d || choose_tile(d, k) != P2L_OK) return 0;
-  return k.tb_log == 0;     // one image per tile; the caller decides about split-K
-}
-
-extern "C" int p2l_conv_arb_nblk(const P2LConv* d) {
-  ConvK k{};
-  if (!d || choose_tile(d, k) != P2L_OK) return 0;
-  return k.n_mtiles / d->B;
-}
-
-extern "C" int p2l_conv_arb_split_fusable(const P2LConv* d) {
-  ConvK k{};
-  if (!d || choose_tile(d, k) != P2L_OK || k.partial) return 0;
-  return effective_splitk(d) > 1 && d->pool != P2L_POOL_MAX;
-}
-
-extern "C" int p2l_conv_arb_nblk_ws(const P2LConv* d) {
-  if (!d) return 0;
-  const int sh = d->ups == 3 ? 2 : 1;       // (quads of the grid the finish kernel walks: low-res for ups 3)
-  return effective_splitk(d) > 1 ? (d->H >> sh) * (d->W >> sh) : p2l_conv_arb_nblk(d);
-}
-
-static int dgrad_arb_unsplit(const P2LConv* d, const P2LArb* arb, const float* dy, const float* w,
-                             float* dx, void* workspace, size_t ws_bytes, void* stream);
-// what p2l_arb_finish will check of ds / dt, in front of the conv launch that writes dx
-static int arb_outputs_ok(const P2LConv* d, const P2LArb* arb) {
-  if (!arb->ds || !arb->dt) return P2L_EINVAL;
-  if (arb->dsdt_bstride % 4 || arb->dsdt_bstride < d->Cout) return P2L_EINVAL;
-  return P2L_OK;
-}
+// (the workspace of an unsplit launch only serves the fp16 x 2 forms)
 extern "C" int p2l_conv_dgrad_arb_ws(const P2LConv* d, const P2LArb* arb, const float* dy,
                                      const float* w, float* dx, void* workspace, size_t ws_bytes,
                                      void* stream) {
   if (!d || !arb || !dx) return P2L_EINVAL;
-  if (int rc0 = arb_outputs_ok(d, arb)) return rc0;
-  P2LConv dd = *d;
-  if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
-  if (effective_splitk(&dd) <= 1) return dgrad_arb_unsplit(d, arb, dy, w, dx, workspace, ws_bytes, stream);
+  // what p2l_arb_finish will check of ds / dt, in front of the conv launch that writes dx
+  if (!arb->ds || !arb->dt) return P2L_EINVAL;
+  if (arb->dsdt_bstride % 4 || arb->dsdt_bstride < d->Cout) return P2L_EINVAL;
+  bool sliced;
+  const P2LConv dd = arb_descriptor(d, sliced);
   const bool pooled = dd.pool == P2L_POOL_SUM;
   int rc = conv_launch_impl(&dd, arb, nullptr, dy, w, nullptr, nullptr, nullptr, nullptr, nullptr,
                             pooled ? nullptr : dx, pooled ? dx : nullptr, workspace, ws_bytes,
                             stream);
   if (rc) return rc;
-  return p2l_arb_finish(arb->partial, arb->ds, arb->dt, dd.B, p2l_conv_arb_nblk_ws(&dd), dd.Cout,
-                        arb->dsdt_bstride, stream);
-}
-
-// (the workspace of an unsplit launch only serves the fp16 x 2 Winograd form: wino_h2)
-static int dgrad_arb_unsplit(const P2LConv* d, const P2LArb* arb, const float* dy, const float* w,
-                             float* dx, void* workspace, size_t ws_bytes, void* stream) {
-  if (!d || !arb || !dx) return P2L_EINVAL;
-  if (int rc0 = arb_outputs_ok(d, arb)) return rc0;
-  P2LConv dd = *d;
-  dd.splitk = 1;
-  if (dd.ups == 3) dd.pool = P2L_POOL_NONE;
-  const bool pooled = dd.pool == P2L_POOL_SUM;
-  int rc = conv_launch_impl(&dd, arb, nullptr, dy, w, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            pooled ? nullptr : dx, pooled ? dx : nullptr, workspace, ws_bytes, stream);
-  if (rc) return rc;
-  const int nblk = p2l_conv_arb_nblk(&dd);
-  return p2l_arb_finish(arb->partial, arb->ds, arb->dt, dd.B, nblk, dd.Cout,
+  return p2l_arb_finish(arb->partial, arb->ds, arb->dt, dd.B, arb_nblk(&dd, Routed(&dd).r, sliced), dd.Cout,
                         arb->dsdt_bstride, stream);
 }
 extern "C" int p2l_conv_dgrad_arb(const P2LConv* d, const P2LArb* arb, const float* dy,
                                   const float* w, float* dx, void* stream) {
-  return dgrad_arb_unsplit(d, arb, dy, w, dx, nullptr, 0, stream);
+  if (!d) return P2L_EINVAL;
+  P2LConv dd = *d;
+  dd.splitk = 1;
+  return p2l_conv_dgrad_arb_ws(&dd, arb, dy, w, dx, nullptr, 0, stream);
+}
+
+// One image of a packed buffer from OIHW weights: the [tap][K / kc][N][kc] fp32 layout or the bf16 x 3 tile image
+// of a conv of `taps` taps (mode < 0), or of the 16 phase-tap slabs of a 3x3 conv's sub-pixel form (mode 0 / 1)
+static int pack_image(const float* w_oihw, int O, int I, int taps, int N_pad, int K_pad, int kc, int flip,
+                      int bf3, int mode, float* dst, void* stream) {
+  if (!w_oihw || !dst || taps < 1 || mode > 1) return P2L_EINVAL;
+  const int N = flip ? I : O, K = flip ? O : I;
+  if (K_pad % kc || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
+  const size_t total = (size_t)(mode < 0 ? taps : 16) * K_pad * N_pad;
+  if (mode < 0)
+    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw,
+                       dst, O, I, taps, N_pad, K_pad, kc, flip, bf3);
+  else
+    hipLaunchKernelGGL(pack_subpix_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw, dst,
+                       O, I, N_pad, K_pad, flip, mode, bf3);
+  return p2l_check_launch();
 }
 
 extern "C" int p2l_pack_conv_weight_subpix(const float* w_oihw, int O, int I, int N_pad,
                                            int K_pad, int transpose_flip, int mode,
                                            float* w_packed, void* stream) {
-  if (!w_oihw || !w_packed || mode < 0 || mode > 1) return P2L_EINVAL;
-  const int N = transpose_flip ? I : O, K = transpose_flip ? O : I;
-  if (K_pad % 16 || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
-  const size_t total = (size_t)16 * K_pad * N_pad;
-  hipLaunchKernelGGL(pack_subpix_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, w_packed, O, I, N_pad, K_pad, transpose_flip,
-                     mode, 0);
-  return p2l_check_launch();
+  return mode < 0 ? P2L_EINVAL : pack_image(w_oihw, O, I, 9, N_pad, K_pad, 16, transpose_flip, 0, mode, w_packed, stream);
 }
 
 extern "C" int p2l_pack_conv_weight_subpix_bf3(const float* w_oihw, int O, int I, int N_pad,
                                                int K_pad, int transpose_flip, int mode,
                                                float* w_packed, void* stream) {
-  if (!w_oihw || !w_packed || mode < 0 || mode > 1) return P2L_EINVAL;
-  const int N = transpose_flip ? I : O, K = transpose_flip ? O : I;
-  if (K_pad % 16 || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
-  const size_t total = (size_t)16 * K_pad * N_pad;
-  hipLaunchKernelGGL(pack_subpix_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, w_packed, O, I, N_pad, K_pad, transpose_flip,
-                     mode, 1);
-  return p2l_check_launch();
+  return mode < 0 ? P2L_EINVAL : pack_image(w_oihw, O, I, 9, N_pad, K_pad, 16, transpose_flip, 1, mode, w_packed, stream);
 }
 
 
@@ -2051,60 +2118,42 @@ extern "C" int p2l_pack_conv_weight(const float* w_oihw, int O, int I, int taps,
                                     int N_pad, int K_pad, int transpose_flip,
                                     float* w_packed, void* stream) {
   // taps = KH*KW: 1 and 9 feed conv_mfma_kernel, anything else (25, 121) p2l_gconv_fwd
-  if (!w_oihw || !w_packed || taps < 1) return P2L_EINVAL;
-  const int kc = (taps != 1) ? 16 : (K_pad % 32 == 0 ? 32 : 16);
-  const int N = transpose_flip ? I : O, K = transpose_flip ? O : I;
-  if (K_pad % kc || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
-  const size_t total = (size_t)taps * K_pad * N_pad;
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(cdiv(total, 256)), dim3(256),
-                     0, (hipStream_t)stream, w_oihw, w_packed, O, I, taps, N_pad,
-                     K_pad, kc, transpose_flip, 0);
-  return p2l_check_launch();
+  return pack_image(w_oihw, O, I, taps, N_pad, K_pad, conv_kc(taps, K_pad), transpose_flip, 0, -1, w_packed, stream);
 }
 
 // weights of the generic gather conv (p2l_gconv_fwd, p2l_alex.hip): [tap][K_pad/16][N_pad][16] for EVERY kernel
 // size -- p2l_pack_conv_weight gives 1x1 convs 32-channel chunks where K_pad allows it (conv_mfma_kernel<1, ..>)
 extern "C" int p2l_pack_gconv_weight(const float* w_oihw, int O, int I, int taps, int N_pad, int K_pad,
                                      int transpose_flip, float* w_packed, void* stream) {
-  if (!w_oihw || !w_packed || taps < 1) return P2L_EINVAL;
-  const int N = transpose_flip ? I : O, K = transpose_flip ? O : I;
-  if (K_pad % 16 || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
-  const size_t total = (size_t)taps * K_pad * N_pad;
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w_oihw,
-                     w_packed, O, I, taps, N_pad, K_pad, 16, transpose_flip, 0);
-  return p2l_check_launch();
+  return pack_image(w_oihw, O, I, taps, N_pad, K_pad, 16, transpose_flip, 0, -1, w_packed, stream);
+}
+
+// Sizes of the packed buffers and the pack functions of the formats with several images: every offset is
+// weight_images' (above), which the launcher reads too.
+extern "C" size_t p2l_packed_weight_floats(int taps, int N_pad, int K_pad, int wfmt) {
+  return weight_images(taps, false, N_pad, K_pad, wfmt).total;
+}
+extern "C" size_t p2l_packed_subpix_weight_floats(int N_pad, int K_pad, int wfmt) {
+  return weight_images(9, true, N_pad, K_pad, wfmt).total;
 }
 
 // bf16x3 pre-split weights for the BF3 conv kernels: 1.5 x taps*K_pad*N_pad floats
-// P2L_WFMT_BF16X3W: the direct bf16x3 tile image followed -- for shapes the Winograd kernel
-// takes (p2l_wino_weight_ok) -- by the transform-domain image of the same weights
-extern "C" size_t p2l_packed_weight_floats(int taps, int N_pad, int K_pad, int wfmt) {
-  const size_t direct = (size_t)taps * N_pad * K_pad;
-  if (wfmt == P2L_WFMT_F32) return direct;
-  if (wfmt == P2L_WFMT_PW)                                      // fp32 layout + bf16x3 image + fp16x2 image
-    return direct + direct * 3 / 2 + p2l_pw_h2_weight_floats(N_pad, K_pad);
-  size_t n = direct * 3 / 2;
-  if (wfmt == P2L_WFMT_BF16X3W && taps == 9 && p2l_wino_weight_ok(N_pad, K_pad))
-    n += p2l_wino_weight_floats(N_pad, K_pad) + p2l_wino_h2_weight_floats(N_pad, K_pad);
-  if (wfmt == P2L_WFMT_BF16X3W && taps == 9) n += p2l_h2_weight_floats(N_pad, K_pad, 0);   // fp16 x 2 direct image
-  if (wfmt == P2L_WFMT_BF16X3T && taps == 9) n += p2l_thin_weight_floats(N_pad, K_pad);
-  return n;
+extern "C" int p2l_pack_conv_weight_bf3(const float* w_oihw, int O, int I, int taps, int N_pad,
+                                        int K_pad, int transpose_flip, float* w_packed,
+                                        void* stream) {
+  return taps != 9 ? P2L_EINVAL : pack_image(w_oihw, O, I, 9, N_pad, K_pad, 16, transpose_flip, 1, -1, w_packed, stream);
 }
 
 // P2L_WFMT_PW (1x1 convs): the fp32 layout of p2l_pack_conv_weight followed by the bf16x3 image
-// [K_pad/16][N_pad/32][32 rows][96 B]; the launcher picks per layer shape
+// [K_pad/16][N_pad/32][32 rows][96 B] and the fp16 x 2 image; the launcher picks per layer shape
 extern "C" int p2l_pack_conv_weight_pw(const float* w_oihw, int O, int I, int N_pad, int K_pad,
                                        int transpose_flip, float* w_packed, void* stream) {
   int rc = p2l_pack_conv_weight(w_oihw, O, I, 1, N_pad, K_pad, transpose_flip, w_packed, stream);
   if (rc) return rc;
-  const size_t total = (size_t)K_pad * N_pad;
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                     (hipStream_t)stream, w_oihw, w_packed + total, O, I, 1, N_pad, K_pad, 16,
-                     transpose_flip, 1);
-  rc = p2l_check_launch();
+  const WeightImages wi = weight_images(1, false, N_pad, K_pad, P2L_WFMT_PW);
+  rc = pack_image(w_oihw, O, I, 1, N_pad, K_pad, 16, transpose_flip, 1, -1, w_packed + wi.pw, stream);
   if (rc) return rc;
-  return p2l_pw_pack_h2(w_oihw, O, I, N_pad, K_pad, transpose_flip, w_packed + total + total * 3 / 2,
-                        (hipStream_t)stream);
+  return p2l_pw_pack_h2(w_oihw, O, I, N_pad, K_pad, transpose_flip, w_packed + wi.pw_h2, (hipStream_t)stream);
 }
 
 // P2L_WFMT_BF16X3T: the direct bf16x3 image followed by the thin image of a conv with three real
@@ -2114,50 +2163,33 @@ extern "C" int p2l_pack_conv_weight_bf3t(const float* w_oihw, int O, int I, int 
   int rc = p2l_pack_conv_weight_bf3(w_oihw, O, I, 9, N_pad, K_pad, transpose_flip, w_packed, stream);
   if (rc) return rc;
   return p2l_thin_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip,
-                       w_packed + (size_t)9 * N_pad * K_pad * 3 / 2, (hipStream_t)stream);
+                       w_packed + weight_images(9, false, N_pad, K_pad, P2L_WFMT_BF16X3T).thin, (hipStream_t)stream);
 }
 
+// P2L_WFMT_BF16X3W: the direct bf16x3 tile image followed -- for shapes the Winograd kernel takes
+// (p2l_wino_weight_ok) -- by the transform-domain images of the same weights (p2l_wino_pack writes both), and the
+// fp16 x 2 image of the direct kernel's weight tile (p2l_h2.hip) behind everything else
 extern "C" int p2l_pack_conv_weight_bf3w(const float* w_oihw, int O, int I, int taps, int N_pad,
                                          int K_pad, int transpose_flip, float* w_packed,
                                          void* stream) {
   int rc = p2l_pack_conv_weight_bf3(w_oihw, O, I, taps, N_pad, K_pad, transpose_flip, w_packed,
                                     stream);
   if (rc) return rc;
-  float* next = w_packed + (size_t)taps * N_pad * K_pad * 3 / 2;
+  const WeightImages wi = weight_images(taps, false, N_pad, K_pad, P2L_WFMT_BF16X3W);
   if (p2l_wino_weight_ok(N_pad, K_pad)) {
-    rc = p2l_wino_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip, next, (hipStream_t)stream);
+    rc = p2l_wino_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip, w_packed + wi.wino, (hipStream_t)stream);
     if (rc) return rc;
-    next += p2l_wino_weight_floats(N_pad, K_pad) + p2l_wino_h2_weight_floats(N_pad, K_pad);
   }
-  // the fp16 x 2 image of the direct kernel's weight tile (p2l_h2.hip) behind everything else
-  return p2l_h2_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip, -1, next, (hipStream_t)stream);
+  return p2l_h2_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip, -1, w_packed + wi.h2, (hipStream_t)stream);
 }
 
 // sub-pixel weights of a P2L_WFMT_BF16X3W model: the bf16 x 3 image of p2l_pack_conv_weight_subpix_bf3
 // followed by the fp16 x 2 image of the same 16 phase-tap slabs
-extern "C" size_t p2l_packed_subpix_weight_floats(int N_pad, int K_pad, int wfmt) {
-  const size_t n = (size_t)16 * N_pad * K_pad;
-  if (wfmt == P2L_WFMT_F32) return n;
-  return n * 3 / 2 + (wfmt == P2L_WFMT_BF16X3W ? p2l_h2_weight_floats(N_pad, K_pad, 1) : 0);
-}
 extern "C" int p2l_pack_conv_weight_subpix_h2(const float* w_oihw, int O, int I, int N_pad, int K_pad,
                                               int transpose_flip, int mode, float* w_packed,
                                               void* stream) {
   int rc = p2l_pack_conv_weight_subpix_bf3(w_oihw, O, I, N_pad, K_pad, transpose_flip, mode, w_packed, stream);
   if (rc) return rc;
   return p2l_h2_pack(w_oihw, O, I, N_pad, K_pad, transpose_flip, mode,
-                     w_packed + (size_t)16 * N_pad * K_pad * 3 / 2, (hipStream_t)stream);
-}
-
-extern "C" int p2l_pack_conv_weight_bf3(const float* w_oihw, int O, int I, int taps, int N_pad,
-                                        int K_pad, int transpose_flip, float* w_packed,
-                                        void* stream) {
-  if (!w_oihw || !w_packed || taps != 9) return P2L_EINVAL;
-  const int N = transpose_flip ? I : O, K = transpose_flip ? O : I;
-  if (K_pad % 16 || N_pad % 32 || N_pad < N || K_pad < K) return P2L_EINVAL;
-  const size_t total = (size_t)taps * K_pad * N_pad;
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(cdiv(total, 256)), dim3(256),
-                     0, (hipStream_t)stream, w_oihw, w_packed, O, I, taps, N_pad,
-                     K_pad, 16, transpose_flip, 1);
-  return p2l_check_launch();
+                     w_packed + weight_images(9, true, N_pad, K_pad, P2L_WFMT_BF16X3W).h2, (hipStream_t)stream);
 }
