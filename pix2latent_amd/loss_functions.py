@@ -18,6 +18,7 @@ The weighted L2 pixel term (the StyleGAN2 projector's MSE; `ReconstructionLoss('
 (csrc/p2l_pixel.hip).  The un-weighted variants, and CPU tensors, use
 plain torch ops on the tensor's own device.
 """
+import collections
 import ctypes as C
 import os
 import warnings
@@ -805,47 +806,51 @@ class _LossEngine(object):
         self._memo[name][2].reader()
         return self._memo[name][1]
 
-    def pooled(self, target, weight, loss_mask, f, want_l1):
-        """-> _Pooled of conformed full-resolution tensors, memoised on their identity and version as `bind` does:
-        pooling runs once per chunk and generation, a step makes no new device tensors, and the cache slot of the
-        pooled-size LPIPS term (keyed on the identity of the POOLED tensors) stays the same."""
-        from . import ops
-        key = (self._ident(target), self._ident(weight), self._ident(loss_mask), f, want_l1)
+    def _memoised(self, what, target, weight, loss_mask, make):
+        """-> the _Pooled `make()` gave for these conformed tensors, memoised on their identity and version as
+        `bind` does (key: the three identities + `what`; LRU, 2 * MAX_SLOTS entries).  The sources are kept alive in
+        the entry: their data_ptr identifies them."""
+        key = (self._ident(target), self._ident(weight), self._ident(loss_mask)) + what
         ent = self._pooled.pop(key, None)
         if ent is None:
             if len(self._pooled) >= 2 * self.MAX_SLOTS:
                 self._pooled.pop(next(iter(self._pooled)))
-            wsum = None
-            if want_l1:
-                B, HW3 = target.size(0), target[0].numel()
-                wsum = torch.empty(B, device=target.device, dtype=torch.float32)
-                N.check(self.lib.p2l_weight_sum(N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum), B, HW3, N.stream()),
-                        'p2l_weight_sum')
-            # (the sources are kept alive: their data_ptr identifies them)
-            ent = _Pooled(ops.area_pool_nchw(target, f), ops.area_pool_nchw(weight, f, mul=loss_mask), wsum,
-                          (target, weight, loss_mask))
+            ent = make()
         else:
-            ent.guard.reader()                 # (pooled on another lane's stream, perhaps in this very step)
+            ent.guard.reader()                 # (made on another lane's stream, perhaps in this very step)
         self._pooled[key] = ent
         return ent
 
+    def _wsum(self, target, weight, loss_mask):
+        B, HW3 = target.size(0), target[0].numel()
+        wsum = torch.empty(B, device=target.device, dtype=torch.float32)
+        N.check(self.lib.p2l_weight_sum(N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum), B, HW3, N.stream()),
+                'p2l_weight_sum')
+        return wsum
+
+    def pooled(self, target, weight, loss_mask, f, want_l1):
+        """-> _Pooled of conformed full-resolution tensors: pooling runs once per chunk and generation, a step makes
+        no new device tensors, and the cache slot of the pooled-size LPIPS term (keyed on the identity of the POOLED
+        tensors) stays the same."""
+        from . import ops
+        held = (target, weight, loss_mask)
+
+        def make():
+            wsum = self._wsum(*held) if want_l1 else None
+            return _Pooled(ops.area_pool_nchw(target, f), ops.area_pool_nchw(weight, f, mul=loss_mask), wsum, held)
+        return self._memoised((f, want_l1), *held, make=make)
+
     def weight_sum(self, target, weight, loss_mask):
-        """-> wsum [B] of conformed tensors (p2l_weight_sum), memoised on their identity and version as `pooled`
-        does: once per chunk and generation.  For a pixel term that runs without a cache slot."""
-        key = (self._ident(target), self._ident(weight), self._ident(loss_mask), 'wsum')
-        ent = self._pooled.pop(key, None)
-        if ent is None:
-            if len(self._pooled) >= 2 * self.MAX_SLOTS:
-                self._pooled.pop(next(iter(self._pooled)))
-            B, HW3 = target.size(0), target[0].numel()
-            wsum = torch.empty(B, device=target.device, dtype=torch.float32)
-            N.check(self.lib.p2l_weight_sum(N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum), B, HW3, N.stream()),
-                    'p2l_weight_sum')
-            ent = _Pooled(None, None, wsum, (target, weight, loss_mask))
-        else:
-            ent.guard.reader()
-        self._pooled[key] = ent
-        return ent.wsum
+        """-> wsum [B] of conformed tensors (p2l_weight_sum), once per chunk and generation.  For a pixel term that
+        runs without a cache slot."""
+        held = (target, weight, loss_mask)
+        return self._memoised(('wsum',), *held, make=lambda: _Pooled(None, None, self._wsum(*held), held)).wsum
+
+    def read(self, slot):
+        """behind the last launch of a loss forward / backward that READS `slot`: with a second lane its stream may
+        be the one that evicts the slot (one stream: program order already protects an evicted slot)"""
+        if len(self._lanes) > 1:
+            slot.used()
 
     def _same_content(self, target, weight, loss_mask, use_lpips, B):
         """A generation of a CMA run starts from FRESH variables (reference base_cma_optimizer.py:79):
@@ -934,94 +939,11 @@ def _channels(t):
     return None if t is None else (t.size(0) if t.dim() == 3 else t.size(1))
 
 
-def _apply(eng, output, target, weight, loss_mask, beta, mode):
-    B = output.size(0)
-    # Reference broadcasting quirk (loss_functions.py:119-123): with a ONE-channel
-    # `_weight = loss_mask * weight` the numerator sum(|t - o| * _weight) runs over the 3
-    # image channels but the denominator sum(_weight) over one, i.e. the L1 term is 3x the
-    # 3-channel-weight value.  (The LPIPS map has one channel itself, so its term is not.)
-    wc, mc = _channels(weight), _channels(loss_mask)
-    l1_factor = 3.0 if (wc == 1 and mc in (None, 1)) else 1.0
-    if mode == 2:
-        l1_factor = 1.0
-    loss = _ProjLossFn.apply(output, eng.bind('target', target, B, like=output),
-                             eng.bind('weight', weight, B, like=output),
-                             eng.bind('loss_mask', loss_mask, B, like=output), eng,
-                             float(beta) / l1_factor, mode)
-    return loss if l1_factor == 1.0 else l1_factor * loss
-
-
-class _ProjLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, output, target, weight, loss_mask, eng, beta, mode):
-        # mode: 0 = L1 + beta*LPIPS, 1 = L1 only, 2 = LPIPS only
-        lib = eng.lib
-        B, _, H, W = output.shape
-        out_c = output.contiguous().float()
-        use_lpips = 0 if mode == 1 else 1
-        slot = eng.prepare(out_c, target, weight, loss_mask, use_lpips)
-        ctx.slot = slot
-        s = eng._scratch.here()
-        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, N.stream()),
-                'p2l_nchw3_to_nhwc16')
-        loss = torch.empty(B, device=output.device, dtype=torch.float32)
-        l1 = torch.empty_like(loss)
-        lp = torch.empty_like(loss)
-        vref = C.byref(eng.vgg.desc) if use_lpips else None
-        N.check(eng.f_fwd(vref, N.ptr(s.img16), N.ptr(target), N.ptr(weight),
-                          N.ptr(loss_mask), C.byref(slot.desc), N.f32(beta),
-                          use_lpips, B, H, W, N.ptr(s.ws),
-                          C.c_size_t(s.ws_bytes), N.ptr(loss), N.ptr(l1),
-                          N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
-        if len(eng._lanes) > 1:          # (one stream: program order already protects an evicted slot)
-            slot.used()
-        ctx.eng, ctx.beta, ctx.mode = eng, beta, mode
-        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None
-                              else torch.empty(0))
-        ctx.has_mask = loss_mask is not None
-        ctx.stamp = eng._scratch.stamp()
-        eng.last_l1, eng.last_lpips = l1, lp
-        if mode == 2:
-            return lp
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
-            return _ProjLossFn._backward(ctx, gloss)
-
-    @staticmethod
-    def _backward(ctx, gloss):
-        eng = ctx.eng
-        lib = eng.lib
-        out_c, target, weight, loss_mask = ctx.saved_tensors
-        if not ctx.has_mask:
-            loss_mask = None
-        B, _, H, W = out_c.shape
-        use_lpips = 0 if ctx.mode == 1 else 1
-        if eng._scratch.stale(ctx.stamp):
-            raise N.NativeError('loss workspace was reused by a later forward before '
-                                'backward(); use one loss object per in-flight graph')
-        s = eng._scratch.here()
-        g = gloss.contiguous().float()
-        if ctx.mode == 2:
-            use_lpips = 2          # the LPIPS term alone (L1 accumulation switched off)
-        N.check(eng.f_bwd(C.byref(eng.vgg.desc) if use_lpips else None,
-                          N.ptr(s.img16), N.ptr(target), N.ptr(weight),
-                          N.ptr(loss_mask), C.byref(ctx.slot.desc), N.f32(ctx.beta),
-                          use_lpips, N.ptr(g), B, H, W, N.ptr(s.ws),
-                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()),
-                'p2l_%sloss_bwd' % eng.prefix)
-        if len(eng._lanes) > 1:
-            ctx.slot.used()
-        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
-        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dimg16), N.ptr(dout), B, H, W, N.stream()),
-                'p2l_nhwc16_to_nchw3')
-        return dout, None, None, None, None, None, None
-
-
 def _pixel_factor(weight, loss_mask):
-    """the reference's one-channel-weight quirk (see `_apply`): 3 for a one-channel `weight * loss_mask`"""
+    """Reference broadcasting quirk (loss_functions.py:119-123): with a ONE-channel `_weight = loss_mask * weight`
+    the numerator sum(|t - o| * _weight) runs over the 3 image channels but the denominator sum(_weight) over one,
+    i.e. the pixel term is 3x the 3-channel-weight value.  (The LPIPS map has one channel itself, so its term is
+    not.)  -> 3 for a one-channel `weight * loss_mask`, else 1"""
     wc, mc = _channels(weight), _channels(loss_mask)
     return 3.0 if (wc == 1 and mc in (None, 1)) else 1.0
 
@@ -1031,248 +953,169 @@ def _stale_error():
                          'backward(); use one loss object per in-flight graph')
 
 
-def _apply_l2(eng, output, target, weight, loss_mask):
-    """the weighted L2 term alone (`ReconstructionLoss('l2')`), factor 3 of a one-channel weight included"""
+# What one call of `_ImageLossFn` runs (made once per call in `_apply`):
+#   f         0 = no plan; else the plan runs at [H/f, W/f] (1: on the packed image, > 1: on the pooled one)
+#   use_fwd, beta_fwd   `use_lpips` and `beta` of the plan's forward;  use_bwd, beta: of its backward
+#   pixel     None | 'plan' (the L1 term the plan computes itself) | 'l1' | 'l2' (p2l_l1_/l2_loss_* beside it)
+#   scale     weight of an 'l1' / 'l2' pixel term inside the Function: loss = scale * pixel + beta * lpips
+# An 'l1' / 'l2' term beside a full-size plan (f = 1) reads the image the plan staged (img16), puts its block partials
+# in `pix_part`, takes `wsum` from the slot's cache and ADDS its gradient into dimg16; otherwise (f = 0, f > 1) it
+# stages the image itself (full16 / l1_part / dfull16 of `grow_full`) with the memoised full-size `wsum`.
+_Form = collections.namedtuple('_Form', 'f use_fwd beta_fwd use_bwd beta pixel scale')
+
+
+def _apply(eng, output, target, weight, loss_mask, beta, pixel, f=1, pixel_weight=1.0):
+    """pixel_weight * (weighted `pixel` term, 'l1' | 'l2') + beta * (LPIPS term at [H/f, W/f]) [B] through the one
+    native Function; pixel = None / beta = None: the other term alone.  The factor 3 of a one-channel weight
+    (`_pixel_factor`) belongs to the pixel term: where the plan computes that term itself it takes beta / 3 and the
+    result is multiplied by 3 out here, as a torch op that autograd sees."""
     B = output.size(0)
-    factor = _pixel_factor(weight, loss_mask)
-    loss = _L2LossFn.apply(output, eng.bind('target', target, B, like=output),
-                           eng.bind('weight', weight, B, like=output),
-                           eng.bind('loss_mask', loss_mask, B, like=output), eng)
-    return loss if factor == 1.0 else factor * loss
+    k = _pixel_factor(weight, loss_mask)
+    outside = 1.0
+    if pixel is None:                      # LPIPS alone: the plan's L1 is switched off in the backward (use_lpips = 2)
+        form = _Form(f, 1, float(beta), 2, float(beta), None, 1.0)
+    elif beta is None and pixel == 'l2':   # no plan, no arena, no cache slot
+        form, outside = _Form(0, 0, 0.0, 0, 0.0, 'l2', 1.0), k
+    elif beta is None:                     # the plan without its network
+        form, outside = _Form(1, 0, 0.0, 0, 0.0, 'plan', 1.0), k
+    elif pixel == 'l1' and f == 1:
+        form, outside = _Form(1, 1, float(beta) / k, 1, float(beta) / k, 'plan', 1.0), k
+    else:                                  # the plan as the LPIPS term alone, the pixel term beside it
+        form = _Form(f, 1, 1.0, 2, float(beta), pixel, float(pixel_weight) * k)
+    loss = _ImageLossFn.apply(output, eng.bind('target', target, B, like=output),
+                              eng.bind('weight', weight, B, like=output),
+                              eng.bind('loss_mask', loss_mask, B, like=output), eng, form)
+    return loss if outside == 1.0 else outside * loss
 
 
-class _L2LossFn(torch.autograd.Function):
-    """L2w(out, target, weight * loss_mask) [B] through p2l_l2_loss_fwd / _bwd: stage the image (one launch), the
-    weight sum once per (target, weight, loss_mask) identity, the kernels, unpack.  The staging and the block
-    partials are the lane's full-resolution scratch (`lanes.Scratch.grow_full`); no LPIPS arena is allocated."""
+class _ImageLossFn(torch.autograd.Function):
+    """Every native image loss: one sequence of optional steps over a `_Form`.  Forward: stage the image for the
+    plan (pack, or pool + pack in one launch); the plan; stage the image at full size if the pixel term is not on
+    the plan's buffer; the pixel term; combine.  Backward, the mirror: the plan; the pixel term; ONE unpack launch.
+
+      form (chosen in the losses' __call__)        plan forward         pixel term                  plan backward  returns
+      L1 + beta LPIPS, f = 1  (ProjectionLoss)     use_lpips 1, beta/k  the plan's own              1, beta/k      loss
+      L1 alone (ReconstructionLoss 'l1')           use_lpips 0, NULL net  the plan's own            0              loss
+      LPIPS alone, any f  (PerceptualLoss, a = 0)  use_lpips 1, beta    --                          2              lp
+      L2 alone (ReconstructionLoss 'l2')           --                   l2 on full16, accumulate 0  --             l2
+      a L2 + beta LPIPS, f = 1                     use_lpips 1, 1.0     l2 on img16, accumulate 1   2, beta        a k l2 + beta lp
+      a L1|L2 + beta LPIPS, f > 1                  use_lpips 1, 1.0     l1|l2 on full16, acc. 0     2, beta        a k pix + beta lp
+
+    (k = `_pixel_factor`, a = pixel_weight; a L1 with 0 < a != 1 is a * (L1 + (beta / a) LPIPS) in ProjectionLoss.)
+    * The plan's forward has no LPIPS-only form: with a pixel term beside it, or pooled, it runs with use_lpips = 1
+      and beta = 1, and its own L1 pass -- at full size in the fifth row -- is computed and discarded (DESIGN.md
+      section 14); the backward's use_lpips = 2 writes d (beta * LPIPS) alone into dimg16.
+    * L2 alone: stage the image (one launch), the weight sum once per (target, weight, loss_mask) identity, the
+      kernels, unpack; the staging and the block partials are the lane's full-resolution scratch
+      (`lanes.Scratch.grow_full`), no LPIPS arena is allocated.
+    * L2 beside a full-size plan: on the image the plan staged, block partials in `pix_part`, the weight sum the one
+      in the slot's cache; p2l_l2_loss_bwd adds the pixel term with gscale = a k g into dimg16.
+    * f > 1: the engine's plan is allocated and prepared at the pooled size; the pixel term runs at full resolution,
+      and the backward ends in ONE launch that writes d out = d pixel + expand_f(d LPIPS) / f^2.
+    `eng.last_l1` is the pixel term of the last forward (the L2 value where that is the pixel term; the plan's
+    by-product where there is none), `eng.last_lpips` the LPIPS term."""
 
     @staticmethod
-    def forward(ctx, output, target, weight, loss_mask, eng):
-        lib = eng.lib
+    def forward(ctx, output, target, weight, loss_mask, eng, form):
+        lib, f, pixel = eng.lib, form.f, form.pixel
         B, _, H, W = output.shape
         out_c = output.contiguous().float()
-        wsum = eng.weight_sum(target, weight, loss_mask)
-        s = eng._scratch.grow_full(B, H, W, lib.p2l_l2_loss_nblk(H, W), output.device)
-        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()), 'p2l_nchw3_to_nhwc16')
-        loss = torch.empty(B, device=output.device, dtype=torch.float32)
-        N.check(lib.p2l_l2_loss_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), N.ptr(wsum),
-                                    N.ptr(loss), N.ptr(s.l1_part), B, H, W, N.stream()), 'p2l_l2_loss_fwd')
-        ctx.eng, ctx.wsum = eng, wsum
-        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
-        ctx.has_mask = loss_mask is not None
-        ctx.stamp = eng._scratch.stamp()
-        eng.last_l1 = loss
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
-            return _L2LossFn._backward(ctx, gloss)
-
-    @staticmethod
-    def _backward(ctx, gloss):
-        eng = ctx.eng
-        lib = eng.lib
-        out_c, target, weight, loss_mask = ctx.saved_tensors
-        if not ctx.has_mask:
-            loss_mask = None
-        B, _, H, W = out_c.shape
-        if eng._scratch.stale(ctx.stamp):
-            raise _stale_error()
-        s = eng._scratch.here()
-        g = gloss.contiguous().float()
-        N.check(lib.p2l_l2_loss_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                                    N.ptr(ctx.wsum), N.ptr(g), N.ptr(s.dfull16), B, H, W, 0, N.stream()),
-                'p2l_l2_loss_bwd')
-        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
-        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dfull16), N.ptr(dout), B, H, W, N.stream()), 'p2l_nhwc16_to_nchw3')
-        return dout, None, None, None, None
-
-
-def _apply_proj_l2(eng, output, target, weight, loss_mask, beta, pixel_weight):
-    """pixel_weight * L2w + beta * LPIPSw at the output's own resolution"""
-    B = output.size(0)
-    return _ProjL2LossFn.apply(output, eng.bind('target', target, B, like=output),
-                               eng.bind('weight', weight, B, like=output),
-                               eng.bind('loss_mask', loss_mask, B, like=output), eng, float(beta),
-                               float(pixel_weight) * _pixel_factor(weight, loss_mask))
-
-
-class _ProjL2LossFn(torch.autograd.Function):
-    """The L2 term beside the plan, on the image the plan staged.  Forward: pack, the plan (use_lpips = 1: its
-    forward has no LPIPS-only form, so its full-resolution L1 pass runs too and is discarded),
-    L2, then loss = scale * l2 + beta * lp.  Backward: the plan with use_lpips = 2 writes
-    d (beta * LPIPS) into dimg16, p2l_l2_loss_bwd adds the pixel term with gscale = scale * g (accumulate = 1).
-    The weight sum is the one in the slot's cache."""
-
-    @staticmethod
-    def forward(ctx, output, target, weight, loss_mask, eng, beta, scale):
-        lib = eng.lib
-        B, _, H, W = output.shape
-        out_c = output.contiguous().float()
-        slot = eng.prepare(out_c, target, weight, loss_mask, 1)
-        nblk = lib.p2l_l2_loss_nblk(H, W)
-        s = eng._scratch.grow_part(eng._scratch.here().cap * nblk, output.device)
-        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, N.stream()), 'p2l_nchw3_to_nhwc16')
-        loss = torch.empty(B, device=output.device, dtype=torch.float32)
-        l1 = torch.empty_like(loss)
-        l2 = torch.empty_like(loss)
-        lp = torch.empty_like(loss)
-        # (the plan's own L1 term lands in `l1`: a by-product)
-        N.check(eng.f_fwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                          C.byref(slot.desc), N.f32(1.0), 1, B, H, W, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
-                          N.ptr(loss), N.ptr(l1), N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
-        wsum = C.c_void_p(slot.desc.wsum)
-        N.check(lib.p2l_l2_loss_fwd(N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), wsum,
-                                    N.ptr(l2), N.ptr(s.pix_part), B, H, W, N.stream()), 'p2l_l2_loss_fwd')
-        # loss = scale * l2 + beta * lp
-        N.check(lib.p2l_vec_scale_div(N.ptr(l2), None, N.ptr(loss), B, N.f32(scale), N.stream()),
-                'p2l_vec_scale_div')
-        N.check(lib.p2l_reduce_rows(N.ptr(lp), N.ptr(loss), B, 1, N.f32(beta), None, 1, N.stream()),
-                'p2l_reduce_rows')
-        if len(eng._lanes) > 1:
-            slot.used()
-        ctx.eng, ctx.slot, ctx.beta, ctx.scale = eng, slot, beta, scale
-        ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
-        ctx.has_mask = loss_mask is not None
-        ctx.stamp = eng._scratch.stamp()
-        eng.last_l1, eng.last_lpips = l2, lp
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
-            return _ProjL2LossFn._backward(ctx, gloss)
-
-    @staticmethod
-    def _backward(ctx, gloss):
-        eng = ctx.eng
-        lib = eng.lib
-        out_c, target, weight, loss_mask = ctx.saved_tensors
-        if not ctx.has_mask:
-            loss_mask = None
-        B, _, H, W = out_c.shape
-        if eng._scratch.stale(ctx.stamp):
-            raise _stale_error()
-        s = eng._scratch.here()
-        g = gloss.contiguous().float()
-        N.check(eng.f_bwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                          C.byref(ctx.slot.desc), N.f32(ctx.beta), 2, N.ptr(g), B, H, W, N.ptr(s.ws),
-                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()), 'p2l_%sloss_bwd' % eng.prefix)
-        gl = g if ctx.scale == 1.0 else g * ctx.scale
-        N.check(lib.p2l_l2_loss_bwd(N.ptr(s.img16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                                    C.c_void_p(ctx.slot.desc.wsum), N.ptr(gl), N.ptr(s.dimg16), B, H, W, 1,
-                                    N.stream()), 'p2l_l2_loss_bwd')
-        if len(eng._lanes) > 1:
-            ctx.slot.used()
-        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
-        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dimg16), N.ptr(dout), B, H, W, N.stream()), 'p2l_nhwc16_to_nchw3')
-        return dout, None, None, None, None, None, None
-
-
-def _apply_pooled(eng, output, target, weight, loss_mask, beta, mode, f, pixel='l1', pixel_weight=1.0):
-    """`_apply` with the LPIPS term at [H/f, W/f]: L1w(out, ...) + beta * LPIPSw(pool_f(out), pool_f(target),
-    pool_f(weight * loss_mask)); mode 2 = the second term alone.  The one-channel-weight factor 3 of the reference
-    (see `_apply`) belongs to the L1 term.  pixel = 'l2': pixel_weight * L2w(out, ...) in the place of the L1 term
-    (its weight travels with the factor 3)."""
-    B = output.size(0)
-    wc, mc = _channels(weight), _channels(loss_mask)
-    l1_factor = 3.0 if (mode == 0 and wc == 1 and mc in (None, 1)) else 1.0
-    if pixel == 'l2':
-        l1_factor = l1_factor * float(pixel_weight)
-    return _PooledLossFn.apply(output, eng.bind('target', target, B, like=output),
-                               eng.bind('weight', weight, B, like=output),
-                               eng.bind('loss_mask', loss_mask, B, like=output), eng, float(beta), l1_factor,
-                               mode, f, pixel)
-
-
-class _PooledLossFn(torch.autograd.Function):
-    """The engine's plan is allocated and prepared at the pooled size and driven as the LPIPS term alone; the L1
-    term runs at full resolution through p2l_l1_loss_fwd / _bwd.  Forward: pool + pack (one launch), the plan,
-    [pack, L1].  Backward: the plan, [L1], then ONE launch that writes d out = dL1 + expand_f(dLPIPS) / f^2."""
-
-    @staticmethod
-    def forward(ctx, output, target, weight, loss_mask, eng, beta, l1_factor, mode, f, pixel='l1'):
-        lib = eng.lib
-        # the pixel term's entry points: L1, or L2 (same layouts and contract)
-        pix_nblk, pix_fwd, pix_name = (
-            (lib.p2l_l2_loss_nblk, lib.p2l_l2_loss_fwd, 'p2l_l2_loss_fwd') if pixel == 'l2' else
-            (lib.p2l_l1_loss_nblk, lib.p2l_l1_loss_fwd, 'p2l_l1_loss_fwd'))
-        B, _, H, W = output.shape
-        h, w = H // f, W // f
-        out_c = output.contiguous().float()
-        want_l1 = mode != 2
-        ent = eng.pooled(target, weight, loss_mask, f, want_l1)
-        slot = eng.prepare(ent.target, ent.target, ent.weight, None, 1)      # (first argument: shape and device)
-        s = eng._scratch.here()
-        N.check(lib.p2l_area_pool3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, f, N.stream()),
-                'p2l_area_pool3_to_nhwc16')
-        loss = torch.empty(B, device=output.device, dtype=torch.float32)
-        l1 = torch.empty_like(loss)
-        lp = torch.empty_like(loss)
-        # (the plan's own L1 term, of the pooled images, lands in `l1`: a by-product unless this is mode 2)
-        N.check(eng.f_fwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(ent.target), N.ptr(ent.weight), None,
-                          C.byref(slot.desc), N.f32(1.0), 1, B, h, w, N.ptr(s.ws), C.c_size_t(s.ws_bytes),
-                          N.ptr(loss), N.ptr(l1), N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
-        if want_l1:
-            eng._scratch.grow_full(B, H, W, pix_nblk(H, W), output.device)
-            l1 = torch.empty_like(loss)
-            N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()),
-                    'p2l_nchw3_to_nhwc16')
-            N.check(pix_fwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                            N.ptr(ent.wsum), N.ptr(l1), N.ptr(s.l1_part), B, H, W, N.stream()),
-                    pix_name)
-            # loss = l1_factor * l1 + beta * lp
-            N.check(lib.p2l_vec_scale_div(N.ptr(l1), None, N.ptr(loss), B, N.f32(l1_factor), N.stream()),
-                    'p2l_vec_scale_div')
-            N.check(lib.p2l_reduce_rows(N.ptr(lp), N.ptr(loss), B, 1, N.f32(beta), None, 1, N.stream()),
-                    'p2l_reduce_rows')
-        if len(eng._lanes) > 1:
-            slot.used()
-        ctx.eng, ctx.slot, ctx.ent = eng, slot, ent
-        ctx.beta, ctx.l1_factor, ctx.want_l1, ctx.f, ctx.pixel = beta, l1_factor, want_l1, f, pixel
+        new = lambda: torch.empty(B, device=output.device, dtype=torch.float32)
+        slot = ent = wsum = loss = l1 = lp = None
+        if f:
+            # the plan, on the packed image (f = 1) or on the pooled one
+            if f > 1:
+                ent = eng.pooled(target, weight, loss_mask, f, pixel is not None)
+                wsum, planned = ent.wsum, (ent.target, ent.weight, None)
+                slot = eng.prepare(ent.target, *planned, 1)            # (first argument: shape and device)
+            else:
+                planned = (target, weight, loss_mask)
+                slot = eng.prepare(out_c, *planned, form.use_fwd)
+            s = eng._scratch.here()
+            if f > 1:
+                N.check(lib.p2l_area_pool3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, f, N.stream()),
+                        'p2l_area_pool3_to_nhwc16')
+            else:
+                N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.img16), B, H, W, N.stream()),
+                        'p2l_nchw3_to_nhwc16')
+            loss, l1, lp = new(), new(), new()
+            # (the plan's own L1 term lands in `l1`: a by-product unless pixel == 'plan')
+            N.check(eng.f_fwd(C.byref(eng.vgg.desc) if form.use_fwd else None, N.ptr(s.img16),
+                              *map(N.ptr, planned), C.byref(slot.desc), N.f32(form.beta_fwd), form.use_fwd,
+                              B, H // f, W // f, N.ptr(s.ws), C.c_size_t(s.ws_bytes), N.ptr(loss), N.ptr(l1),
+                              N.ptr(lp), N.stream()), 'p2l_%sloss_fwd' % eng.prefix)
+        if pixel in ('l1', 'l2'):
+            nblk = getattr(lib, 'p2l_%s_loss_nblk' % pixel)(H, W)
+            if f == 1:
+                s = eng._scratch.grow_part(s.cap * nblk, output.device)
+                img, part, wsum_p = s.img16, s.pix_part, C.c_void_p(slot.desc.wsum)
+            else:
+                if wsum is None:
+                    wsum = eng.weight_sum(target, weight, loss_mask)
+                s = eng._scratch.grow_full(B, H, W, nblk, output.device)
+                N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(out_c), N.ptr(s.full16), B, H, W, N.stream()),
+                        'p2l_nchw3_to_nhwc16')
+                img, part, wsum_p = s.full16, s.l1_part, N.ptr(wsum)
+            l1 = new()
+            N.check(getattr(lib, 'p2l_%s_loss_fwd' % pixel)(
+                N.ptr(img), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), wsum_p, N.ptr(l1), N.ptr(part),
+                B, H, W, N.stream()), 'p2l_%s_loss_fwd' % pixel)
+            if f:
+                # loss = scale * l1 + beta * lp
+                N.check(lib.p2l_vec_scale_div(N.ptr(l1), None, N.ptr(loss), B, N.f32(form.scale), N.stream()),
+                        'p2l_vec_scale_div')
+                N.check(lib.p2l_reduce_rows(N.ptr(lp), N.ptr(loss), B, 1, N.f32(form.beta), None, 1, N.stream()),
+                        'p2l_reduce_rows')
+        if f:
+            eng.read(slot)
+        ctx.eng, ctx.form, ctx.slot, ctx.ent, ctx.wsum = eng, form, slot, ent, wsum
         ctx.save_for_backward(out_c, target, weight, loss_mask if loss_mask is not None else torch.empty(0))
         ctx.has_mask = loss_mask is not None
         ctx.stamp = eng._scratch.stamp()
         eng.last_l1, eng.last_lpips = l1, lp
-        return loss if want_l1 else lp
+        return lp if pixel is None else loss if f else l1
 
     @staticmethod
     def backward(ctx, gloss):
         with lanes.use(ctx.stamp[0]):    # (autograd's thread: the scratch of the forward's lane)
-            return _PooledLossFn._backward(ctx, gloss)
-
-    @staticmethod
-    def _backward(ctx, gloss):
-        eng, ent, f = ctx.eng, ctx.ent, ctx.f
-        lib = eng.lib
-        out_c, target, weight, loss_mask = ctx.saved_tensors
-        if not ctx.has_mask:
-            loss_mask = None
-        B, _, H, W = out_c.shape
-        if eng._scratch.stale(ctx.stamp):
-            raise N.NativeError('loss workspace was reused by a later forward before '
-                                'backward(); use one loss object per in-flight graph')
-        s = eng._scratch.here()
-        g = gloss.contiguous().float()
-        # d (beta * LPIPS) / d pool_f(out), the LPIPS term alone (use_lpips = 2)
-        N.check(eng.f_bwd(C.byref(eng.vgg.desc), N.ptr(s.img16), N.ptr(ent.target), N.ptr(ent.weight), None,
-                          C.byref(ctx.slot.desc), N.f32(ctx.beta), 2, N.ptr(g), B, H // f, W // f, N.ptr(s.ws),
-                          C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.stream()), 'p2l_%sloss_bwd' % eng.prefix)
-        if len(eng._lanes) > 1:
-            ctx.slot.used()
-        dfull = None
-        if ctx.want_l1:
-            gl = g if ctx.l1_factor == 1.0 else g * ctx.l1_factor
-            dfull = s.dfull16
-            pix_bwd = lib.p2l_l2_loss_bwd if ctx.pixel == 'l2' else lib.p2l_l1_loss_bwd
-            N.check(pix_bwd(N.ptr(s.full16), N.ptr(target), N.ptr(weight), N.ptr(loss_mask),
-                            N.ptr(ent.wsum), N.ptr(gl), N.ptr(dfull), B, H, W, 0, N.stream()),
-                    'p2l_%s_loss_bwd' % ctx.pixel)
-        dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
-        N.check(lib.p2l_area_unpool16_add_nchw3(N.ptr(s.dimg16), N.ptr(dfull), N.ptr(dout), B, H, W, f,
-                                                N.stream()), 'p2l_area_unpool16_add_nchw3')
-        return dout, None, None, None, None, None, None, None, None, None
+            eng, form, slot, ent = ctx.eng, ctx.form, ctx.slot, ctx.ent
+            lib, f, pixel = eng.lib, form.f, form.pixel
+            out_c, target, weight, loss_mask = ctx.saved_tensors
+            if not ctx.has_mask:
+                loss_mask = None
+            B, _, H, W = out_c.shape
+            if eng._scratch.stale(ctx.stamp):
+                raise _stale_error()
+            s = eng._scratch.here()
+            g = gloss.contiguous().float()
+            beside = pixel in ('l1', 'l2')
+            if f:
+                planned = (ent.target, ent.weight, None) if f > 1 else (target, weight, loss_mask)
+                N.check(eng.f_bwd(C.byref(eng.vgg.desc) if form.use_bwd else None, N.ptr(s.img16),
+                                  *map(N.ptr, planned), C.byref(slot.desc), N.f32(form.beta), form.use_bwd,
+                                  N.ptr(g), B, H // f, W // f, N.ptr(s.ws), C.c_size_t(s.ws_bytes), N.ptr(s.dimg16),
+                                  N.stream()), 'p2l_%sloss_bwd' % eng.prefix)
+            on_plan = beside and f == 1           # the pixel term reads the slot too (its wsum)
+            if f and not on_plan:
+                eng.read(slot)
+            dpix = None
+            if beside:
+                gl = g if form.scale == 1.0 else g * form.scale
+                img, dpix, wsum_p = (s.img16, s.dimg16, C.c_void_p(slot.desc.wsum)) if on_plan else \
+                    (s.full16, s.dfull16, N.ptr(ctx.wsum))
+                N.check(getattr(lib, 'p2l_%s_loss_bwd' % pixel)(
+                    N.ptr(img), N.ptr(target), N.ptr(weight), N.ptr(loss_mask), wsum_p, N.ptr(gl), N.ptr(dpix),
+                    B, H, W, 1 if on_plan else 0, N.stream()), 'p2l_%s_loss_bwd' % pixel)
+                if on_plan:
+                    eng.read(slot)
+            dout = torch.empty(B, 3, H, W, device=out_c.device, dtype=torch.float32)
+            if f > 1:
+                N.check(lib.p2l_area_unpool16_add_nchw3(N.ptr(s.dimg16), N.ptr(dpix), N.ptr(dout), B, H, W, f,
+                                                        N.stream()), 'p2l_area_unpool16_add_nchw3')
+            else:
+                N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.dimg16 if f else dpix), N.ptr(dout), B, H, W, N.stream()),
+                        'p2l_nhwc16_to_nchw3')
+            return dout, None, None, None, None, None
 
 
 _VGG_PARAMS = {}
@@ -1356,21 +1199,13 @@ class ProjectionLoss(nn.Module):
         f = lpips_pool_factor(output.shape, self.lpips_size)
         eng, a = self._engine, self.pixel_weight
         if self.pixel_loss == 'l2':
-            if f == 1:
-                return _apply_proj_l2(eng, output, target, weight, loss_mask, self.beta, a)
-            return _apply_pooled(eng, output, target, weight, loss_mask, self.beta, 0, f, 'l2', a)
+            return _apply(eng, output, target, weight, loss_mask, self.beta, 'l2', f, a)
         if a == 1.0:
-            if f == 1:
-                return _apply(eng, output, target, weight, loss_mask, self.beta, 0)
-            return _apply_pooled(eng, output, target, weight, loss_mask, self.beta, 0, f)
+            return _apply(eng, output, target, weight, loss_mask, self.beta, 'l1', f)
         if a == 0.0:                            # the LPIPS term alone
-            lp = _apply(eng, output, target, weight, loss_mask, 1.0, 2) if f == 1 else \
-                _apply_pooled(eng, output, target, weight, loss_mask, 1.0, 2, f)
-            return self.beta * lp
+            return self.beta * _apply(eng, output, target, weight, loss_mask, 1.0, None, f)
         # a * L1 + beta * LPIPS = a * (L1 + (beta / a) * LPIPS): the rescaling route of the factor 3
-        if f == 1:
-            return a * _apply(eng, output, target, weight, loss_mask, self.beta / a, 0)
-        return a * _apply_pooled(eng, output, target, weight, loss_mask, self.beta / a, 0, f)
+        return a * _apply(eng, output, target, weight, loss_mask, self.beta / a, 'l1', f)
 
 
 class ReconstructionLoss(nn.Module):
@@ -1393,9 +1228,8 @@ class ReconstructionLoss(nn.Module):
         if self._native and weight is not None and _native_ok(output, target, weight):
             if self._engine is None:
                 self._engine = _LossEngine(None)
-            if self.loss_fn is l2_loss:
-                return _apply_l2(self._engine, output, target, weight, loss_mask)
-            return _apply(self._engine, output, target, weight, loss_mask, 0.0, 1)
+            pixel = 'l2' if self.loss_fn is l2_loss else 'l1'
+            return _apply(self._engine, output, target, weight, loss_mask, None, pixel)
         loss = self.loss_fn(output, target)
         if weight is not None:
             _weight = weight if loss_mask is None else (loss_mask * weight)
@@ -1417,6 +1251,4 @@ class PerceptualLoss(nn.Module):
 
     def __call__(self, output, target, weight=None, loss_mask=None):
         f = lpips_pool_factor(output.shape, self.lpips_size)
-        if f == 1:
-            return _apply(self._engine, output, target, weight, loss_mask, 1.0, 2)
-        return _apply_pooled(self._engine, output, target, weight, loss_mask, 1.0, 2, f)
+        return _apply(self._engine, output, target, weight, loss_mask, 1.0, None, f)
