@@ -834,7 +834,14 @@ typedef struct P2LGConv {         /* generic NHWC conv: any size / stride / padd
   int32_t reserved0;
 } P2LGConv;
 /* y = [mask>0] relu?( conv(pro_s*x+pro_t zero-padded) + bias + res );
- * w packed by p2l_pack_conv_weight(taps = KH*KW, K chunk 16).                          */
+ * w packed by p2l_pack_gconv_weight: [tap][Cin/16][Cout][16] for every kernel size
+ * (p2l_pack_conv_weight gives the same layout for taps other than 1 and 9).
+ * Ho = (Hi + 2 pad - KH) / stride + 1 (floor; Wo alike); columns n < n_store of y, res and
+ * mask are touched, rows at pitch y_ld / res_ld / mask_ld.  P2L_EINVAL before any launch:
+ * a null d, x, w or y; Cin % 16, Cout % 64, x_ld % 4, x_ld < Cin; KH, KW, stride, B, Hi or
+ * Wi < 1; pad < 0; Ho or Wo < 1; exactly one of pro_s / pro_t; n_store < 0 or > Cout;
+ * y_ld < n_store (0 counted as Cout); res with res_ld < n_store; mask with mask_ld <
+ * n_store.  P2L_EUNSUP: B*Ho*Wo*max(y_ld, Cout) >= 2^31.                                */
 int p2l_gconv_fwd(const P2LGConv* d, const float* x, const float* w_packed, const float* bias,
                   const float* pro_s, const float* pro_t, const float* res, const float* mask,
                   float* y, void* stream);

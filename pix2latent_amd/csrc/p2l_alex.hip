@@ -213,6 +213,11 @@ extern "C" int p2l_gconv_fwd(const P2LGConv* d, const float* x, const float* w, 
   if (!d || !x || !w || !y) return P2L_EINVAL;
   if (d->Cin % 16 || d->Cout % 64 || d->x_ld % 4 || d->x_ld < d->Cin) return P2L_EINVAL;
   if (d->KH < 1 || d->KW < 1 || d->stride < 1 || d->pad < 0 || d->B < 1) return P2L_EINVAL;
+  if (d->Hi < 1 || d->Wi < 1) return P2L_EINVAL;   // (pad >= K would give Ho >= 1 and a clamp to row -1)
+  if (d->n_store < 0 || d->n_store > d->Cout) return P2L_EINVAL;
+  const int n_store = d->n_store > 0 ? d->n_store : d->Cout;
+  if (d->y_ld < n_store) return P2L_EINVAL;
+  if ((res && d->res_ld < n_store) || (mask && d->mask_ld < n_store)) return P2L_EINVAL;
   const int Ho = (d->Hi + 2 * d->pad - d->KH) / d->stride + 1;
   const int Wo = (d->Wi + 2 * d->pad - d->KW) / d->stride + 1;
   if (Ho < 1 || Wo < 1) return P2L_EINVAL;
@@ -223,7 +228,7 @@ extern "C" int p2l_gconv_fwd(const P2LGConv* d, const float* x, const float* w, 
   k.x = x; k.w = w; k.bias = bias; k.res = res; k.mask = mask; k.pro_s = pro_s; k.pro_t = pro_t;
   k.y = y; k.B = d->B; k.Hi = d->Hi; k.Wi = d->Wi; k.Cin = d->Cin; k.x_ld = d->x_ld;
   k.Ho = Ho; k.Wo = Wo; k.Cout = d->Cout; k.y_ld = d->y_ld; k.res_ld = d->res_ld;
-  k.mask_ld = d->mask_ld; k.n_store = d->n_store > 0 ? d->n_store : d->Cout;
+  k.mask_ld = d->mask_ld; k.n_store = n_store;
   k.KH = d->KH; k.KW = d->KW; k.stride = d->stride; k.pad = d->pad; k.relu = d->relu;
   k.M = (int)M;
   hipLaunchKernelGGL(gconv_mfma_kernel, dim3(cdiv(M, 64), d->Cout / 64), dim3(256), 0, ST(stream), k);

@@ -2330,6 +2330,248 @@ def subpix_arb_bound(c, r64, ax):
                           res=None, act=ACT_NONE), r64, ax, subpix_k)
 
 
+# ---- generic gather conv (tests/test_gconv_kernels_gpu.py) ----------------------------------------------------------
+# gconv_mfma_kernel behind p2l_gconv_fwd (csrc/p2l_alex.hip): every conv of the AlexNet and SqueezeNet LPIPS plans and,
+# through transpose_flip packings, their input gradients.  A case is the LAUNCH: x [B, Hi, Wi, Cin] -> y [B, Ho, Wo,
+# n_store of Cout], a weight of O x I real channels packed into Cout x Cin.  A `dgrad` case draws the OIHW weight wf [I,
+# O, KH, KW] of the stride-1 forward conv it differentiates (padding K - 1 - pad), packs it with transpose_flip and is
+# judged against that conv's float64 vjp.
+def gconv_out(c):
+    return (c['Hi'] + 2 * c['pad'] - c['KH']) // c['stride'] + 1, (c['Wi'] + 2 * c['pad'] - c['KW']) // c['stride'] + 1
+
+
+def gconv(x, w, stride=1, pad=0, pro_s=None, pro_t=None, bias=None, res=None, mask=None, relu=False, acc=None):
+    """the header's contract in the dtype of x: y = [mask > 0] relu?( conv(zero_pad(pro_s x + pro_t)) + bias + res ), x
+    [B, Hi, Wi, C], w [N, C, KH, KW], pro_s / pro_t [C], bias [N], res / mask [B, Ho, Wo, N]; Ho = (Hi + 2 pad - KH)
+    // stride + 1.  `acc` replaces the conv's sum (a restatement's accumulator, a vjp).  -> dict: y, den = sum over
+    taps and channels of (|pro_s| |x| + |pro_t|) |w| + |bias| + |res|, carried through the ReLU and the mask"""
+    dt = x.dtype
+    w = w.to(dt)
+    a, aabs = x, x.abs()
+    if pro_s is not None:
+        a, aabs = fma(x, pro_s.to(dt), pro_t.to(dt)), x.abs() * pro_s.to(dt).abs() + pro_t.to(dt).abs()
+    conv = lambda u, v: F.conv2d(u.permute(0, 3, 1, 2), v, stride=stride, padding=pad).permute(0, 2, 3, 1)
+    v = conv(a, w) if acc is None else acc.to(dt)
+    den = conv(aabs, w.abs())
+    if bias is not None:
+        v, den = v + bias.to(dt), den + bias.to(dt).abs()
+    if res is not None:
+        v, den = v + res.to(dt), den + res.to(dt).abs()
+    if relu:
+        v = torch.relu(v)
+    if mask is not None:
+        v = torch.where(mask > 0, v, torch.zeros_like(v))
+    return dict(y=v.contiguous(), den=den.contiguous())
+
+
+def gconv_cols(a, c):
+    """im2col of the zero-padded a [B, Hi, Wi, C] with the K axis in the order gconv_mfma_kernel walks it: tap (ky KW
+    + kx; pixel (oy stride - pad + ky, ox stride - pad + kx)), 16-channel chunk, then the eight 32x32x2 MFMAs, each
+    of which takes channels j and 8 + j -> [B, Ho, Wo, KH KW C]"""
+    B, C = a.shape[0], a.shape[-1]
+    Ho, Wo = gconv_out(c)
+    s, p = c['stride'], c['pad']
+    ap = F.pad(a, (0, 0, p, p, p, p))
+    taps = torch.stack([ap[:, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]
+                        for ky in range(c['KH']) for kx in range(c['KW'])], dim=3)              # [B, Ho, Wo, T, C]
+    return taps.reshape(B, Ho, Wo, -1, C // 16, 2, 8).transpose(-1, -2).reshape(B, Ho, Wo, -1)
+
+
+def gconv_wmat(w):
+    """[N, C, KH, KW] -> [N, KH KW C] in gconv_cols' order"""
+    N, C = w.shape[:2]
+    return w.reshape(N, C, -1).permute(0, 2, 1).reshape(N, -1, C // 16, 2, 8).transpose(-1, -2).reshape(N, -1)
+
+
+def gconv_pack(w, N_pad, K_pad, flip=False, kc=16):
+    """host statement of p2l_pack_gconv_weight (and of p2l_pack_conv_weight at taps 25 / 121): OIHW -> [tap][K_pad /
+    kc][N_pad][kc], zero fill; flip: the input gradient's weight, N = I, K = O, taps reversed"""
+    O, I = w.shape[:2]
+    m = w.reshape(O, I, -1)
+    if flip:
+        m = m.permute(1, 0, 2).flip(2)
+    T = m.shape[2]
+    full = torch.zeros(N_pad, K_pad, T, dtype=w.dtype)
+    full[:m.shape[0], :m.shape[1]] = m
+    return full.permute(2, 1, 0).reshape(T, K_pad // kc, kc, N_pad).permute(0, 1, 3, 2).contiguous().reshape(-1)
+
+
+def _gc(name, K, stride, pad, HW, B, Cin, Cout, **kw):
+    KH, KW = K if isinstance(K, tuple) else (K, K)
+    c = dict(name=name, KH=KH, KW=KW, stride=stride, pad=pad, Hi=HW[0], Wi=HW[1], B=B, Cin=Cin, Cout=Cout, I=Cin, O=Cout,
+             pro=False, bias=False, relu=False, res=False, mask=False, n_store=None, tight=False, aux_tight=False,
+             x_off=False, dgrad=False, y_ld=None, col=0)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    c['n_store'] = c['O'] if c['n_store'] is None else c['n_store']
+    if c['y_ld'] is None:
+        c['y_ld'] = c['n_store'] + (0 if c['tight'] else 4)
+    return c
+
+
+def gconv_id(c):
+    return c['name']
+
+
+_FIRST = dict(I=3, pro=True, bias=True, relu=True)
+_BR = dict(bias=True, relu=True)
+GCONV_CASES = [
+    # the strided first convs on an NHWC16 image: three real channels, the scaling layer as the prologue
+    _gc('alex0-11x11s4p2-23x19', 11, 4, 2, (23, 19), 2, 16, 64, **_FIRST),               # M = 40: one ragged block
+    _gc('alex0-11x11s4p2-22x22', 11, 4, 2, (22, 22), 2, 16, 64, **_FIRST),               # the last row / column unused
+    _gc('sqz0-3x3s2p0-9x12', 3, 2, 0, (9, 12), 2, 16, 64, **_FIRST),                     # the last column unused
+    # M = 105: two pixel blocks, images straddling a block, three channel blocks
+    _gc('alex1-5x5p2-64to192', 5, 1, 2, (7, 5), 3, 64, 192, **_BR),
+    _gc('3x3p1-48to128', 3, 1, 1, (5, 7), 2, 48, 128, **_BR),                            # three K chunks
+    _gc('3x3p1-192to64', 3, 1, 1, (4, 5), 2, 192, 64, **_BR),
+    # squeeze convs: 64 padded outputs, n_store of them stored at pitch n_store / n_store + 4
+    _gc('squeeze-1x1-ns16-tight', 1, 1, 0, (5, 7), 2, 64, 64, O=16, tight=True, **_BR),
+    _gc('squeeze-1x1-ns16', 1, 1, 0, (5, 7), 2, 64, 64, O=16, **_BR),
+    _gc('squeeze-1x1-ns48-tight', 1, 1, 0, (5, 7), 2, 64, 64, O=48, tight=True, **_BR),
+    _gc('squeeze-1x1-ns48', 1, 1, 0, (5, 7), 2, 64, 64, O=48, **_BR),
+    # block edges
+    _gc('M1', 3, 1, 0, (3, 3), 1, 16, 64, bias=True),
+    _gc('M64', 3, 1, 1, (8, 8), 1, 16, 64, res=True),
+    _gc('M128', 3, 1, 1, (8, 8), 2, 16, 64, mask=True),
+    _gc('M63-B3', 3, 1, 1, (3, 7), 3, 16, 64, **_BR),
+    _gc('M65', 3, 1, 1, (5, 13), 1, 16, 64, res=True, mask=True, relu=True),
+    # descriptors ops.gconv cannot express
+    _gc('1x3p1-5x6', (1, 3), 1, 1, (5, 6), 2, 16, 64, pro=True, bias=True),             # rows 0 and Ho - 1: padding alone
+    _gc('5x2s2p1-7x4', (5, 2), 2, 1, (7, 4), 2, 16, 64, pro=True, res=True),
+    _gc('2x2s3p0-8x7', 2, 3, 0, (8, 7), 2, 32, 64, bias=True, mask=True),
+    _gc('1x1p1-4x5', 1, 1, 1, (4, 5), 2, 16, 64, pro=True, bias=True),                   # the border: padding alone
+    # input gradients: flipped and transposed packing, pad K - 1 - P, no bias, no ReLU
+    _gc('dgrad-e3-64to16-xoff-res-mask', 3, 1, 1, (5, 7), 2, 64, 64, O=16, dgrad=True, x_off=True, res=True, mask=True,
+        tight=True, aux_tight=True),
+    _gc('dgrad-e3-64to32-xoff-res', 3, 1, 1, (5, 7), 2, 64, 64, O=32, dgrad=True, x_off=True, res=True, aux_tight=True),
+    _gc('dgrad-e1-64to48-xoff-mask', 1, 1, 0, (5, 7), 2, 64, 64, O=48, dgrad=True, x_off=True, mask=True,
+        aux_tight=True),
+    _gc('dgrad-3x3-48to32', 3, 1, 1, (4, 9), 2, 48, 64, O=32, dgrad=True),
+    _gc('dgrad-alex1-5x5-192to64', 5, 1, 2, (5, 4), 2, 192, 64, dgrad=True, res=True, mask=True),
+]
+# the expand pair of a fire: both write one tensor of pitch 128, at columns 0 and 64
+GCONV_PAIR = (_gc('expand-1x1-16to64-of128', 1, 1, 0, (5, 7), 2, 16, 64, y_ld=128, col=0, **_BR),
+              _gc('expand-3x3p1-16to64-of128', 3, 1, 1, (5, 7), 2, 16, 64, y_ld=128, col=64, **_BR))
+
+
+def gconv_geometries():
+    """the distinct (KH, KW, stride, pad) of the cases"""
+    out = []
+    for c in GCONV_CASES + list(GCONV_PAIR):
+        g = (c['KH'], c['KW'], c['stride'], c['pad'])
+        if g not in out:
+            out.append(g)
+    return out
+
+
+def gconv_inputs(g, c):
+    """the operands of a case on the host, dense fp32: every image at a magnitude of its own (x, the residual); x, pro_s
+    and pro_t zero in the channels >= I of a first conv; the mask relu(randn) -- about half of it exact zeros -- with
+    a few -0.0 and negative entries; dgrad: wf is the forward conv's weight [I, O, KH, KW], w the launch's equivalent
+    [O, I, KH, KW] (transposed, taps reversed)"""
+    B, Hi, Wi, Cin, Cout, I, O, ns = c['B'], c['Hi'], c['Wi'], c['Cin'], c['Cout'], c['I'], c['O'], c['n_store']
+    KH, KW = c['KH'], c['KW']
+    Ho, Wo = gconv_out(c)
+    rn = lambda *sh: torch.randn(*sh, generator=g)
+    mg = mags(B).view(B, 1, 1, 1)
+    i = dict(x=rn(B, Hi, Wi, Cin) * mg)
+    i['x'][..., I:] = 0.0
+    if c['dgrad']:
+        i['wf'] = rn(I, O, KH, KW) / math.sqrt(I * KH * KW)
+        i['w'] = i['wf'].permute(1, 0, 2, 3).flip(2, 3).contiguous()
+    else:
+        i['w'] = rn(O, I, KH, KW) / math.sqrt(I * KH * KW)
+    if c['pro']:
+        i['pro_s'], i['pro_t'] = 0.5 + torch.rand(Cin, generator=g), 0.3 * rn(Cin)
+        i['pro_s'][I:] = 0.0
+        i['pro_t'][I:] = 0.0
+    if c['bias']:
+        i['bias'] = 0.1 * rn(Cout)
+    if c['res']:
+        i['res'] = rn(B, Ho, Wo, ns) * mg
+    if c['mask']:
+        m = torch.relu(rn(B, Ho, Wo, ns))
+        flat = m.view(-1)
+        flat[1::97] = -0.0
+        flat[5::89] = -1.5
+        i['mask'] = m
+    return i
+
+
+def _gconv_kwargs(c, i, dtype):
+    cv = lambda name: i[name].to(dtype) if name in i else None
+    return dict(stride=c['stride'], pad=c['pad'], pro_s=cv('pro_s'), pro_t=cv('pro_t'),
+                bias=None if cv('bias') is None else cv('bias')[:c['n_store']], res=cv('res'), mask=cv('mask'),
+                relu=c['relu'])
+
+
+def gconv_weight(c, i, dtype=torch.float32):
+    """the launch's weight on its stored outputs and all Cin channels, [n_store, Cin, KH, KW]"""
+    w = torch.zeros(c['n_store'], c['Cin'], c['KH'], c['KW'], dtype=dtype)
+    w[:c['O'], :c['I']] = i['w'].to(dtype)[:c['n_store']]
+    return w
+
+
+def gconv_refs(c, i):
+    """-> the float64 reference (gconv's dict; dgrad: the conv's sum is the vjp of the forward conv) and the fp32
+    restatement: the same formula with the sum in gconv_mfma_kernel's order, one fp32 product and one fp32 addition
+    per column"""
+    x64, w64 = i['x'].double(), gconv_weight(c, i, torch.float64)
+    acc = None
+    if c['dgrad']:
+        Ho, Wo = gconv_out(c)
+        wf = torch.zeros(c['Cin'], c['n_store'], c['KH'], c['KW'], dtype=torch.float64)
+        wf[:c['I'], :c['O']] = i['wf'].double()
+        fwd = lambda X: F.conv2d(X, wf, padding=c['KH'] - 1 - c['pad'])
+        X0 = torch.zeros(c['B'], c['n_store'], Ho, Wo, dtype=torch.float64)
+        acc = vjp(fwd, [X0], x64.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+    r64 = gconv(x64, w64, acc=acc, **_gconv_kwargs(c, i, torch.float64))
+    x32, w32 = i['x'], gconv_weight(c, i)
+    a = fma(x32, i['pro_s'], i['pro_t']) if c['pro'] else x32
+    acc32 = acc_fp32(gconv_cols(a, c), gconv_wmat(w32), 1, 16)
+    r32 = gconv(x32, w32, acc=acc32, **_gconv_kwargs(c, i, torch.float32))
+    return r64, r32
+
+
+def gconv_k(c):
+    """the bar's k of a case, counted from gconv_mfma_kernel's arithmetic like direct_k's route F: one chain per
+    output over the KH KW Cin columns (tap-major, 16-channel chunks, a 32x32x2 MFMA per channel pair j, 8 + j), a
+    product and an addition each; the prologue's product and sum (2), the bias (1), the residual (1).  ReLU and mask
+    select"""
+    return 2 * c['KH'] * c['KW'] * c['Cin'] + 2 * c['pro'] + c['bias'] + c['res']
+
+
+def gconv_spots(c):
+    """(image, y, x) of one-hot input pixels: the four corners, an edge pixel of every side, and an interior pixel of
+    every residue of (y, x) modulo the stride, on the last image"""
+    B, Hi, Wi, s = c['B'], c['Hi'], c['Wi'], c['stride']
+    b = B - 1
+    sp = [(0, 0, 0), (b, 0, Wi - 1), (b, Hi - 1, 0), (0, Hi - 1, Wi - 1), (b, 0, Wi // 2), (b, Hi // 2, 0),
+          (0, Hi - 1, Wi // 2), (b, Hi // 2, Wi - 1)]
+    y0, x0 = max(1, Hi // 2 - s // 2), max(1, Wi // 2 - s // 2)
+    sp += [(b, min(y0 + ry, Hi - 2), min(x0 + rx, Wi - 2)) for ry in range(s) for rx in range(s)]
+    out = []
+    for q in sp:
+        if q not in out:
+            out.append(q)
+    return out
+
+
+def gconv_onehot(c, spot, n=0):
+    """exact inputs: x zero but for one power of two at `spot` in channel (5 n) % Cin; w[o, ci, tap] = (1 + (ci % 16) /
+    16 + o / 1024) 2^(tap - taps // 2 + ci // 16): a value of its own for every (tap, channel, output), with an
+    eleven-bit mantissa.  Every output is ONE product, exact in fp32, and names the tap and the channel that reached
+    it"""
+    B, Hi, Wi, Cin, Cout = c['B'], c['Hi'], c['Wi'], c['Cin'], c['Cout']
+    T = c['KH'] * c['KW']
+    assert Cin == 16 and Cout <= 64, 'with a second chunk (tap, chunk 1) would share its value with (tap + 1, chunk 0)'
+    x = torch.zeros(B, Hi, Wi, Cin)
+    x[spot[0], spot[1], spot[2], (5 * n) % Cin] = 2.0 ** (n % 5 - 2) * (-1.0) ** n
+    ci, o, tap = torch.arange(Cin).view(1, Cin, 1), torch.arange(Cout).view(Cout, 1, 1), torch.arange(T).view(1, 1, T)
+    w = (1.0 + (ci % 16) / 16.0 + o / 1024.0) * 2.0 ** (tap - T // 2 + ci // 16).double()
+    return dict(x=x, w=w.float().view(Cout, Cin, c['KH'], c['KW']))
+
+
 # ---- optimiser ----------------------------------------------------------------------------------------------------
 def adam_reference(p0, grads, lr, first_step=1, m0=None, v0=None):
     """torch.optim.Adam (defaults) stepped on the CPU in fp32 from step number `first_step`; returns the parameter

@@ -1263,3 +1263,118 @@ def test_subpix_case_tables():
     assert float((sl[3].abs() / big[3]).median()) < 2.0 ** -16          # phase (0, 0), tap (1, 1): {1, 2} x {1, 2}
     off = (R.subpix_slabs(w, 0, False)[3].double() - sl[3]).abs()          # ... and fp32 cannot follow the chain
     assert float((off / sl[3].abs()).median()) > 2.0 ** -10 and float((off / big[3]).max()) <= 3 * R.U
+
+
+# ---- generic gather conv: the references, restatements and cases of tests/test_gconv_kernels_gpu.py -----------------
+GCONV_ALL = R.GCONV_CASES + list(R.GCONV_PAIR)
+
+
+def test_gconv_reference_geometry_and_im2col_order():
+    """R.gconv against a conv written out tap by tap on the padded tensor (stride, padding, floor division, KH != KW);
+    column (tap, chunk, j, h) of gconv_cols holds channel 16 chunk + 8 h + j of pixel (oy s - p + ky, ox s - p + kx);
+    cols x wmat is the conv; a dgrad case's vjp is the launch's conv with the transposed, tap-reversed weight"""
+    for n, c in enumerate(GCONV_ALL):
+        i = R.gconv_inputs(_g(400 + n), c)
+        x, w = i['x'].double(), R.gconv_weight(c, i, D)
+        s, p, KH, KW = c['stride'], c['pad'], c['KH'], c['KW']
+        Ho, Wo = R.gconv_out(c)
+        assert (Ho - 1) * s + KH <= c['Hi'] + 2 * p < Ho * s + KH and (Wo - 1) * s + KW <= c['Wi'] + 2 * p < Wo * s + KW
+        xp = torch.zeros(c['B'], c['Hi'] + 2 * p, c['Wi'] + 2 * p, c['Cin'], dtype=D)
+        a = x * i['pro_s'].double() + i['pro_t'].double() if c['pro'] else x
+        xp[:, p:p + c['Hi'], p:p + c['Wi']] = a
+        want = torch.zeros(c['B'], Ho, Wo, c['n_store'], dtype=D)
+        for ky in range(KH):
+            for kx in range(KW):
+                win = xp[:, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]
+                want += win @ w[:, :, ky, kx].t()
+        plain = R.gconv(x, w, s, p, i.get('pro_s'), i.get('pro_t'))
+        assert float((plain['y'] - want).abs().max()) <= 1e-12 * float(plain['den'].max())
+        cols, wm = R.gconv_cols(a, c), R.gconv_wmat(w)
+        assert float((cols @ wm.t() - want).abs().max()) <= 1e-12 * float(plain['den'].max())
+        tap, ch, j, h = KH * KW - 1, c['Cin'] // 16 - 1, 3, 1
+        col = ((tap * (c['Cin'] // 16) + ch) * 8 + j) * 2 + h
+        assert torch.equal(cols[..., col], xp[:, KH - 1:KH + (Ho - 1) * s:s, KW - 1:KW + (Wo - 1) * s:s, 16 * ch + 8 * h + j])
+        assert torch.equal(wm[:, col], w[:, 16 * ch + 8 * h + j, KH - 1, KW - 1])
+        r64, _ = R.gconv_refs(c, i)
+        full = R.gconv(x, w, **R._gconv_kwargs(c, i, D))
+        if c['dgrad']:
+            assert float((r64['y'] - full['y']).abs().max()) <= 1e-12 * float(full['den'].max())
+        else:
+            assert torch.equal(r64['y'], full['y'])
+        if c['mask']:
+            dead = ~(i['mask'] > 0)
+            assert bool(dead.any()) and bool((r64['y'][dead] == 0).all())
+            assert bool((i['mask'] < 0).any()) and bool(torch.signbit(i['mask'][i['mask'] == 0]).any())
+
+
+@pytest.mark.parametrize('case', GCONV_ALL, ids=R.gconv_id)
+def test_gconv_restatements_stay_under_a_quarter_of_k(case):
+    """for every case's generator and shape the fp32 restatement is within k / 4 of the fp64 reference on the issue's
+    denominator: the bar min(k, 4 x restatement) is attainable and k was not set from the kernel.  Zero padding
+    applied in FRONT of the prologue is far outside the bar at the border of every case with a prologue and
+    padding"""
+    def body(gen):
+        i = R.gconv_inputs(gen('gconv', R.gconv_id(case)), case)
+        r64, r32 = R.gconv_refs(case, i)
+        f = _fig(r32['y'], r64['y'], r64['den'])
+        assert f <= R.gconv_k(case) / 4.0, (f, R.gconv_k(case))
+        if case['pro'] and case['pad'] and not case['relu']:
+            x = i['x'].double()
+            p = case['pad']
+            xs = F.pad(x * i['pro_s'].double(), (0, 0, p, p, p, p)) + i['pro_t'].double()     # the halo holds pro_t
+            w = R.gconv_weight(case, i, D)
+            acc = F.conv2d(xs.permute(0, 3, 1, 2), w, stride=case['stride']).permute(0, 2, 3, 1)
+            wrong = R.gconv(x, w, acc=acc, **R._gconv_kwargs(case, i, D))
+            err = (wrong['y'] - r64['y']).abs() / r64['den'] / R.U
+            assert float(err[:, 0].median()) > 100 * min(R.gconv_k(case), 4.0 * f)
+    _draws(body)
+
+
+def test_gconv_one_hot_inputs_are_exact_in_the_restatement():
+    for KH, KW, s, p in R.gconv_geometries():
+        c = R._gc('onehot', (KH, KW), s, p, (max(KH, 7) + 2 * s, max(KW, 6) + 2 * s + 1), 2, 16, 64)
+        for n, spot in enumerate(R.gconv_spots(c)):
+            i = R.gconv_onehot(c, spot, n)
+            r64, r32 = R.gconv_refs(c, i)
+            assert torch.equal(r32['y'].double(), r64['y']), (KH, KW, s, p, spot)
+            # one product per output: the quotient by x is the weight of the one tap and channel that reached it
+            xv = float(i['x'][spot][(5 * n) % 16])
+            nz = r64['y'] != 0
+            vals = set((r64['y'][nz] / xv).tolist())
+            assert vals <= set(i['w'][:, (5 * n) % 16].double().reshape(-1).tolist()), (KH, KW, s, p, spot)
+    assert len(R.gconv_geometries()) >= 10
+
+
+@pytest.mark.parametrize('taps_hw', [(1, 1), (2, 3), (3, 3), (5, 5), (11, 11)])
+@pytest.mark.parametrize('flip', [False, True])
+def test_gconv_pack_is_the_written_out_layout(taps_hw, flip):
+    KH, KW = taps_hw
+    O, I, N_pad, K_pad = (16, 3, 64, 16) if not flip else (35, 16, 64, 48)
+    w = torch.randn(O, I, KH, KW, generator=_g(430))
+    got = R.gconv_pack(w, N_pad, K_pad, flip).view(KH * KW, K_pad // 16, N_pad, 16)
+    N, K = (I, O) if flip else (O, I)
+    want = torch.zeros_like(got)
+    for tap in range(KH * KW):
+        for k in range(K):
+            for n in range(N):
+                v = w[k, n].reshape(-1)[KH * KW - 1 - tap] if flip else w[n, k].reshape(-1)[tap]
+                want[tap, k // 16, n, k % 16] = v
+    assert torch.equal(got, want)
+
+
+def test_gconv_case_table():
+    """the mechanisms the issue names, each in at least one case"""
+    cs = R.GCONV_CASES
+    M = lambda c: c['B'] * R.gconv_out(c)[0] * R.gconv_out(c)[1]
+    assert set([1, 63, 64, 65, 128, 40, 105]) <= set(M(c) for c in cs)
+    assert any(c['Cin'] == 48 and not c['dgrad'] for c in cs) and any(c['Cin'] == 48 and c['dgrad'] for c in cs)
+    assert set(c['n_store'] for c in cs if c['tight']) >= set([16, 48])
+    assert set(c['n_store'] for c in cs if c['dgrad'] and c['aux_tight']) == set([16, 32, 48])
+    d = [c for c in cs if c['dgrad']]
+    assert set((c['res'], c['mask']) for c in d) == set([(True, True), (True, False), (False, True), (False, False)])
+    assert any(c['x_off'] for c in d) and any(c['KH'] == 5 and c['Cin'] == 192 for c in d)
+    assert any(c['KH'] != c['KW'] for c in cs) and any(c['stride'] > c['KH'] for c in cs)
+    assert any(c['pad'] >= c['KH'] and c['pro'] for c in cs)
+    assert all(max(c['Hi'], c['Wi']) <= 24 for c in cs + list(R.GCONV_PAIR))
+    assert len(set(R.gconv_id(c) for c in GCONV_ALL)) == len(GCONV_ALL)
+    assert [c['col'] for c in R.GCONV_PAIR] == [0, 64] and all(c['y_ld'] == 128 for c in R.GCONV_PAIR)
