@@ -1229,6 +1229,53 @@ int p2l_feature_anchor_fwd(const float* f, const float* anchor, int64_t anchor_b
 int p2l_feature_anchor_bwd(const float* f, const float* anchor, int64_t anchor_bstride, const float* gloss, int Bn,
                            int64_t n, double weight, float* df, void* stream);
 
+/* StyleSpace (S) search: the synthesis behind the affine layers (csrc/p2l_plan_sg2.hip, csrc/p2l_sg2_style.hip,
+ * DESIGN.md section 16).  A candidate's styles are one flat fp32 vector [S_total] in network order: conv[0], rgb[0],
+ * then per resolution the up conv, the plain conv and their ToRGB (rgb[j] follows conv[rgb[j].after_conv]); every
+ * entry is that layer's cin modulation scalars.  p2l_sg2_style_layout is host-only: conv_off [n_conv] and rgb_off
+ * [n_rgb] receive the float offsets of the layers (either may be NULL), *total S_total (may be NULL);
+ * P2L_EINVAL for a NULL m, layer counts outside the descriptor's limits, a cin < 1 or an rgb that follows no conv.
+ * p2l_sg2_styles writes styles [Bn][S_total] of latent [Bn][n_latent][512]: every layer's affine of its W+ row, by the
+ * grouped launch of p2l_sg2_synthesis_fwd (one launch, no synthesis, no workspace): the bits are the ones the full run
+ * leaves in its style slots.
+ * p2l_sg2_synthesis_s_fwd is p2l_sg2_synthesis_fwd with the affine launch replaced by ONE scatter launch from styles
+ * into the style slots of the workspace; _s_bwd is p2l_sg2_synthesis_bwd up to and including the demodulation backward,
+ * then ONE gather launch of the style gradients into dstyles [Bn][S_total] (every element is written) instead of the
+ * two transposed affines: no dlatent exists.  noise / dnoise: layer-major as in the full run, dnoise may be NULL.  The
+ * workspace is the one of the full run (p2l_sg2_ws_bytes; p2l_sg2_ws_lookup describes it).  Scatter and gather use no
+ * atomics.  Before anything is launched: P2L_EINVAL for a NULL m, a NULL required pointer, Bn < 1 (the scatter and
+ * the gather: Bn <= 65535) and a descriptor p2l_sg2_style_layout refuses; P2L_EWS for a NULL or short workspace. */
+int p2l_sg2_style_layout(const P2LStyleGAN2* m, int32_t* conv_off, int32_t* rgb_off, int32_t* total);
+int p2l_sg2_styles(const P2LStyleGAN2* m, const float* latent, int Bn, float* styles, void* stream);
+int p2l_sg2_synthesis_s_fwd(const P2LStyleGAN2* m, const float* styles, const float* noise, int Bn, void* ws,
+                            size_t ws_bytes, float* img16, void* stream);
+int p2l_sg2_synthesis_s_bwd(const P2LStyleGAN2* m, const float* styles, const float* noise, int Bn, void* ws,
+                            size_t ws_bytes, const float* dimg16, float* dstyles, float* dnoise, void* stream);
+/* Per-column moments of x [rows][ld] fp32 (cols <= ld): sum[c] = sum_r x[r,c] and sumsq[c] = sum_r x[r,c]^2, fp64 [cols]
+ * on the device (csrc/p2l_sg2_style.hip).  x -> fp64 and x^2 are exact; one thread owns a column and adds its rows in
+ * row order (two fma-free chains), so the order follows from (rows, cols) alone.  accumulate = 1 continues from what
+ * sum / sumsq hold (the chain goes on as if the rows had been one call: a sample set streamed in chunks gives a
+ * result that depends on nothing but the rows), 0 starts from zero.  One launch, no atomics, no workspace.
+ * P2L_EINVAL (NULL x / sum / sumsq, rows or cols < 1, ld < cols, rows * ld >= 2^62) before the launch. */
+int p2l_col_moments_f64(const float* x, int64_t rows, int cols, int64_t ld, double* sum, double* sumsq,
+                        int accumulate, void* stream);
+/* StylePrior: a diagonal Gaussian prior on a flat variable (csrc/p2l_sg2_style.hip).
+ * x [Bn][n] fp32, center [n] and inv_scale [n] fp64, on the device:
+ *   loss[b] = weight (1 / n) sum_i ((x[b,i] - center[i]) inv_scale[i])^2
+ * fp64 throughout, 4096-element chunks in a fixed order as p2l_feature_anchor_*, weight * (sum / n) rounded once to
+ * fp32.  _bwd: dx[b,i] = gloss[b] (NULL = 1) * ((2 weight / n) * ((x - center) inv_scale) inv_scale), fp64, rounded
+ * once; gloss is applied last, so gloss = 2 or -1 scale the result bit for bit.  A candidate's loss and dx do not
+ * depend on Bn, on its row, on the stream or on the call.  Launches: forward 2, backward 1; no atomics, no memset.
+ * The forward's workspace holds Bn * ceil(n / 4096) fp64 partial sums; the backward needs none.
+ * P2L_EINVAL (NULL x / center / inv_scale / loss / dx, Bn < 1 or > 65535, n < 1 or >= 2^31) and P2L_EWS (NULL, not
+ * 8-byte aligned or short workspace) are returned before any launch; p2l_diag_prior_ws_bytes is host-only and 0 for
+ * sizes the launches refuse. */
+size_t p2l_diag_prior_ws_bytes(int Bn, int64_t n);
+int p2l_diag_prior_fwd(const float* x, const double* center, const double* inv_scale, int Bn, int64_t n, double weight,
+                       float* loss, void* ws, size_t ws_bytes, void* stream);
+int p2l_diag_prior_bwd(const float* x, const double* center, const double* inv_scale, const float* gloss, int Bn,
+                       int64_t n, double weight, float* dx, void* stream);
+
 
 #ifdef __cplusplus
 }

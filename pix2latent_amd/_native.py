@@ -318,6 +318,8 @@ EXPORTS = [
     'p2l_l2_loss_nblk', 'p2l_l2_loss_fwd', 'p2l_l2_loss_bwd', 'p2l_adam_step_sched',
     'p2l_sg2_synthesis_from_fwd', 'p2l_sg2_synthesis_from_bwd', 'p2l_sg2_capture', 'p2l_nhwc_to_nchw', 'p2l_nchw_to_nhwc',
     'p2l_feature_anchor_ws_bytes', 'p2l_feature_anchor_fwd', 'p2l_feature_anchor_bwd',
+    'p2l_sg2_style_layout', 'p2l_sg2_styles', 'p2l_sg2_synthesis_s_fwd', 'p2l_sg2_synthesis_s_bwd',
+    'p2l_col_moments_f64', 'p2l_diag_prior_ws_bytes', 'p2l_diag_prior_fwd', 'p2l_diag_prior_bwd',
 ]
 
 _lib = None
@@ -414,7 +416,15 @@ def lib():
                 ('p2l_nchw_to_nhwc', [vp, vp, i32, i32, i32, i32, vp]),
                 ('p2l_feature_anchor_ws_bytes', [i32, i64_]),
                 ('p2l_feature_anchor_fwd', [vp, vp, i64_, i32, i64_, C.c_double, vp, vp, C.c_size_t, vp]),
-                ('p2l_feature_anchor_bwd', [vp, vp, i64_, vp, i32, i64_, C.c_double, vp, vp])):
+                ('p2l_feature_anchor_bwd', [vp, vp, i64_, vp, i32, i64_, C.c_double, vp, vp]),
+                ('p2l_sg2_style_layout', [vp, vp, vp, vp]),
+                ('p2l_sg2_styles', [vp, vp, i32, vp, vp]),
+                ('p2l_sg2_synthesis_s_fwd', [vp, vp, vp, i32, vp, C.c_size_t, vp, vp]),
+                ('p2l_sg2_synthesis_s_bwd', [vp, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp]),
+                ('p2l_col_moments_f64', [vp, i64_, i32, i64_, vp, vp, i32, vp]),
+                ('p2l_diag_prior_ws_bytes', [i32, i64_]),
+                ('p2l_diag_prior_fwd', [vp, vp, vp, i32, i64_, C.c_double, vp, vp, C.c_size_t, vp]),
+                ('p2l_diag_prior_bwd', [vp, vp, vp, vp, i32, i64_, C.c_double, vp, vp])):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = types
                 if name.endswith('_ws_bytes'):

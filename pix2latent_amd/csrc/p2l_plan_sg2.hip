@@ -248,10 +248,31 @@ int sg_cut(const P2LStyleGAN2* m, int res, SgCut& c) {
   return P2L_OK;
 }
 
+// the style slots s[l] / rs[j] (grads = 0) or their gradients ds[l] / rds[j] (grads = 1) of the whole network, each at
+// its place in the flat StyleSpace vector (p2l_sg2_style_layout)
+int sg_style_items(const P2LStyleGAN2* m, const SgLayout& L, float* W, int B, int grads, float* flat,
+                   p2lsg2::StyleMoveK& k) {
+  int32_t co[P2L_SG2_MAX_CONVS], ro[P2L_SG2_MAX_RGBS], total = 0;
+  RET_IF(p2l_sg2_style_layout(m, co, ro, &total));
+  if (m->n_conv + m->n_rgb > p2lsg2::STYLE_MAX) return P2L_EINVAL;
+  k.n = 0; k.Bn = B; k.total = total; k.flat = flat;
+  for (int l = 0; l < m->n_conv; ++l) {
+    p2lsg2::StyleMoveItem& a = k.g[k.n++];
+    a.slot = W + (grads ? L.ds[l] : L.s[l]); a.off = co[l]; a.cin = m->conv[l].cin;
+  }
+  for (int j = 0; j < m->n_rgb; ++j) {
+    p2lsg2::StyleMoveItem& a = k.g[k.n++];
+    a.slot = W + (grads ? L.rds[j] : L.rs[j]); a.off = ro[j]; a.cin = m->rgb[j].cin;
+  }
+  return P2L_OK;
+}
+
 // styles, demodulation and the layer loop from conv[l0] / rgb[j0 + 1] to the clamp.  The input of conv[l0] is the
 // constant (l0 = 0) or what the caller left in the slot of y[l0 - 1]; rgb[j0 + 1] adds the up-sampled skip[j0].
+// styles != NULL (StyleSpace search, full run only): the style slots are scattered from the flat vector instead of
+// computed from latent, which is not read.
 int sg_forward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* latent, const float* noise, int B,
-               SgCut cut, float* img16, void* st) {
+               SgCut cut, float* img16, void* st, const float* styles = nullptr) {
   const int l0 = cut.l0, j0 = cut.j0;
   const int D = m->style_dim, lat_ld = m->n_latent * D;
   if (hipMemsetAsync(W + L.zeros, 0, (L.ubuf - L.zeros) * sizeof(float), (hipStream_t)st) != hipSuccess)
@@ -278,7 +299,13 @@ int sg_forward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* 
       a.W = r.mod_w; a.bias = r.mod_b; a.x = latent + (size_t)r.latent_idx * D; a.x_ld = lat_ld;
       a.y = W + L.rs[j]; a.y_ld = r.cin; a.K = D; a.N = r.cin;
     }
-    RET_IF(p2lsg2::grouped_linear_fwd(gs, st));
+    if (styles) {                          // (gs is filled and dropped: its addresses are never read)
+      p2lsg2::StyleMoveK sk;
+      RET_IF(sg_style_items(m, L, W, B, 0, const_cast<float*>(styles), sk));
+      RET_IF(p2lsg2::style_move(sk, 1, st));
+    } else {
+      RET_IF(p2lsg2::grouped_linear_fwd(gs, st));
+    }
     RET_IF(p2lsg2::grouped_linear_fwd(gd, st));
   }
   // Maxima of every conv's MODULATED input (y[l-1] * s[l]), left by the kernel that wrote y[l-1]: the fp16 x 2
@@ -354,12 +381,14 @@ int sg_forward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* 
 // The backward of sg_forward: from the clamp down to conv[l0].  dlatent is zero-filled as a whole and receives the
 // rows of the layers that ran.  *gx_out: the gradient with respect to the input of conv[l0], NHWC, and *gskip_out:
 // the gradient with respect to skip[j0], NHWC16 (j0 >= 0), both inside the workspace.
+// dstyles != NULL (StyleSpace search, full run only): the pass ends behind the demodulation backward with one gather
+// of ds[l] / rds[j] into the flat vector; dlatent is not touched.
 int sg_backward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float* noise, int B, SgCut cut,
                 const float* dimg16, float* dlatent, float* dnoise, const float** gx_out, const float** gskip_out,
-                void* st) {
+                void* st, float* dstyles = nullptr) {
   const int l0 = cut.l0, j0 = cut.j0;
   const int D = m->style_dim, lat_ld = m->n_latent * D;
-  if (hipMemsetAsync(dlatent, 0, (size_t)B * lat_ld * sizeof(float), (hipStream_t)st) != hipSuccess)
+  if (!dstyles && hipMemsetAsync(dlatent, 0, (size_t)B * lat_ld * sizeof(float), (hipStream_t)st) != hipSuccess)
     return P2L_ELAUNCH;
   const bool hand = !(m->wfmt & P2L_WFMT_FLAG_NO_AMAX);
   if (hand && hipMemsetAsync(W + L.amax_b, 0, (size_t)2 * m->n_conv * B * P2L_SG2_AMAX_SLOTS * sizeof(float),
@@ -441,11 +470,12 @@ int sg_backward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float*
     p2lsg2::GLinBwdItem& a = gm.g[gm.n++];
     a.W = c.wsq; a.dy = W + L.dd[l]; a.d = W + L.d[l]; a.x = W + L.s[l]; a.dx = W + L.ds[l];
     a.K = c.cin; a.N = c.cout; a.dx_ld = c.cin; a.accumulate = 1;
+    if (dstyles) continue;
     p2lsg2::GLinBwdItem& e = gc.g[gc.n++];
     e.W = c.mod_w; e.dy = W + L.ds[l]; e.dx = dlatent + (size_t)c.latent_idx * D;
     e.K = D; e.N = c.cin; e.dx_ld = lat_ld; e.accumulate = 1;
   }
-  for (int j = j0 + 1; j < m->n_rgb; ++j) {
+  for (int j = j0 + 1; j < m->n_rgb && !dstyles; ++j) {
     const P2LSg2Rgb& r = m->rgb[j];
     p2lsg2::GLinBwdItem& e = gr.g[gr.n++];
     e.W = r.mod_w; e.dy = W + L.rds[j]; e.dx = dlatent + (size_t)r.latent_idx * D;
@@ -454,8 +484,14 @@ int sg_backward(const P2LStyleGAN2* m, const SgLayout& L, float* W, const float*
   RET_IF(p2l_arb_defer_flush(st));
   RET_IF(p2l_sg2_rows_defer_flush(st));
   RET_IF(p2lsg2::grouped_linear_bwd(gm, st));
-  RET_IF(p2lsg2::grouped_linear_bwd(gc, st));
-  RET_IF(p2lsg2::grouped_linear_bwd(gr, st));
+  if (dstyles) {
+    p2lsg2::StyleMoveK sk;
+    RET_IF(sg_style_items(m, L, W, B, 1, dstyles, sk));
+    RET_IF(p2lsg2::style_move(sk, 0, st));
+  } else {
+    RET_IF(p2lsg2::grouped_linear_bwd(gc, st));
+    RET_IF(p2lsg2::grouped_linear_bwd(gr, st));
+  }
   if (gx_out) *gx_out = gx;
   if (gskip_out) *gskip_out = gs_cur;
   return P2L_OK;
@@ -525,4 +561,50 @@ extern "C" int p2l_sg2_capture(const P2LStyleGAN2* m, int res, int B, const void
   const float* W = (const float*)ws;
   RET_IF(p2l_nhwc_to_nchw(W + L.y[cut.l0 - 1], feat_nchw, B, m->conv[cut.l0].cin, res, res, st));
   return p2l_nhwc16_to_nchw3(W + L.skip[cut.j0], skip_nchw3, B, res, res, st);
+}
+
+// StyleSpace (S) search: the affines alone, and the full run behind them
+extern "C" int p2l_sg2_styles(const P2LStyleGAN2* m, const float* latent, int B, float* styles, void* st) {
+  int32_t co[P2L_SG2_MAX_CONVS], ro[P2L_SG2_MAX_RGBS], total = 0;
+  if (B < 1 || B > 65535 * 16 || !latent || !styles || p2l_sg2_style_layout(m, co, ro, &total)) return P2L_EINVAL;
+  if (m->n_conv + m->n_rgb > p2lsg2::GL_MAX) return P2L_EINVAL;
+  const int D = m->style_dim, lat_ld = m->n_latent * D;
+  // the items of sg_forward's first grouped launch, each writing its place in the flat vector instead of its slot
+  p2lsg2::GLinFwdK gs{};
+  gs.Bn = B; gs.mode = 0;
+  for (int l = 0; l < m->n_conv; ++l) {
+    const P2LSg2Conv& c = m->conv[l];
+    p2lsg2::GLinItem& a = gs.g[gs.n++];
+    a.W = c.mod_w; a.bias = c.mod_b; a.x = latent + (size_t)c.latent_idx * D; a.x_ld = lat_ld;
+    a.y = styles + co[l]; a.y_ld = total; a.K = D; a.N = c.cin;
+  }
+  for (int j = 0; j < m->n_rgb; ++j) {
+    const P2LSg2Rgb& r = m->rgb[j];
+    p2lsg2::GLinItem& a = gs.g[gs.n++];
+    a.W = r.mod_w; a.bias = r.mod_b; a.x = latent + (size_t)r.latent_idx * D; a.x_ld = lat_ld;
+    a.y = styles + ro[j]; a.y_ld = total; a.K = D; a.N = r.cin;
+  }
+  return p2lsg2::grouped_linear_fwd(gs, st);
+}
+
+extern "C" int p2l_sg2_synthesis_s_fwd(const P2LStyleGAN2* m, const float* styles, const float* noise, int B, void* ws,
+                                       size_t ws_bytes, float* img16, void* st) {
+  SgLayout L;
+  if (B < 1 || B > 65535 || !styles || !noise || !img16 || p2l_sg2_style_layout(m, nullptr, nullptr, nullptr) ||
+      m->n_conv + m->n_rgb > p2lsg2::STYLE_MAX)
+    return P2L_EINVAL;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float)) return P2L_EWS;
+  return sg_forward(m, L, (float*)ws, nullptr, noise, B, SgCut{0, -1}, img16, st, styles);
+}
+
+extern "C" int p2l_sg2_synthesis_s_bwd(const P2LStyleGAN2* m, const float* styles, const float* noise, int B, void* ws,
+                                       size_t ws_bytes, const float* dimg16, float* dstyles, float* dnoise, void* st) {
+  SgLayout L;
+  if (B < 1 || B > 65535 || !styles || !noise || !dimg16 || !dstyles ||
+      p2l_sg2_style_layout(m, nullptr, nullptr, nullptr) || m->n_conv + m->n_rgb > p2lsg2::STYLE_MAX)
+    return P2L_EINVAL;
+  RET_IF(sg_layout(m, B, L));
+  if (!ws || ws_bytes < L.total * sizeof(float)) return P2L_EWS;
+  return sg_backward(m, L, (float*)ws, noise, B, SgCut{0, -1}, dimg16, nullptr, dnoise, nullptr, nullptr, st, dstyles);
 }

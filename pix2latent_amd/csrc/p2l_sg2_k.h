@@ -40,4 +40,18 @@ struct GLinBwdK {
 };
 int grouped_linear_bwd(const GLinBwdK& k, void* stream);
 
+// StyleSpace search (p2l_sg2_style.hip): one launch moves every layer's [Bn][cin] slot of the workspace from
+// (to_ws = 1) or to (to_ws = 0) its place in the flat per-candidate vector, flat[b * total + off + c]
+constexpr int STYLE_MAX = 32;
+struct StyleMoveItem {
+  float* slot;         // [Bn][cin]
+  int off, cin;
+};
+struct StyleMoveK {
+  StyleMoveItem g[STYLE_MAX];
+  float* flat;         // [Bn][total]; read only when to_ws = 1
+  int n, Bn, total;
+};
+int style_move(const StyleMoveK& k, int to_ws, void* stream);
+
 }  // namespace p2lsg2

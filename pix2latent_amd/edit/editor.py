@@ -1,7 +1,8 @@
 """BigGANLatentEditor (reference pix2latent/edit/editor.py): loads the `vars.npy` an inversion saved and
 re-renders its best candidate with the class swapped or z moved along a GANSpace direction.
 StyleGAN2LatentEditor does the same for the StyleGAN2 results (z or w+ search): the latent moves along a
-principal direction of W, in all layers or in some."""
+principal direction of W, in all layers or in some, or a single StyleSpace channel moves by a multiple of its spread
+(`edit_s`; results of z, w+ and s search alike)."""
 import numpy as np
 import torch
 
@@ -76,8 +77,10 @@ class BigGANLatentEditor():
 
 
 class StyleGAN2LatentEditor():
-    def __init__(self, model):
+    def __init__(self, model, style_samples=100000):
+        """style_samples: how many mapped z the channel stds of edit_s are taken over (model.style_stats)"""
         self.model = model
+        self.style_samples = style_samples
 
     def _device(self):
         return self.model._dev
@@ -86,13 +89,21 @@ class StyleGAN2LatentEditor():
         """ load optimized result: the best candidate's latent as w+ [1, n_latent, 512] and its per-layer
         noises (list of [1, 1, h, w]).  z search: w = mapping(z) in every layer, and a noise list drawn once
         from a seeded CPU generator (the model draws fresh noise on every forward, which would change the
-        image between two renders of one edit).  w+ search: the stored latent and its stored noises. """
+        image between two renders of one edit).  w+ search: the stored latent and its stored noises.  s search: the
+        stored styles [1, S_total] and noises; there is no latent, so edit_w / render_w_sweep / default render from
+        the styles.  Every result also leaves its styles (`model.styles` of the latent for z and w+) for edit_s. """
         model, dev = self.model, self._device()
         self._var = load_result(var_path)
         self._idx = np.argmin(self._var.loss[-1][1]['loss'])
         z = self._var.input.z.data[self._idx].detach().float().to(dev)
         n_latent = model._desc.n_latent
         with torch.no_grad():
+            if model.search == 's':
+                self._latent = None
+                self._styles = z.reshape(1, model.n_styles).contiguous()
+                flat = self._var.input.noises.data[self._idx].detach().float().to(dev)
+                self._noises = [n.contiguous() for n in model.reshape_noise(flat.reshape(1, -1))]
+                return
             if model.search == 'z':
                 w = model.mapping(z.reshape(1, 512))
                 self._latent = w.unsqueeze(1).expand(-1, n_latent, -1).contiguous()
@@ -102,6 +113,7 @@ class StyleGAN2LatentEditor():
                 self._latent = z.reshape(1, n_latent, 512).contiguous()
                 flat = self._var.input.noises.data[self._idx].detach().float().to(dev)
                 self._noises = [n.contiguous() for n in model.reshape_noise(flat.reshape(1, -1))]
+            self._styles = model.styles(self._latent)
         return
 
     def _components(self):
@@ -119,6 +131,8 @@ class StyleGAN2LatentEditor():
 
     def _edited(self, component, sigma, idx):
         """the latent with sigma * stdev[k] * components[k] added to the rows `idx`"""
+        if self._latent is None:
+            raise ValueError('an s-search result has no W latent to move: use edit_s')
         U = self._components()
         latent = self._latent.clone()
         latent[:, idx] = latent[:, idx] + sigma * self.stdev[component] * U[component]
@@ -147,6 +161,53 @@ class StyleGAN2LatentEditor():
         w = torch.cat(ws)
         return torch.cat([self._render(w[i:i + SWEEP_CHUNK]) for i in range(0, w.shape[0], SWEEP_CHUNK)])
 
+    # ---- StyleSpace: one channel of one layer
+    def _style_std(self):
+        if not hasattr(self, 'style_std'):
+            self.style_mean, self.style_std = (t.float() for t in self.model.style_stats(num_samples=self.style_samples))
+        return self.style_std
+
+    def _style_index(self, layer, channel):
+        """position of (layer, channel) in the flat style vector; `layer` counts `model.style_layout` (network
+        order: the numbering of the StyleSpace paper)"""
+        layout = self.model.style_layout
+        if int(layer) != layer or not 0 <= layer < len(layout):
+            raise ValueError('layer must be in [0, %d), got %s' % (len(layout), layer))
+        e = layout[int(layer)]
+        if int(channel) != channel or not 0 <= channel < e.channels:
+            raise ValueError('channel of layer %d (%s) must be in [0, %d), got %s' % (layer, e.name, e.channels, channel))
+        return e.offset + int(channel)
+
+    def _edited_s(self, layer, channel, sigma):
+        i = self._style_index(layer, channel)
+        styles = self._styles.clone()
+        styles[:, i] = styles[:, i] + sigma * self._style_std()[i]
+        return styles
+
+    def _render_s(self, styles):
+        B = styles.shape[0]
+        flat = torch.cat([n.reshape(1, -1) for n in self._noises], dim=1).expand(B, -1).contiguous()
+        with torch.no_grad():
+            return self.model.forward_s(styles, flat)
+
+    def edit_s(self, layer, channel, sigma):
+        """ move style channel `channel` of layer `layer` (index into model.style_layout) by sigma times the
+        channel's std under the generator's prior (model.style_stats) """
+        return self._render_s(self._edited_s(layer, channel, sigma))[0]
+
+    def render_s_sweep(self, edits, sigmas):
+        """edit_s for every ((layer, channel), sigma) pair, edit-major: image i * len(sigmas) + j is
+        edit_s(*edits[i], sigmas[j]), bit for bit (the generator is batch-invariant).  Rendered in batches of at
+        most SWEEP_CHUNK.  Returns [len(edits) * len(sigmas), 3, S, S]."""
+        S = self.model.im_res
+        ss = [self._edited_s(l, c, s) for (l, c) in edits for s in sigmas]
+        if not ss:
+            return torch.empty(0, 3, S, S, device=self._device())
+        st = torch.cat(ss)
+        return torch.cat([self._render_s(st[i:i + SWEEP_CHUNK]) for i in range(0, st.shape[0], SWEEP_CHUNK)])
+
     def default(self):
         """ optimized result """
+        if self._latent is None:
+            return self._render_s(self._styles)[0]
         return self._render(self._latent)[0]

@@ -479,6 +479,124 @@ class FeatureAnchor(object):
 
 
 # ---------------------------------------------------------------------------
+# Diagonal prior on the StyleSpace variable
+# ---------------------------------------------------------------------------
+def style_prior_torch(x, center, scale, weight=1.0):
+    """The definition in torch ops, on any device.  x [B, n], center [n], scale [n] (> 0):
+        loss[b] = weight * (1 / n) * sum_i ((x[b, i] - center[i]) * (1 / scale[i]))^2
+    in fp64, rounded once to fp32; differentiable in x.  The CPU path of `diag_prior`."""
+    center = torch.as_tensor(center).to(x.device).double().reshape(-1)
+    inv = 1.0 / torch.as_tensor(scale).to(x.device).double().reshape(-1)
+    if x.dim() != 2 or center.numel() != x.size(1) or inv.numel() != x.size(1):
+        raise ValueError('style_prior: x %s under a center of %d and a scale of %d channels'
+                         % (tuple(x.shape), center.numel(), inv.numel()))
+    d = (x.double() - center) * inv
+    return (float(weight) * ((d * d).sum(1) / d.size(1))).float()
+
+
+class _DiagPriorFn(torch.autograd.Function):
+    """loss [B] of x through p2l_diag_prior_fwd / _bwd: the backward reads x, center and 1 / scale again, nothing is
+    shared between lanes or with a captured graph, nothing waits for the host."""
+
+    @staticmethod
+    def forward(ctx, x, center, inv_scale, weight):
+        from . import ops
+        x = x.detach()
+        ctx.save_for_backward(x, center, inv_scale)
+        ctx.weight = weight
+        return ops.diag_prior_fwd(x, center, inv_scale, weight)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        from . import ops
+        x, center, inv_scale = ctx.saved_tensors
+        return ops.diag_prior_bwd(x, center, inv_scale, ctx.weight, gloss.float().contiguous()), None, None, None
+
+
+def diag_prior(x, center, inv_scale, weight=1.0):
+    """loss [B] fp32 = weight * mean_i ((x[b, i] - center[i]) * inv_scale[i])^2, differentiable in x [B, n]; center and
+    inv_scale are contiguous fp64 [n] on the device of x.  Device tensors run the HIP kernels, CPU tensors
+    `style_prior_torch` (with scale = 1 / inv_scale)."""
+    if not x.is_cuda:
+        return style_prior_torch(x, center, 1.0 / torch.as_tensor(inv_scale).double(), weight)
+    n = x.size(1) if x.dim() == 2 else -1
+    for t, what in ((center, 'center'), (inv_scale, 'inv_scale')):
+        if t.device != x.device or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n:
+            raise ValueError('diag_prior: %s is a contiguous fp64 tensor of %d values on %s (x is %s)'
+                             % (what, n, x.device, tuple(x.shape)))
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    return _DiagPriorFn.apply(x, center, inv_scale, float(weight))
+
+
+class StylePrior(object):
+    """`weight * mean_i (((S - center) / scale)_i^2)` per candidate: the `regularizer=` of the StyleSpace variable of
+    `StyleGAN2(search='s')` (`var_manager.register('z', (model.n_styles,), ..., regularizer=LF.StylePrior.around(s0,
+    model))`).  The 9 088 style channels are free once they no longer come from W+; the term keeps each within its
+    own spread under the generator's prior (StyleSpace, Wu et al. 2021: channel statistics over mapped z).
+    center [n] and scale [n] (> 0) are kept in fp64 on the CPU; the device copies (center and 1 / scale) are made at
+    the first use on a device, which therefore must not happen inside a graph capture."""
+
+    def __init__(self, center, scale, weight=1.0):
+        import hashlib
+        self.center = torch.as_tensor(center).detach().double().cpu().reshape(-1).contiguous()
+        self.scale = torch.as_tensor(scale).detach().double().cpu().reshape(-1).contiguous()
+        if self.center.numel() != self.scale.numel() or self.center.numel() < 1:
+            raise ValueError('StylePrior: center and scale are [n], got %d and %d values'
+                             % (self.center.numel(), self.scale.numel()))
+        if not bool((self.scale > 0).all()) or not bool(torch.isfinite(self.scale).all()):
+            raise ValueError('StylePrior: every scale is positive and finite (see min_std of the constructors)')
+        self.weight = float(weight)
+        h = hashlib.sha1(self.center.numpy().tobytes())
+        h.update(self.scale.numpy().tobytes())
+        self._digest = h.hexdigest()
+        self._on_device = {}
+
+    @staticmethod
+    def _scale_of(model, num_samples, min_std):
+        mean, std = model.style_stats(num_samples=num_samples)
+        return mean, std.clamp(min=float(min_std))
+
+    @classmethod
+    def stylegan2(cls, model, num_samples=100000, weight=1.0, min_std=1e-3):
+        """centred on the channel means of `model.style_stats(num_samples)` with the channel stds as scale: styles of
+        mapped normal z score about `weight`.  A std below `min_std` takes that floor (a channel the affine leaves
+        constant would divide by zero)."""
+        mean, scale = cls._scale_of(model, num_samples, min_std)
+        return cls(mean, scale, weight)
+
+    @classmethod
+    def around(cls, styles0, model, num_samples=100000, weight=1.0, min_std=1e-3):
+        """centred on styles0 [S_total] (`model.styles` of a W+ solution) with the same scale: the distance from
+        the start in units of each channel's spread"""
+        _, scale = cls._scale_of(model, num_samples, min_std)
+        return cls(torch.as_tensor(styles0).reshape(-1), scale, weight)
+
+    def _device_tensors(self, device):
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self._on_device:
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('StylePrior: first use on %s inside a graph capture; call it once eagerly' % device)
+            self._on_device[device] = (self.center.to(device), (1.0 / self.scale).to(device))
+        return self._on_device[device]
+
+    def graph_key(self):
+        """what a captured step bakes in of this term (optimizer/base_optimizer.py `_graph_key`)"""
+        return ('StylePrior', self.center.numel(), self.weight, self._digest)
+
+    def __call__(self, x):
+        if not x.is_cuda:
+            return style_prior_torch(x, self.center, self.scale, self.weight)
+        if x.dim() != 2 or x.size(1) != self.center.numel():
+            raise ValueError('StylePrior: x %s under a prior of %d channels' % (tuple(x.shape), self.center.numel()))
+        center, inv = self._device_tensors(x.device)
+        return diag_prior(x, center, inv, self.weight)
+
+
+# ---------------------------------------------------------------------------
 # `lpips_size`: the LPIPS term on an area-pooled image (the StyleGAN2 projector's 256^2; DESIGN.md section 12)
 # ---------------------------------------------------------------------------
 POOL_FACTORS = (1, 2, 4, 8, 16)

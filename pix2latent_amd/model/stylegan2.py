@@ -13,6 +13,9 @@ Not in the reference: `search='f'` (feature-space / F/W+ inversion, DESIGN.md se
 `f_res` -- `feat`, with the partial RGB `skip` -- next to the W+ rows and noise maps of the layers above it:
 `features(z, noises)` captures both out of a W+ forward, `forward_f` / `__call__(z, noises, feat=, skip=)` run the
 synthesis from there (`p2l_sg2_synthesis_from_*`), `feature_cut` is the arithmetic of the cut.
+`search='s'` (StyleSpace) optimises the per-channel modulation scalars themselves, one flat
+vector [S_total] per candidate named `z`: `styles(wplus)` computes them, `forward_s` runs the synthesis behind the
+affines (`p2l_sg2_synthesis_s_*`), `style_layout` names the layers, `style_stats` gives the channel means and stds.
 
 Weights: `$P2L_STYLEGAN2_<MODEL>_WEIGHTS` (a torch-loadable rosinality checkpoint with a
 'g_ema' entry) if set, else seeded random-init tensors of the same architecture (no
@@ -135,6 +138,92 @@ class _SynthFromFn(torch.autograd.Function):
         return (dlatent if need[0] else None), dnoise, dfeat, dskip, None, None
 
 
+class _SynthStyleFn(torch.autograd.Function):
+    """(styles [B, S_total], layer-major noise) -> image [B,3,S,S]: the synthesis behind the affine layers
+    (p2l_sg2_synthesis_s_fwd / _bwd), in the lane workspace of _SynthFn and under its stamp / stale check.  The noise
+    gets a gradient only when autograd asks for it."""
+
+    @staticmethod
+    def forward(ctx, styles, noise_lm, model):
+        B = styles.shape[0]
+        styles = styles.contiguous().float()
+        noise_lm = noise_lm.contiguous().float()
+        lib, S = model._lib, model.im_res
+        s = model._ensure_ws(B)
+        N.check(lib.p2l_sg2_synthesis_s_fwd(C.byref(model._desc), N.ptr(styles), N.ptr(noise_lm), B, N.ptr(s.ws),
+                                            C.c_size_t(s.ws_bytes), N.ptr(s.img16), N.stream()),
+                'p2l_sg2_synthesis_s_fwd')
+        out = torch.empty(B, 3, S, S, device=styles.device, dtype=torch.float32)
+        N.check(lib.p2l_nhwc16_to_nchw3(N.ptr(s.img16), N.ptr(out), B, S, S, N.stream()),
+                'p2l_nhwc16_to_nchw3')
+        ctx.model, ctx.stamp = model, model._scratch.stamp()
+        ctx.save_for_backward(styles, noise_lm)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        with lanes.use(ctx.stamp[0]):    # (the saved activations live in the forward's lane)
+            return _SynthStyleFn._backward(ctx, dout)
+
+    @staticmethod
+    def _backward(ctx, dout):
+        model = ctx.model
+        styles, noise_lm = ctx.saved_tensors
+        if model._scratch.stale(ctx.stamp):
+            raise N.NativeError('StyleGAN2 workspace was reused by a later forward before '
+                                'backward(); use one model object per in-flight graph')
+        s = model._scratch.here()
+        B, S, lib = styles.shape[0], model.im_res, model._lib
+        N.check(lib.p2l_nchw3_to_nhwc16(N.ptr(dout.contiguous().float()), N.ptr(s.dimg16), B, S,
+                                        S, N.stream()), 'p2l_nchw3_to_nhwc16')
+        need = ctx.needs_input_grad
+        # (the library always writes dstyles: the style gradients are what the pass reduces into)
+        dstyles = torch.empty_like(styles)
+        dnoise = torch.empty_like(noise_lm) if need[1] else None
+        N.check(lib.p2l_sg2_synthesis_s_bwd(C.byref(model._desc), N.ptr(styles), N.ptr(noise_lm), B, N.ptr(s.ws),
+                                            C.c_size_t(s.ws_bytes), N.ptr(s.dimg16), N.ptr(dstyles), N.ptr(dnoise),
+                                            N.stream()), 'p2l_sg2_synthesis_s_bwd')
+        return (dstyles if need[0] else None), dnoise, None
+
+
+StyleEntry = collections.namedtuple('StyleEntry', 'name kind index offset channels res')
+
+
+def _style_entries(convs, rgbs):
+    """network order from (cin, res) per conv and (cin, res, after_conv) per ToRGB"""
+    out, off, rj = [], 0, 0
+    for l, (cin, res) in enumerate(convs):
+        out.append(StyleEntry('conv1' if l == 0 else 'convs.%d' % (l - 1), 'conv', l, off, int(cin), int(res)))
+        off += int(cin)
+        while rj < len(rgbs) and rgbs[rj][2] == l:
+            out.append(StyleEntry('to_rgb1' if rj == 0 else 'to_rgbs.%d' % (rj - 1), 'rgb', rj, off, int(rgbs[rj][0]),
+                                  int(rgbs[rj][1])))
+            off += int(rgbs[rj][0])
+            rj += 1
+    return out
+
+
+def style_layout(size, channels=None):
+    """The StyleSpace layout of a generator of size `size` -- host arithmetic, no device: a list of
+    (name, kind 'conv' | 'rgb', index, offset, channels, res) in network order (conv1, to_rgb1, then per resolution
+    convs.{2j}, convs.{2j+1}, to_rgbs.{j}: the layer numbering of Wu et al., "StyleSpace Analysis", 2021).  An
+    entry's `channels` is the layer's input width, the length of its modulation vector; `index` counts within the
+    kind; the last offset + channels is S_total (9088 at 1024^2, 8960 at 512^2 with the released width table;
+    `channels`: {resolution: width} overrides it)."""
+    size = int(size)
+    if size < 8 or size & (size - 1):
+        raise ValueError('style layout of a %s^2 generator: the size is a power of two >= 8' % size)
+    widths = dict(synthetic.sg2_channels())
+    widths.update(channels or {})
+    log_size = size.bit_length() - 1
+    convs = []
+    for l in range(2 * (log_size - 2) + 1):
+        res = 4 if l == 0 else 2 ** ((l + 1) // 2 + 2)
+        convs.append((widths[res // 2] if l % 2 == 1 else widths[res], res))
+    rgbs = [(widths[4 * 2 ** j], 4 * 2 ** j, 2 * j) for j in range(log_size - 1)]
+    return _style_entries(convs, rgbs)
+
+
 FeatureCut = collections.namedtuple('FeatureCut', 'l0 j0 C rows noise_off')
 
 
@@ -252,7 +341,7 @@ class StyleGAN2(nn.Module):
             latent_out = self.mapping(zs)
             if search == 'z':
                 self.mean_latent = latent_out.mean(0, keepdim=True)
-            elif search in ('w+', 'f'):
+            elif search in ('w+', 'f', 's'):       # ('s': a W+ start is the usual way into StyleSpace)
                 self.latent_mean = latent_out.mean(0)
                 latent_std = (latent_out - self.latent_mean).pow(2).sum()
                 self.latent_std = (latent_std / n_mean_latent) ** 0.5
@@ -326,6 +415,17 @@ class StyleGAN2(nn.Module):
             r.bias = self._t(b32)
         d.n_rgb = len(rgb_names)
         self._noise_sizes = [s[-1] * s[-2] for s in self.noise_shape]
+        # StyleSpace layout in network order; the library's walk of the same descriptor has to agree (a library built
+        # before the entry point existed -- P2L_LIB_PATH, the A/B runs of tools/plan_bits.py -- is not asked)
+        self.style_layout = _style_entries([(d.conv[l].cin, d.conv[l].res) for l in range(d.n_conv)],
+                                           [(d.rgb[j].cin, d.rgb[j].res, d.rgb[j].after_conv) for j in range(d.n_rgb)])
+        self.n_styles = self.style_layout[-1].offset + self.style_layout[-1].channels
+        if hasattr(self._lib, 'p2l_sg2_style_layout'):
+            co, ro, total = (C.c_int32 * d.n_conv)(), (C.c_int32 * d.n_rgb)(), C.c_int32(0)
+            N.check(self._lib.p2l_sg2_style_layout(C.byref(d), co, ro, C.byref(total)), 'p2l_sg2_style_layout')
+            offs = {'conv': co, 'rgb': ro}
+            assert all(offs[e.kind][e.index] == e.offset for e in self.style_layout) and total.value == self.n_styles
+        self._style_stats = {}
 
     lanes_ok = True              # per-lane workspaces: chunks of one step may run on several streams
     _lanes = property(lambda self: self._scratch.lanes)
@@ -382,6 +482,8 @@ class StyleGAN2(nn.Module):
             raise ValueError("feat / skip are the inputs of search='f'; this model searches %r" % (self.search,))
         if self.search == 'w+':
             return self.forward_w(z, noises)
+        if self.search == 's':
+            return self.forward_s(z, noises)
         return self.forward_z(z, noises=noises)
 
     class _CutMethod(object):
@@ -442,6 +544,60 @@ class StyleGAN2(nn.Module):
         latent = z if z.dim() == 3 else z.unsqueeze(1).expand(-1, self._desc.n_latent, -1)
         noise_lm = _NoiseLayoutFn.apply(noises.to(self._dev), self)
         return _SynthFromFn.apply(latent, noise_lm, feat.to(self._dev), skip.to(self._dev), self, int(res))
+
+    # ----------------------------------------------------- StyleSpace (S) search
+    style_layout = staticmethod(style_layout)      # (on the class: no model, no device; an instance holds its list)
+
+    def styles(self, wplus):
+        """[B, S_total]: every layer's affine of its row of the W+ latents wplus [B, n_latent, 512] (or [B, 512], one
+        w for all layers), in the order of `style_layout` -- the bits a forward_w leaves in its style slots
+        (p2l_sg2_styles: the affines alone, no synthesis).  Under no_grad; the result is a new tensor."""
+        with torch.no_grad():
+            w = wplus.detach().to(self._dev, torch.float32)
+            latent = (w if w.dim() == 3 else w.unsqueeze(1).expand(-1, self._desc.n_latent, -1)).contiguous()
+            B = latent.shape[0]
+            if tuple(latent.shape) != (B, self._desc.n_latent, 512):
+                raise ValueError('styles: W+ latents are [B, %d, 512] or [B, 512], got %s'
+                                 % (self._desc.n_latent, list(wplus.shape)))
+            out = torch.empty(B, self.n_styles, device=self._dev, dtype=torch.float32)
+            N.check(self._lib.p2l_sg2_styles(C.byref(self._desc), N.ptr(latent), B, N.ptr(out), N.stream()),
+                    'p2l_sg2_styles')
+        return out
+
+    def style_stats(self, num_samples=100000, chunk_rows=65536, seed=0):
+        """(mean, std) fp64 [S_total] on the device: the channel statistics of styles(mapping(z)) over `num_samples`
+        normal z, drawn chunk by chunk (`chunk_rows` rows at a time) from one CPU generator seeded with `seed`.  The
+        moments are p2l_col_moments_f64 sums continued from chunk to chunk; std is the population one,
+        sqrt(E x^2 - mean^2).  Cached on the model per (num_samples, chunk_rows, seed)."""
+        from .. import ops
+        key = (int(num_samples), int(chunk_rows), int(seed))
+        if key[0] < 1 or key[1] < 1:
+            raise ValueError('style_stats: num_samples and chunk_rows are at least 1')
+        if key not in self._style_stats:
+            g = torch.Generator(device='cpu').manual_seed(key[2])
+            sums = None
+            with torch.no_grad():
+                for lo in range(0, key[0], key[1]):
+                    rows = min(key[1], key[0] - lo)
+                    z = torch.randn(rows, 512, generator=g).to(self._dev)
+                    # (the mapping in batches of the size the constructor uses)
+                    w = torch.cat([self.mapping(z[i:i + 4096]) for i in range(0, rows, 4096)])
+                    st = torch.cat([self.styles(w[i:i + 4096]) for i in range(0, rows, 4096)])
+                    sums = ops.col_moments_f64(st, *(sums or ()))
+            mean = sums[0] / key[0]
+            var = (sums[1] / key[0] - mean * mean).clamp_(min=0.0)
+            self._style_stats[key] = (mean, var.sqrt())
+        return self._style_stats[key]
+
+    def forward_s(self, z, noises):
+        """the synthesis behind the affine layers: z [B, S_total] the styles (`styles`, `style_layout`), noises
+        [B, sum(h*w)] flat.  Gradients go to both."""
+        if z.dim() != 2 or z.shape[1] != self.n_styles:
+            raise ValueError("search='s' takes the styles [B, S_total = %d], got %s" % (self.n_styles, list(z.shape)))
+        if noises is None:
+            raise ValueError("search='s' takes the flat noises [B, %d]" % self._desc.noise_total)
+        noise_lm = _NoiseLayoutFn.apply(noises.to(self._dev), self)
+        return _SynthStyleFn.apply(z.to(self._dev), noise_lm, self)
 
     def forward_z(self, z, truncation=1.0, noises=None):
         """generator([z], truncation=1.0).clamp_(-1, 1); `noises` (list of [B,1,h,w]) makes

@@ -580,3 +580,40 @@ def feature_anchor_bwd(f, anchor, weight, gloss=None):
     N.check(_lib().p2l_feature_anchor_bwd(N.ptr(f), N.ptr(anchor), _anchor_stride(f, anchor), N.ptr(gloss), B, n,
                                           float(weight), N.ptr(df), N.stream()), 'p2l_feature_anchor_bwd')
     return df
+
+
+# ---- StyleSpace search: channel moments and the diagonal prior (csrc/p2l_sg2_style.hip) ----
+def col_moments_f64(x, sum=None, sumsq=None, cols=None):
+    """x [rows, ld] fp32 device tensor (rows may be strided by ld >= cols; `cols` defaults to x.size(1)) ->
+    (sum, sumsq) fp64 [cols] of its columns.  Given `sum` / `sumsq`, the call continues their chains
+    (p2l_col_moments_f64 with accumulate = 1) and returns them."""
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1 and x.size(0) >= 1
+    rows, ld = x.size(0), (x.stride(0) if x.size(0) > 1 else x.size(1))
+    cols = x.size(1) if cols is None else int(cols)
+    acc = sum is not None
+    if not acc:
+        sum = torch.empty(cols, dtype=torch.float64, device=x.device)
+        sumsq = torch.empty(cols, dtype=torch.float64, device=x.device)
+    N.check(_lib().p2l_col_moments_f64(C.c_void_p(x.data_ptr()), rows, cols, ld, _f64_ptr(sum, 'sum', cols),
+                                       _f64_ptr(sumsq, 'sumsq', cols), int(acc), N.stream()), 'p2l_col_moments_f64')
+    return sum, sumsq
+
+
+def diag_prior_fwd(x, center, inv_scale, weight):
+    """x [B, n] fp32 device, center / inv_scale [n] fp64 device -> loss [B] fp32"""
+    B, n = x.shape
+    ws = torch.empty(max(_lib().p2l_diag_prior_ws_bytes(B, n) // 8, 1), dtype=torch.float64, device=x.device)
+    loss = torch.empty(B, dtype=torch.float32, device=x.device)
+    N.check(_lib().p2l_diag_prior_fwd(N.ptr(x), _f64_ptr(center, 'center', n), _f64_ptr(inv_scale, 'inv_scale', n), B,
+                                      n, float(weight), N.ptr(loss), C.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                      N.stream()), 'p2l_diag_prior_fwd')
+    return loss
+
+
+def diag_prior_bwd(x, center, inv_scale, weight, gloss=None):
+    """gloss [B] (None = ones) times d loss / d x, [B, n]"""
+    B, n = x.shape
+    dx = torch.empty_like(x)
+    N.check(_lib().p2l_diag_prior_bwd(N.ptr(x), _f64_ptr(center, 'center', n), _f64_ptr(inv_scale, 'inv_scale', n),
+                                      N.ptr(gloss), B, n, float(weight), N.ptr(dx), N.stream()), 'p2l_diag_prior_bwd')
+    return dx
