@@ -343,7 +343,19 @@ enum { P2L_WFMT_F32 = 0, P2L_WFMT_BF16X3 = 1, P2L_WFMT_BF16X3W = 2, P2L_WFMT_PW 
  * K_pad == 16: conv_to_rgb, the first VGG conv and their input gradients): the BF16X3 image
  * followed by the image of p2l_thin.hip's kernels (27 tap-channel products as one K dimension
  * | a pointwise product onto 27 columns + 9-tap gather).  P2L_WFMT_FLAG_THIN in a MODEL
- * descriptor's wfmt says its image-end weights were packed this way. */
+ * descriptor's wfmt says its image-end weights were packed this way.
+ * The thin kernels take whole 8x16-pixel blocks (H % 8 == 0, W % 16 == 0), ups == 0, and N_pad == 32 with K_pad > 16
+ * (thin output) or K_pad == 16 with N_pad > 32 (thin input); the packer returns P2L_EINVAL for any other padded
+ * shape and for more than three real channels on the thin side.  Every other launch of the format, one with
+ * P2L_FORM_NO_THIN, one with oscale or noise (P2LConvExtra), and a thin-OUTPUT shape with a residual, a mask, a
+ * pool, y == NULL or a fused backward run the generic bf16 x 3 kernel on the first image of the buffer: the same
+ * contract, another summation order.  A thin shape never takes K slices: p2l_conv_suggest_splitk is 1,
+ * p2l_conv_workspace_bytes asks for none whatever d->splitk says, and the launch ignores d->splitk.
+ * Thin output: channels 3 .. n_store - 1 of every stored pixel are act(bias[c]) (+0 without a bias), as the
+ * generic kernel stores them from the packer's zero rows.  Maxima (P2LAmax): a thin-input launch fills
+ * p2l_conv_amax_slots(d) = (H / 8) (W / 16) 4 slots per image, slot 4 block + wave; a thin-output launch has none.
+ * The slot query knows the descriptor alone: a thin-input shape launched with oscale or noise runs the generic
+ * kernel, whose tiles are others, and records NO maxima -- out / outp keep what they held. */
 int p2l_pack_conv_weight_bf3t(const float* w_oihw, int O, int I, int N_pad, int K_pad,
                               int transpose_flip, float* w_packed, void* stream);
 int p2l_pack_conv_weight_pw(const float* w_oihw, int O, int I, int N_pad, int K_pad,

@@ -1904,7 +1904,8 @@ extern "C" int p2l_conv_amax_slots(const P2LConv* d) {
 // (the slices are sized for d->splitk as it stands, never fewer than the launch takes: DESIGN.md 4, the route of a launch)
 extern "C" size_t p2l_conv_workspace_bytes(const P2LConv* d) {
   const Routed q(d);
-  return q.r.amax_bytes + slice_bytes(d, d->splitk);
+  // (a thin shape never takes K slices, on its own kernels or on the generic one its launch may fall back to)
+  return q.r.amax_bytes + (q.r.thin >= 0 ? 0 : slice_bytes(d, d->splitk));
 }
 extern "C" int p2l_conv_arb_fusable(const P2LConv* d) {
   const Routed q(d);

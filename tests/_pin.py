@@ -1,10 +1,10 @@
 """The harness of the tests that pin a kernel against a float64 reference of its own (tests/test_small_kernels_gpu.py,
 tests/test_loss_kernels_gpu.py, tests/test_glue_kernels_gpu.py and the conv families: tests/test_pw_kernels_gpu.py,
 tests/test_wino_kernels_gpu.py, tests/test_direct_kernels_gpu.py, tests/test_subpix_kernels_gpu.py,
-tests/test_gconv_kernels_gpu.py; the metric and the bars are described in the first): seeded draws, guard-banded
-outputs, the pooled error figures and the file they are recorded in.  A test module imports the fixtures `N` and
-`_record_file` by name; `_record_file` writes the rows of the module it was imported into, to the file that module's
-environment variable names."""
+tests/test_gconv_kernels_gpu.py, tests/test_thin_kernels_gpu.py; the metric and the bars are described in the
+first): seeded draws, guard-banded outputs, the pooled error figures and the file they are recorded in.  A test module
+imports the fixtures `N` and `_record_file` by name; `_record_file` writes the rows of the module it was imported
+into, to the file that module's environment variable names."""
 import functools
 import os
 import zlib
@@ -23,7 +23,8 @@ _RECORDS = []
 _ERR_FILE_ENV = {'test_small_kernels_gpu': 'P2L_SMALL_ERR_FILE', 'test_loss_kernels_gpu': 'P2L_LOSS_ERR_FILE',
                  'test_glue_kernels_gpu': 'P2L_GLUE_ERR_FILE', 'test_pw_kernels_gpu': 'P2L_PW_ERR_FILE',
                  'test_wino_kernels_gpu': 'P2L_WINO_ERR_FILE', 'test_direct_kernels_gpu': 'P2L_DIRECT_ERR_FILE',
-                 'test_subpix_kernels_gpu': 'P2L_SUBPIX_ERR_FILE', 'test_gconv_kernels_gpu': 'P2L_GCONV_ERR_FILE'}
+                 'test_subpix_kernels_gpu': 'P2L_SUBPIX_ERR_FILE', 'test_gconv_kernels_gpu': 'P2L_GCONV_ERR_FILE',
+                 'test_thin_kernels_gpu': 'P2L_THIN_ERR_FILE'}
 
 
 class _Native(object):

@@ -6,7 +6,8 @@ independent formulations, tests/test_small_kernels_gpu.py, tests/test_loss_kerne
 tests/test_glue_kernels_gpu.py, tests/test_pw_kernels_gpu.py (the 1x1 convs: references, per-route fp32
 restatements, host packers and the case tables) and tests/test_wino_kernels_gpu.py (the Winograd 3x3 routes: the
 same), tests/test_direct_kernels_gpu.py (the direct 3x3 routes, ups 0 / 1: the same) and
-tests/test_subpix_kernels_gpu.py (the sub-pixel routes, ups 2 / 3: the same) hold the kernels to them.  (The
+tests/test_subpix_kernels_gpu.py (the sub-pixel routes, ups 2 / 3: the same) and tests/test_thin_kernels_gpu.py (the
+thin 3-channel routes: the same) hold the kernels to them.  (The
 closed-form lpips_tap_bwd and the pool backwards are the exceptions to "autograd through the forward":
 the first because autograd has no value at ||f|| == 0, the second are autograd through F.max_pool2d.)
 
@@ -2570,6 +2571,357 @@ def gconv_onehot(c, spot, n=0):
     ci, o, tap = torch.arange(Cin).view(1, Cin, 1), torch.arange(Cout).view(Cout, 1, 1), torch.arange(T).view(1, 1, T)
     w = (1.0 + (ci % 16) / 16.0 + o / 1024.0) * 2.0 ** (tap - T // 2 + ci // 16).double()
     return dict(x=x, w=w.float().view(Cout, Cin, c['KH'], c['KW']))
+
+
+# ---- thin 3x3 convs: three real channels on one side (tests/test_thin_kernels_gpu.py) ---------------------------------
+# Routes of a taps = 9, ups = 0, P2L_WFMT_BF16X3T launch (csrc/p2l_thin.hip): TI conv_thinin_kernel (16 (3 real) -> Cout
+# > 32), TO conv_thinout_kernel (Cin > 16 -> 32 (3 real)), B the generic bf16 x 3 kernel on the first image of the same
+# buffer -- by P2L_FORM_NO_THIN, by a shape thin_shape does not take, or by the launch's arguments (thin_takes: oscale /
+# noise on either shape; a residual, a mask, a pool, y == NULL or a fused backward on a thin-output shape) -- and F
+# (P2L_WFMT_F32) the recorded twin.  A case's weight is the [Cout, Cin, 3, 3] correlation kernel the launch applies,
+# zero outside its real channels (the packer's zeros); the packer is handed the real channels alone (thin_weight).
+WFMT_BF16X3T, FORM_NO_THIN = 4, 16
+
+
+def thin_real(c):
+    """(real input channels, real output channels): 3 of the 16 / 32 the thin side is padded to"""
+    return (3 if c['Cin'] == 16 else c['Cin']), (3 if c['Cout'] == 32 else c['Cout'])
+
+
+def thin_kind(c):
+    """thin_shape (csrc/p2l_conv.hip) and p2l_thin_mode restated: 1 thin input, 0 thin output, -1 neither.  (x_ld % 4
+    is in thin_shape too, but conv_prepare refuses such a pitch in front of the route: no launch gets that far.)"""
+    if c['H'] % 8 or c['W'] % 16 or c['ups']:
+        return -1
+    if c['Cout'] == 32 and c['Cin'] > 16:
+        return 0
+    return 1 if c['Cin'] == 16 and c['Cout'] > 32 else -1
+
+
+def thin_falls_back(c, arb=False):
+    """thin_takes restated: a thin shape whose launch the generic kernel runs because of its ARGUMENTS"""
+    kind = thin_kind(c)
+    if kind < 0:
+        return False
+    if c.get('oscale') or c.get('noise'):
+        return True
+    return kind == 0 and bool(arb or c['res'] or c['mask'] or c['pool'] != POOL_NONE or not c['want_y'])
+
+
+def thin_form(c, route=None):
+    """-> (P2LConv.wfmt, P2LConv.form) of a case on `route`: B carries P2L_FORM_NO_THIN only where nothing else keeps
+    the launch off the thin kernels"""
+    route = route or c['route']
+    if route == 'F':
+        return 0, 0
+    if route == 'B' and thin_kind(c) >= 0 and not thin_falls_back(c):
+        return WFMT_BF16X3T, FORM_NO_THIN
+    return WFMT_BF16X3T, 0
+
+
+def _tc(route, HW, B, Cin, Cout, **kw):
+    c = _dc(route, HW, B, Cin, Cout)
+    c.update(wfmt='bf3t', y_gap=4, x_gap=4)             # y_ld = n_store + y_gap, x_ld = Cin + x_gap
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def thin_id(c):
+    d = _tc(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+# the smallest shapes at which each form of the two kernels exists (a block is 8 x 16 pixels of one image)
+THIN_SHAPES = {
+    'i8x16': ((8, 16), 1, 16, 64),         # thin input: one block, all four borders in one patch; two 32-channel tiles
+    'i16x32': ((16, 32), 2, 16, 64),       # 2 x 2 tiles per image: seams in both directions, a block range changes image
+    'i24x16': ((24, 16), 3, 16, 96),       # three tile rows, nine blocks (xcd_remap: no multiple of 8); three tiles
+    'i8x48': ((8, 48), 2, 16, 64),         # three tile columns
+    'o8x16': ((8, 16), 1, 32, 32),         # thin output: one block; two 16-channel chunks, the fewest the mode admits
+    'o16x32': ((16, 32), 2, 48, 32),       # 2 x 2 tiles; three chunks: the first stage buffer is written a second time
+    'o24x16': ((24, 16), 3, 64, 32),       # three tile rows, nine blocks; four chunks
+    'o8x48': ((8, 48), 2, 32, 32),         # three tile columns
+    'o16x16': ((16, 16), 2, 32, 32),       # two tile rows (run at another x_ld: every multiple of four is a thin pitch)
+    'n12x20': ((12, 20), 2, 16, 64),       # not thin: partial tiles in both directions
+    'n8x8': ((8, 8), 3, 32, 32),           # not thin: W % 16, two images per tile
+    'n32from16': ((16, 16), 2, 16, 32),    # not thin: 32 <- 16, which neither mode admits (and the packer refuses)
+}
+
+
+def _tsh(route, name, **kw):
+    HW, B, Cin, Cout = THIN_SHAPES[name]
+    return _tc(route, HW, B, Cin, Cout, **kw)
+
+
+THIN_FWD_CASES = [
+    # thin input: the epilogues the conv sections share (EPI[6], oscale + noise: the launch falls back to B) ...
+    _tsh('TI', 'i8x16', **EPI[0]), _tsh('TI', 'i16x32', **EPI[1]), _tsh('TI', 'i24x16', **EPI[2]),
+    _tsh('TI', 'i8x48', **EPI[3]), _tsh('TI', 'i16x32', **EPI[4]), _tsh('TI', 'i24x16', **EPI[5]),
+    _tsh('B', 'i8x48', **EPI[6]),
+    # ... the second 32-channel tile storing one float4 group / nothing, the prologues shared by the batch
+    _tsh('TI', 'i16x32', n_store=36, pro=PRO_AFFINE_RELU, pro_b=0, bias=True),
+    _tsh('TI', 'i8x16', n_store=16, pro=PRO_AFFINE, pro_b=1, act=ACT_LRELU_SQRT2),
+    # ... the first VGG / LPIPS conv verbatim: shared scaling layer, bias, ReLU
+    _tsh('TI', 'i16x32', pro=PRO_AFFINE, pro_b=0, bias=True, act=ACT_RELU),
+    _tsh('B', 'i8x16', noise=True, bias=True), _tsh('B', 'i16x32', oscale=True, pro=PRO_AFFINE_RELU),
+    # thin output: conv_to_rgb verbatim (shared affine-ReLU, bias, tanh, n_store = y_ld = 16) and the first VGG conv's
+    # input gradient verbatim (64 -> 3 plain, n_store = y_ld = 16); then 2 / 3 / 4 chunks, n_store 4 / 16 / 32, every
+    # prologue shared and per image, alpha, every activation
+    _tsh('TO', 'o16x32', n_store=16, y_gap=0, pro=PRO_AFFINE_RELU, pro_b=0, bias=True, act=ACT_TANH),
+    _tsh('TO', 'o24x16', n_store=16, y_gap=0),
+    _tsh('TO', 'o8x16', n_store=4),
+    _tsh('TO', 'o8x48', n_store=32, pro=PRO_AFFINE_RELU, pro_b=1, alpha=0.5, act=ACT_RELU),
+    _tsh('TO', 'o16x32', n_store=32, pro=PRO_AFFINE, pro_b=0, bias=True, act=ACT_LRELU_SQRT2),
+    _tsh('TO', 'o24x16', n_store=4, pro=PRO_AFFINE, pro_b=1, bias=True, alpha=0.7),
+    _tsh('TO', 'o16x16', n_store=16, x_gap=8, bias=True, act=ACT_TANH),
+    # a thin-output shape whose arguments send it to the generic kernel
+    _tsh('B', 'o8x16', n_store=16, res='same', bias=True), _tsh('B', 'o16x32', n_store=16, mask=True, pro=PRO_AFFINE_RELU),
+    _tsh('B', 'o24x16', n_store=32, act=ACT_RELU, pool=POOL_MAX), _tsh('B', 'o8x48', n_store=16, pool=POOL_SUM, want_y=False),
+    _tsh('B', 'o8x16', n_store=16, oscale=True), _tsh('B', 'o16x32', n_store=16, y_gap=0, noise=True, act=ACT_TANH),
+    # shapes thin_shape does not take, on the same format
+    _tsh('B', 'n12x20', n_store=36, bias=True, act=ACT_TANH), _tsh('B', 'n8x8', n_store=16, y_gap=0, bias=True),
+    _tsh('B', 'n32from16', n_store=16, pro=PRO_AFFINE, bias=True),
+]
+
+
+def _tac(route, HW, B, Cin, Cout, **kw):
+    c = _dac(route, HW, B, Cin, Cout)
+    c.update(wfmt='bf3t')
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    return c
+
+
+def thin_arb_id(c):
+    d = _tac(c['route'], (c['H'], c['W']), c['B'], c['Cin'], c['Cout'])
+    return '%s-%dx%dx%d-%dto%d' % (c['route'], c['B'], c['H'], c['W'], c['Cin'], c['Cout']) + ''.join(
+        '-%s%s' % (k, c[k]) for k in sorted(c) if c[k] != d[k])
+
+
+# conv_to_rgb's input gradient: dy with three real channels -> ch, the backward of relu(x s + t) fused, with and
+# without the maxima of dx; the last: a thin-OUTPUT shape with a fused backward, which the generic kernel runs
+THIN_ARB_CASES = [_tac(*base, **dict(kw, **v)) for base, kw in [
+    (('TI', (16, 32), 2, 16, 64), {}), (('TI', (24, 16), 3, 16, 96), dict(amax_out=True)),
+    (('TI', (8, 48), 2, 16, 64), dict(amax_out=True))] for v in ARB_VARIANTS] + [_tac('B', (16, 32), 2, 48, 32)]
+
+
+def thin_inputs(g, c):
+    """the operands of a forward case, dense fp32, at direct_inputs' magnitudes: every image at a magnitude of its own
+    (mags), the first x 1e-6 and the last x 3e4 on top -- x, a per-image t, the residual and the noise alike (a
+    prologue shared by the batch keeps `mags` alone: one t has to fit every image).  x and w are zero outside the real
+    channels; s and t hold finite junk there, which no route may show.  |t| is 0.6 .. 1.5 of the image's max |x|, positive
+    on channel 0 and negative on channel 1: relu(t) > 0 and t != 0, so padding in FRONT of the prologue shows at
+    every border pixel under either prologue"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    ri, ro = thin_real(c)
+    rn = lambda *sh: torch.randn(*sh, generator=g)
+    mg = mags(B)
+    if B >= 2 and (c['pro'] == PRO_NONE or c['pro_b']):
+        mg = mg.clone()
+        mg[0], mg[B - 1] = mg[0] * 1e-6, mg[B - 1] * 3e4
+    x = rn(B, H, W, Cin) * mg.view(B, 1, 1, 1)
+    x[..., ri:] = 0.0
+    w = torch.zeros(Cout, Cin, 3, 3)
+    w[:ro, :ri] = rn(ro, ri, 3, 3) / math.sqrt(9 * ri)
+    i = dict(x=x, w=w)
+    xmax = x.abs().amax(dim=(1, 2, 3))
+    out_mag = mg.view(B, 1, 1, 1)
+    if c['pro'] != PRO_NONE:
+        Bs = B if c['pro_b'] else 1
+        s = 0.5 + torch.rand(Bs, Cin, generator=g)
+        sign = torch.where(torch.rand(Bs, Cin, generator=g) < 0.5, -1.0, 1.0)
+        sign[:, 0], sign[:, 1] = 1.0, -1.0
+        unit = xmax[:Bs].view(Bs, 1) if c['pro_b'] else xmax.min()
+        t = sign * (2.0 + 3.0 * torch.rand(Bs, Cin, generator=g)) * 0.3 * unit
+        s[:, ri:], t[:, ri:] = 7.5, -3.25 * unit * torch.ones(Bs, Cin - ri)
+        i['s'], i['t'] = s, t
+    if c['bias']:
+        i['bias'] = 0.1 * rn(Cout)
+    if c['res'] == 'same':
+        i['res'] = rn(B, H, W, Cout) * out_mag
+    elif c['res'] == 'ups':
+        i['res'] = rn(B, H // 2, W // 2, Cout) * out_mag
+    if c['mask']:
+        i['mask'] = rn(B, H, W, Cout)
+    if c['oscale']:
+        i['oscale'] = 0.5 + torch.rand(B, Cout, generator=g)
+    if c['noise']:
+        i['noise'], i['noise_w'] = rn(B, H, W) * out_mag[..., 0], 0.3
+    return i
+
+
+def thin_weight(c, i, flip=False):
+    """the OIHW tensor the packer is handed: the real channels alone; flip: the forward conv's tensor whose input
+    gradient the launch applies, for the packer's transpose_flip copy"""
+    ri, ro = thin_real(c)
+    w = i['w'][:ro, :ri]
+    return (w.permute(1, 0, 2, 3).flip(2, 3) if flip else w).contiguous()
+
+
+def thin_cols(a):
+    """thin input: the zero-padded a [B, H, W, >= 3] -> [B, H, W, 32], column kk = 3 tap + c holds channel c of pixel
+    (y + dy - 1, x + dx - 1), tap = 3 dy + dx; columns 27 .. 31 zero (read off the A-fragment loop)"""
+    B, H, W, _ = a.shape
+    ap = F.pad(a[..., :3], (0, 0, 1, 1, 1, 1))
+    taps = [ap[:, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)]
+    return torch.cat(taps + [torch.zeros(B, H, W, 5, dtype=a.dtype)], dim=3)
+
+
+def thin_wmat(w):
+    """[N, >= 3, 3, 3] -> [N, 32] in thin_cols' order"""
+    N = w.shape[0]
+    return torch.cat([w[:, :3].permute(0, 2, 3, 1).reshape(N, 27), torch.zeros(N, 5, dtype=w.dtype)], dim=1)
+
+
+def thin_acc32(c, i, route=None, mm=None):
+    """the fp32 restatement of a route's accumulator in front of alpha, [B, H, W, Cout], in the order read off the
+    kernels (mm: the matrix product in place of acc_bf3 -- tests/test_small_refs.py runs the same walk in fp64).  TI:
+    acc_bf3 over the 32 columns kk = 3 tap + c in two 16-steps.  TO: Z = acc_bf3 of every pixel of the zero-padded
+    (AFTER the prologue) tensor onto the 27 columns 3 tap + c over 16-channel chunks; an output is the sum of its
+    nine Z values in fp32, tap 0 first, starting from 0; channels 3 .. 31 hold 0.  B: direct_acc32 unchanged"""
+    route = route or c['route']
+    if route == 'B':
+        return direct_acc32(c, i, 'B')
+    mm = mm or acc_bf3
+    a, _ = pw_prologue(i['x'], c['pro'], i.get('s'), i.get('t'))
+    B, H, W, Cin = a.shape
+    if route == 'TI':
+        return mm(thin_cols(a), thin_wmat(i['w']))
+    assert route == 'TO'
+    wz = i['w'][:3].permute(2, 3, 0, 1).reshape(27, Cin)                     # row 3 tap + c
+    z = mm(F.pad(a, (0, 0, 1, 1, 1, 1)), wz)                                  # [B, H + 2, W + 2, 27]
+    s = torch.zeros(B, H, W, 3, dtype=a.dtype)
+    for tap in range(9):
+        dy, dx = tap // 3, tap % 3
+        s = s + z[:, dy:dy + H, dx:dx + W, 3 * tap:3 * tap + 3]
+    acc = torch.zeros(B, H, W, c['Cout'], dtype=a.dtype)
+    acc[..., :3] = s
+    return acc
+
+
+def thin_refs(c, i, route=None, restate=True):
+    """-> conv3x3's dict in fp64 on den_d = sum_taps,k |a| |w| through the epilogue, and the route's fp32 restatement's
+    (route F or restate = False: None)"""
+    route = route or c['route']
+    i64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in i.items()}
+    r64 = conv3x3(i64['x'], i64['w'], den_w=False, **pw_kwargs(c, i, torch.float64))
+    if not restate or route == 'F':
+        return r64, None
+    return r64, conv3x3(i['x'], i['w'], acc=thin_acc32(c, i, route), den_w=False, **pw_kwargs(c, i, torch.float32))
+
+
+def thin_k(c, route=None, pooled=False):
+    """the bar's k of a thin case, counted like direct_k from the arithmetic of csrc/p2l_thin.hip.  Per column onto an
+    accumulator the six cross terms of exact products (6) -- TI: the 32 columns 3 tap + c of its two 16-steps (192);
+    TO: the Cin columns of one Z value (6 Cin; the nine Z values of an output each carry that against their own share
+    of sum |terms|), then the eight additions of the tap sum (8).  The pieces to 2^-24 relative of either operand (2)
+    and the dropped terms <= 2^-23 (2).  Then pw_k's prologue and epilogue terms: the prologue's fma (2); alpha, oscale,
+    bias, noise (a product and a sum), residual one each; tanh 2; the leaky ReLU's factor sqrt 2 on everything before
+    it and its own rounding; the pool's sum two additions deep.  Route B from the same buffer: direct_k's"""
+    route = route or c['route']
+    if route == 'B':
+        return direct_k(c, 'B', pooled)
+    k = (6 * 32 if route == 'TI' else 6 * c['Cin'] + 8) + 4
+    k += (2 if c['pro'] != PRO_NONE else 0) + 1 + c['oscale'] + c['bias'] + 2 * c['noise'] + (c['res'] is not None)
+    if c['act'] == ACT_TANH:
+        k += 2
+    if c['act'] == ACT_LRELU_SQRT2:
+        k = 1.5 * k + 1
+    return k + 2 if pooled and c['pool'] == POOL_SUM else k
+
+
+def thin_spots(H, W, B):
+    """(image, y, x) of the one-hot pixels on a grid of whole 8 x 16 blocks: the corners and edge midpoints, both sides
+    of every 8-row and 16-column seam, both sides of every wave boundary inside a block (rows 2 w + 1 | 2 w + 2), both
+    sides of a quad boundary in x, the interior, and the first and last pixel of the second image"""
+    sp = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1), (0, 0, W // 2), (0, H // 2, 0),
+          (0, H - 1, W // 2 - 1), (0, H // 2, W - 1), (0, H // 2, W // 2), (0, 1, 1), (0, H - 2, W - 2)]
+    for ys in range(8, H, 8):
+        sp += [(0, ys - 1, W // 3), (0, ys, W // 3), (0, ys - 1, W - 1), (0, ys, 0)]
+    for xs in range(16, W, 16):
+        sp += [(0, H // 3, xs - 1), (0, H // 3, xs), (0, 0, xs - 1), (0, H - 1, xs)]
+    for wv in range(3):
+        sp += [(0, 2 * wv + 1, 5), (0, 2 * wv + 2, 5)]
+    sp += [(0, 3, 7), (0, 3, 8), (0, 4, 9), (0, 4, 10)]
+    if B > 1:
+        sp += [(1, 0, 0), (1, H - 1, W - 1), (B - 1, 0, W - 1), (B - 1, H - 1, 0)]
+    out = []
+    for s in sp:
+        if s not in out:
+            out.append(s)
+    return out
+
+
+def thin_onehot(c, tap, seed=0):
+    """exact inputs: x with single power-of-two pixels at thin_spots, in one of the real channels in turn; w with
+    single power-of-two entries on `tap` at a few (cout, cin) whose input channels hold pixels.  Every output is a sum
+    of a few powers of two within a few binades: exact in fp32 and in three bf16 pieces, through the 27-column K of
+    TI and the Z columns and tap sum of TO alike"""
+    B, H, W, Cin, Cout = c['B'], c['H'], c['W'], c['Cin'], c['Cout']
+    ri, ro = thin_real(c)
+    x, w = torch.zeros(B, H, W, Cin), torch.zeros(Cout, Cin, 3, 3)
+    spots = thin_spots(H, W, B)
+    for n, (b, py, px) in enumerate(spots):
+        x[b, py, px, (5 * (n + seed)) % ri] = 2.0 ** ((n + seed) % 5 - 2)
+    for n in range(min(len(spots), max(ri, 10))):
+        w[(37 * n + seed) % ro, (5 * (n + seed)) % ri, tap // 3, tap % 3] = 2.0 ** (n % 3 - 1) * (-1.0) ** n
+    return dict(x=x, w=w)
+
+
+def thin_arb_inputs(g, c):
+    """direct_arb_inputs with dy and w zero outside the real channels (the loss backward's NHWC16 gradient), and a
+    dead unit: channel 5 of every image has x s + t < 0 at every pixel (ds = dt = 0 there, exactly, unless nomask)"""
+    i = direct_arb_inputs(g, c)
+    ri, ro = thin_real(c)
+    i['at'][:, 5] = -2.0 * i['as'][:, 5].abs() * i['ax'][..., 5].abs().amax(dim=(1, 2))
+    i['x'][..., ri:] = 0.0
+    i['w'][ro:] = 0.0
+    i['w'][:, ri:] = 0.0
+    i['w'] *= math.sqrt(c['Cin'] / float(ri))
+    return i
+
+
+def thin_arb_sums32(g, x, H, W, pool_sum):
+    """ds, dt of fp32 g, x [B, Ho, Wo, C] for a thin-input launch on the H x W grid, in the kernel's order.  An item
+    is one 2x2 quad (one pixel under pool_sum) and four channels: its pixels onto the running sum in sequence, `sgx +=
+    g x` fused, `sg += g`.  Lane 8 q + c4 holds quad q of the wave's two rows: the xor-shuffle over lanes >= 8 (offsets
+    8, 16, 32) adds q ^ 1, q ^ 2, q ^ 4; wave w holds rows 2 w, 2 w + 1 of the block and the four waves meet as (0 + 1) +
+    (2 + 3); one partial per 8 x 16 block, blocks row-major; then p2l_arb_finish (arb_finish_order32)"""
+    def stage(prod):
+        if pool_sum:
+            q = prod(g, x, None)
+        else:
+            q = None
+            for gq, xq in zip(quads(g), quads(x)):
+                q = prod(gq, xq, q)
+        Bn, Hq, Wq, Cc = q.shape
+        assert (Hq, Wq) == (H // 2, W // 2) and H % 8 == 0 and W % 16 == 0
+        t = q.reshape(Bn, Hq // 4, 4, Wq // 8, 8, Cc).permute(0, 1, 3, 2, 4, 5)    # [B, ty, tx, wave, quad, C]
+        v = [t[..., j, :] for j in range(8)]
+        for o in (1, 2, 4):
+            v = [v[j] + v[j ^ o] for j in range(8)]
+        wv = v[0]                                                                  # (every lane holds the same sum)
+        blk = (wv[..., 0, :] + wv[..., 1, :]) + (wv[..., 2, :] + wv[..., 3, :])
+        return arb_finish_order32(blk.reshape(Bn, -1, Cc))
+    return (stage(lambda gq, xq, acc: gq * xq if acc is None else fma(gq, xq, acc)),
+            stage(lambda gq, xq, acc: gq if acc is None else acc + gq))
+
+
+def thin_arb_refs(c, i):
+    """-> conv3x3_arb's dict in fp64 on the direct denominator and the route's fp32 restatement's, ds and dt in the
+    kernel's two stages (TI: thin_arb_sums32; B: arb_sums32, one partial per 128-pixel tile)"""
+    kw = dict(pool_sum=c['pool_sum'], nomask=c['nomask'], skip=i.get('skip'), skip_C=c['Cout'] // 2 if c['skip'] else 0,
+              skip_ups=c['skip'] == 'ups')
+    r64 = conv3x3_arb(i['x'].double(), i['w'].double(), i['ax'].double(), i['as'].double(), i['at'].double(),
+                      den_w=False, **kw)
+    r32 = conv3x3_arb(i['x'], i['w'], i['ax'], i['as'], i['at'], acc=thin_acc32(c, i), den_w=False, **kw)
+    if c['route'] == 'TI':
+        r32['ds'], r32['dt'] = thin_arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'])
+    else:
+        r32['ds'], r32['dt'] = arb_sums32(r32['g'], i['ax'], c['H'], c['W'], c['pool_sum'], False)
+    return r64, r32
 
 
 # ---- optimiser ----------------------------------------------------------------------------------------------------

@@ -1378,3 +1378,244 @@ def test_gconv_case_table():
     assert all(max(c['Hi'], c['Wi']) <= 24 for c in cs + list(R.GCONV_PAIR))
     assert len(set(R.gconv_id(c) for c in GCONV_ALL)) == len(GCONV_ALL)
     assert [c['col'] for c in R.GCONV_PAIR] == [0, 64] and all(c['y_ld'] == 128 for c in R.GCONV_PAIR)
+
+
+# ---- thin 3x3 convs ---------------------------------------------------------------------------------------------------
+def _thin_route(case):
+    """the route a forward case's own launch takes and, where it is a thin one, B beside it"""
+    return [case['route']] + (['B'] if case['route'] != 'B' else [])
+
+
+@pytest.mark.parametrize('case', R.THIN_FWD_CASES, ids=R.thin_id)
+def test_thin_forward_reference_is_conv2d_and_the_walks_are_the_conv(case):
+    """from the definition alone: the fp64 reference of a case is F.conv2d(padding = 1) of the prologue's result on
+    the REAL channels with the real weight, through the epilogue; and the walk of either thin kernel (27 tap-channel
+    columns as one K | Z columns and the nine-tap sum), run with a plain fp64 matrix product, is that conv"""
+    i = R.thin_inputs(_g(400), case)
+    ri, ro = R.thin_real(case)
+    kw = R.pw_kwargs(case, i, D)
+    r64, _ = R.thin_refs(case, i, restate=False)
+    x, s, t = i['x'].double()[..., :ri], kw['s'], kw['t']
+    a = x if case['pro'] == R.PRO_NONE else x * s[:, None, None, :ri] + t[:, None, None, :ri]
+    a = torch.relu(a) if case['pro'] == R.PRO_AFFINE_RELU else a
+    v = F.conv2d(a.permute(0, 3, 1, 2), i['w'].double()[:ro, :ri], padding=1).permute(0, 2, 3, 1)
+    full = torch.zeros(v.shape[:3] + (case['Cout'],), dtype=D)
+    full[..., :ro] = v
+    want = R.conv_epilogue(full * case['alpha'], torch.ones_like(full),
+                           **{k: u for k, u in kw.items() if k not in ('pro', 's', 't', 'alpha')})
+    for out in ('y', 'yp'):
+        if r64[out] is not None:
+            scale = r64['den' if out == 'y' else 'denp'].clamp_min(1e-300)
+            assert float(((want[out] - r64[out]).abs() / scale).max()) < 1e-12, out
+    assert bool(torch.isfinite(r64['y']).all()) and bool(torch.isfinite(r64['den']).all())   # (the junk of s, t shows nowhere)
+    kind = R.thin_kind(case)
+    if kind >= 0:
+        i64 = {k: (u.double() if torch.is_tensor(u) else u) for k, u in i.items()}
+        walk = R.thin_acc32(case, i64, 'TI' if kind else 'TO', mm=lambda p, q: p @ q.t())
+        den = F.conv2d(a.abs().permute(0, 3, 1, 2), i['w'].double()[:ro, :ri].abs(), padding=1).permute(0, 2, 3, 1)
+        assert float(((walk[..., :ro] - v).abs() / den.clamp_min(1e-300)).max()) < 1e-12
+        assert bool((walk[..., ro:] == 0).all())
+
+
+@pytest.mark.parametrize('case', R.THIN_FWD_CASES, ids=R.thin_id)
+def test_thin_forward_restatements_stay_under_a_quarter_of_k(case):
+    """for every case's generator and shape the fp32 restatement of its route -- and of route B on the same inputs --
+    is within k / 4 of the fp64 reference on den_d.  Under a prologue with t != 0 (relu(t) > 0 on channel 0) zero
+    padding applied in FRONT of the prologue is more than 100 bars off at the border of the thin cases."""
+    def body(gen):
+        i = R.thin_inputs(gen('thin', R.thin_id(case)), case)
+        for route in _thin_route(case):
+            r64, r32 = R.thin_refs(case, i, route)
+            for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+                if r64[out] is not None:
+                    f = _fig(r32[out], r64[out], r64[den])
+                    assert f <= R.thin_k(case, route, pooled) / 4.0, (route, out, f, R.thin_k(case, route, pooled))
+        if case['pro'] != R.PRO_NONE:
+            t = i['t']
+            assert bool((t[:, 0] > 0).all()) and bool((t[:, 1] < 0).all())          # relu(t) > 0 somewhere, t != 0
+        if case['pro'] != R.PRO_NONE and case['act'] == R.ACT_NONE and not case['mask'] and case['route'] != 'B':
+            kw = R.pw_kwargs(case, i, D)
+            r64, r32 = R.thin_refs(case, i)
+            a, _ = R.pw_prologue(i['x'].double(), case['pro'], i['s'].double(), i['t'].double())
+            halo, _ = R.pw_prologue(torch.zeros_like(i['x'][:, :1, :1]).double(), case['pro'], i['s'].double(), i['t'].double())
+            ap = F.pad(a - halo, (0, 0, 1, 1, 1, 1)) + halo                      # the halo holds prologue(0)
+            wrong = F.conv2d(ap.permute(0, 3, 1, 2), i['w'].double()).permute(0, 2, 3, 1) * case['alpha']
+            wrong = R.conv_epilogue(wrong, torch.ones_like(wrong), **{k: v for k, v in kw.items() if k not in ('pro', 's', 't', 'alpha')})
+            ro = R.thin_real(case)[1]
+            for out, den, pooled in (('y', 'den', False), ('yp', 'denp', True)):
+                if r64[out] is None:
+                    continue
+                err = ((wrong[out] - r64[out]).abs() / r64[den].clamp_min(1e-300) / R.U)[..., :min(ro, case['n_store'])]
+                border = torch.ones(err.shape[1:3], dtype=torch.bool)
+                border[1:-1, 1:-1] = False
+                bar = min(R.thin_k(case, None, pooled), 4.0 * _fig(r32[out], r64[out], r64[den]))
+                assert float(err[:, border].median()) > 100 * bar, (out, bar)
+                assert float(err[:, ~border].max()) < 1e-3
+    _draws(body)
+
+
+@pytest.mark.parametrize('case', R.THIN_ARB_CASES, ids=R.thin_arb_id)
+def test_thin_dgrad_reference_is_autograd_and_restatements_stay_under_a_quarter_of_k(case):
+    """da of the fp64 reference is autograd through F.conv2d of the FORWARD conv whose OIHW tensor the packer is handed
+    for its transpose_flip copy (thin_weight(flip = True)); dx, ds, dt of the restatement as in the direct module"""
+    kfn = lambda cc, route=None, pooled=False: R.thin_k(cc, case['route'], pooled)
+
+    def body(gen):
+        i = R.thin_arb_inputs(gen('tarb', R.thin_arb_id(case)), case)
+        kdx, kds, kdt = R.arb_k(case, kfn)
+        r64, r32 = R.thin_arb_refs(case, i)
+        f = _fig(r32['dx'], r64['dx'], r64['den_dx'])
+        assert f <= kdx / 4.0, ('dx', f, kdx)
+        for name, bound in zip(('ds', 'dt'), R.arb_bound(case, r64, i['ax'], kfn)):
+            assert bool(((r32[name].double() - r64[name]).abs() <= bound * R.U).all()), name
+        p64, p32 = R.thin_arb_refs(case, R.arb_positive(i))
+        for name, k in (('ds', kds), ('dt', kdt)):
+            f = _fig(p32[name], p64[name], p64['den_' + name])
+            assert f <= k / 4.0, (name, f, k)
+        if not case['nomask'] and not case['skip']:
+            assert bool((r64['g'] == 0).any()) and bool((r64['g'] != 0).any())       # masked-off elements exist
+    _draws(body)
+    # the flip, from the definition: the launch's weight applied as a correlation == the input gradient of the forward conv
+    i = R.thin_arb_inputs(_g(410), case)
+    ri, ro = R.thin_real(case)
+    wf = R.thin_weight(case, i, flip=True).double()                           # forward conv: [O = ri, I = ro, 3, 3]
+    assert wf.shape == (ri, ro, 3, 3)
+    dy = i['x'].double()[..., :ri].permute(0, 3, 1, 2)
+    xin = torch.zeros(case['B'], ro, case['H'], case['W'], dtype=D, requires_grad=True)
+    F.conv2d(xin, wf, padding=1).backward(dy)
+    da = R.conv3x3(i['x'].double(), i['w'].double(), den_w=False)['y']
+    assert float((da[..., :ro] - xin.grad.permute(0, 2, 3, 1)).abs().max()) < 1e-12 * float(da.abs().max())
+    assert bool((da[..., ro:] == 0).all())
+
+
+def test_thin_arb_sums_and_dead_units():
+    """thin_arb_sums32, restated from the thin-input kernel (butterfly over lanes >= 8, (0 + 1) + (2 + 3), one partial
+    per 8 x 16 block), gives the bits of arb_sums32's unsplit order on whole 8 x 16 tiles; its fp64 value is the plain
+    sum; the gradient inputs hold a dead unit (a channel of an image with no live pixel)"""
+    g = _g(420)
+    for H, W, pool_sum in ((16, 32, False), (24, 16, True), (8, 48, False)):
+        Ho, Wo = (H // 2, W // 2) if pool_sum else (H, W)
+        gg, xx = torch.randn(2, Ho, Wo, 8, generator=g), torch.randn(2, Ho, Wo, 8, generator=g)
+        a, b = R.thin_arb_sums32(gg, xx, H, W, pool_sum), R.arb_sums32(gg, xx, H, W, pool_sum, False)
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        assert float((a[0].double() - (gg.double() * xx.double()).sum(dim=(1, 2))).abs().max()) < 1e-4
+    dead = 0
+    for case in R.THIN_ARB_CASES:
+        if case['nomask']:
+            continue
+        i = R.thin_arb_inputs(_g(421), case)
+        r64, _ = R.thin_arb_refs(case, i)
+        live = (R.fma(i['ax'], i['as'][:, None, None], i['at'][:, None, None]) > 0)
+        dead += int((~live).all(dim=1).all(dim=1).sum())
+        assert bool((r64['g'][~live] == 0).all())
+    assert dead > 0
+
+
+@pytest.mark.parametrize('tap', range(9))
+def test_thin_one_hot_inputs_are_exact_in_every_restatement(tap):
+    for c in (R._tsh('TI', 'i16x32'), R._tsh('TI', 'i24x16'), R._tsh('TO', 'o16x32'), R._tsh('TO', 'o24x16'),
+              R._tsh('B', 'n12x20')):
+        for seed in range(3):
+            i = R.thin_onehot(c, tap, seed)
+            for route in _thin_route(c):
+                r64, r32 = R.thin_refs(c, i, route)
+                assert torch.equal(r32['y'].double(), r64['y']), (R.thin_id(c), route, seed)
+            assert int((r64['y'] != 0).sum()) >= 3, (R.thin_id(c), seed)
+
+
+def test_thin_case_tables_and_spots():
+    """every width, chunk count, n_store and prologue the issue names is in the tables; every launch-side fallback of
+    thin_takes; the spot lists cover each seam, wave boundary and quad boundary on both sides; a masked-off element
+    exists; nothing is larger than 24 x 16 ... 16 x 32 ... 8 x 48 pixels"""
+    cs = R.THIN_FWD_CASES
+    ti = [c for c in cs if c['route'] == 'TI']
+    to = [c for c in cs if c['route'] == 'TO']
+    b = [c for c in cs if c['route'] == 'B']
+    assert all(R.thin_kind(c) == 1 for c in ti) and all(R.thin_kind(c) == 0 for c in to)
+    assert not any(R.thin_falls_back(c) for c in ti + to)
+    assert set(c['Cout'] for c in ti) == set([64, 96])
+    assert set(c['n_store'] for c in ti if c['Cout'] == 64) >= set([16, 36, 64])
+    assert set(c['Cin'] // 16 for c in to) == set([2, 3, 4])
+    assert set((c['n_store'], c['y_gap']) for c in to) >= set([(4, 4), (16, 0), (16, 4), (32, 4)])
+    for group in (ti, to):
+        assert set((c['pro'], c['pro_b']) for c in group if c['pro']) == set([(1, 0), (1, 1), (2, 0), (2, 1)])
+        assert any(c['pro'] == R.PRO_NONE for c in group)
+        assert set((c['B'], c['H'], c['W']) for c in group) >= set([(1, 8, 16), (2, 16, 32), (3, 24, 16), (2, 8, 48)])
+    assert set(c['act'] for c in to) == set([0, 1, 2, 3]) and any(c['alpha'] != 1.0 for c in to)
+    assert any(c['bias'] for c in to) and any(not c['bias'] for c in to)
+    for e in R.EPI:
+        assert any(all(c[k] == v for k, v in e.items()) for c in ti + b if R.thin_kind(c) == 1), e
+    # the two product combinations of either kernel
+    assert any(c['pro'] == R.PRO_AFFINE and not c['pro_b'] and c['bias'] and c['act'] == R.ACT_RELU for c in ti)
+    assert any(c['pro'] == R.PRO_AFFINE_RELU and not c['pro_b'] and c['bias'] and c['act'] == R.ACT_TANH and
+               (c['n_store'], c['y_gap']) == (16, 0) for c in to)
+    assert any(c['Cin'] == 64 and c['pro'] == 0 and not c['bias'] and (c['n_store'], c['y_gap']) == (16, 0) for c in to)
+    # the fallbacks of thin_takes, and the shapes thin_shape leaves
+    fb = [c for c in b if R.thin_falls_back(c)]
+    for kind, key in ((0, 'res'), (0, 'mask'), (0, 'oscale'), (0, 'noise'), (1, 'oscale'), (1, 'noise')):
+        assert any(R.thin_kind(c) == kind and c[key] for c in fb), (kind, key)
+    assert any(R.thin_kind(c) == 0 and c['pool'] and c['want_y'] for c in fb)
+    assert any(R.thin_kind(c) == 0 and c['pool'] and not c['want_y'] for c in fb)
+    assert all(R.thin_form(c) == (4, 0) for c in cs) and all(R.thin_form(c, 'B') == (4, 16) for c in ti + to)
+    nt = [c for c in b if R.thin_kind(c) < 0]
+    assert set((c['H'], c['W']) for c in nt) >= set([(12, 20), (8, 8)]) and any((c['Cin'], c['Cout']) == (16, 32) for c in nt)
+    assert all(c['H'] * c['W'] <= 512 for c in cs + R.THIN_ARB_CASES)
+    assert len(set(R.thin_id(c) for c in cs)) == len(cs)
+    assert len(set(R.thin_arb_id(c) for c in R.THIN_ARB_CASES)) == len(R.THIN_ARB_CASES)
+    arb = [c for c in R.THIN_ARB_CASES if c['route'] == 'TI']
+    for v in R.ARB_VARIANTS:
+        for amax_out in (False, True):
+            assert any(all(c[k] == u for k, u in v.items()) and c['amax_out'] == amax_out and
+                       (c['skip'] is None) == ('skip' not in v) for c in arb), (v, amax_out)
+    assert any(c['route'] == 'B' and R.thin_kind(c) == 0 for c in R.THIN_ARB_CASES)
+    # a masked-off element; images 3e14 apart; the real channels alone are non-zero
+    mc = [c for c in cs if c['mask']][0]
+    i = R.thin_inputs(_g(430), mc)
+    assert bool((i['mask'] <= 0).any()) and bool((i['mask'] > 0).any())
+    i = R.thin_inputs(_g(431), R._tsh('TI', 'i24x16'))
+    m = i['x'].abs().amax(dim=(1, 2, 3))
+    assert float(m[2] / m[0]) > 1e13 and bool((i['x'][..., 3:] == 0).all()) and bool((i['w'][:, 3:] == 0).all())
+    # spots: both sides of every seam / wave boundary / quad boundary
+    for H, W, B in ((8, 16, 1), (16, 32, 2), (24, 16, 3), (8, 48, 2)):
+        sp = R.thin_spots(H, W, B)
+        rows, cols = set(s[1] for s in sp if s[0] == 0), set(s[2] for s in sp if s[0] == 0)
+        assert all(0 <= s[0] < B and 0 <= s[1] < H and 0 <= s[2] < W for s in sp)
+        for ys in range(8, H, 8):
+            assert ys - 1 in rows and ys in rows
+        for xs in range(16, W, 16):
+            assert xs - 1 in cols and xs in cols
+        for wv in range(3):
+            assert 2 * wv + 1 in rows and 2 * wv + 2 in rows
+        assert any(s[2] % 2 == 1 and (s[0], s[1], s[2] + 1) in sp for s in sp)
+        assert set([(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1)]) <= set(sp)
+        if B > 1:
+            assert (1, 0, 0) in sp and (1, H - 1, W - 1) in sp
+
+
+def test_thin_size_queries_on_the_host():
+    """pure host functions of the descriptor (no device call): a thin shape never takes K slices --
+    p2l_conv_suggest_splitk is 1 and p2l_conv_workspace_bytes 0 whatever d.splitk says; a shape thin_shape leaves
+    is sized for d.splitk as it stands; the maxima slots are blocks x 4 for thin input and 0 for thin output"""
+    import ctypes as C
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if not os.path.exists(os.path.join(root, 'pix2latent_amd', 'libp2l_hip.so')):
+        import __graft_entry__ as g
+        g.build()
+    from pix2latent_amd import _native as N
+    lib = N.lib()
+    for c in R.THIN_FWD_CASES:
+        for splitk in (1, 4):
+            d = N.P2LConv()
+            d.B, d.H, d.W, d.Cin, d.Cout, d.taps, d.ups = c['B'], c['H'], c['W'], c['Cin'], c['Cout'], 9, 0
+            d.x_ld, d.alpha, d.splitk, d.wfmt, d.form = c['Cin'] + c['x_gap'], 1.0, splitk, R.WFMT_BF16X3T, 0
+            d.n_store = d.y_ld = c['n_store']
+            kind = R.thin_kind(c)
+            if kind >= 0:
+                assert lib.p2l_conv_workspace_bytes(C.byref(d)) == 0, (R.thin_id(c), splitk)
+                assert lib.p2l_conv_suggest_splitk(C.byref(d)) == 1
+                blocks = (c['H'] // 8) * (c['W'] // 16)
+                assert lib.p2l_conv_amax_slots(C.byref(d)) == (blocks * 4 if kind == 1 else 0), R.thin_id(c)
+            elif splitk == 4:
+                # a shape thin_shape leaves is a direct launch: the query sizes the slices of d.splitk as it stands
+                assert lib.p2l_conv_workspace_bytes(C.byref(d)) == 4 * c['B'] * c['H'] * c['W'] * c['Cout'] * 4
